@@ -1,7 +1,7 @@
 """bench.py — images/sec of ONE forward+backward of UniDefenseModelEb4 (pass-1 loss of the train step,
 engine/abstract_engine.py:210-281 in the reference) at 256x256, bs=32 per GPU, fp32, synthetic inputs.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -221,6 +221,47 @@ def extra_measurements(budget_s=100):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 21           # per array: a larger one is written as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, out, params):
+    """--dump-outputs: what the timed step computed in its last step — the loss, every forward output of the model and the
+    parameter gradients — as <path>/<name>.npy, float32 (float64: the loss and the per-parameter gradient norms).  An array
+    of more than DUMP_MAX_ELEMS elements is written as the elements at indices drawn from a fixed seed, flattened (the same
+    indices in every run and build); the gradients as one such sample of all of them concatenated in parameter order."""
+    import numpy as np
+
+    def sample(t):
+        if t.numel() <= DUMP_MAX_ELEMS:
+            return t
+        idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+        return t.reshape(-1)[idx.to(t.device)]
+
+    arrays = {"loss": loss.detach().double().reshape(1)}
+
+    def walk(name, v):
+        if torch.is_tensor(v):
+            arrays[name] = sample(v.detach())
+        elif isinstance(v, dict):
+            for k, u in v.items():
+                walk(f"{name}.{k}" if name else k, u)
+        elif isinstance(v, (list, tuple)):
+            for i, u in enumerate(v):
+                walk(f"{name}.{i}", u)
+    walk("", out)
+    grads = [p.grad.detach() if p.grad is not None else torch.zeros_like(p) for p in params]
+    arrays["grad_norms"] = torch.stack([g.double().norm() for g in grads])
+    arrays["grad_sample"] = sample(torch.cat([g.reshape(-1).float() for g in grads]))
+    arrays = {k: v.cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start `python -m torch.distributed.run --nproc-per-node N` over
     this same command line as a CHILD process (never exec; nothing in this process has touched the GPU yet), relay its
@@ -332,7 +373,12 @@ def main():
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the bounded secondary measurements (the other BASELINE configs, the engine's two-pass train step)")
     ap.add_argument("--train-step", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the loss, the model's outputs and the gradients of the last timed step "
+                         "to DIR/<name>.npy (large arrays as a fixed, seeded sample; at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_measure()), flush=True)
         return
@@ -382,11 +428,12 @@ def main():
     for k_ in ("aw_triplet",):
         LOSSES[k_].n_real = bs // 2
     params = [p for p in model.parameters() if p.requires_grad]
+    last_out = [None]          # the model's outputs of the latest step (of a captured step: the tensors each replay rewrites)
 
     def step():
         for p in params:
             p.grad = None
-        out = model(x)
+        out = last_out[0] = model(x)
         loss = pass1_loss(out, tgt, bs // 2, LOSSES)
         # f16: the engine's GradScaler scale (forgery_engine.py:228), so that half gradients do not underflow
         (loss * 1024.0 if args.dtype == "f16" else loss).backward()
@@ -449,6 +496,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last_out[0], params)      # before the eager steps below replace the gradients
     bn_exchange = getattr(model, "bn_exchange", None)
     if bn_exchange is not None and bn_exchange.ok:
         bn_exchange.check()          # a rank that timed out waiting for a peer's SyncBN sums: fail loudly, no line

@@ -109,6 +109,18 @@ def run_reference_train(m, ref_loss_mod, x, tgt, rng, drop_rate, lam):
 LAMBDAS = dict(lambda_triplet=0.1, lambda_recons=0.1, lambda_freq=1.0, lambda_mask=0.1, lambda_fac=0.1)
 
 
+def record_f64_outputs(m, ref_loss_mod, x, tgt, rng, drop_rate, store):
+    """The train-mode forward outputs once more with the reference run in FLOAT64 (keys prefixed 'f64_'): how far two
+    fp32 evaluations of the deeper outputs (factorization) drift apart depends on the CPU's kernels, two float64
+    evaluations (the oracle and the reference) agree to ~5e-10 on any machine."""
+    m.double()
+    try:
+        out, _ = run_reference_train(m, ref_loss_mod, x.double(), tgt, rng, drop_rate, LAMBDAS)
+        pack_outputs(out, "f64_", store)
+    finally:
+        m.float()
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref_model, ref_loss = ref_import.import_reference()
@@ -169,6 +181,7 @@ def main():
         store[f"{variant}_grad_norms"] = np.array(norms, dtype=np.float64)
         store[f"{variant}_grad_maxabs"] = np.array(maxabs, dtype=np.float64)
         store[f"{variant}_grad_heads"] = np.stack(heads)
+    record_f64_outputs(m, ref_loss, x, tgt, rng, drop_rate, store)
     store["meta"] = np.array([n, 256, in_seed, mask_seed], dtype=np.int64)
     np.savez_compressed(os.path.join(OUT, "udeb4_train_n4.npz"), **store)
     print("wrote udeb4_train_n4.npz  (%d grads x 2 variants)" % len(names))

@@ -66,6 +66,7 @@ def main():
         store[f"{variant}_grad_norms"] = np.array(norms, dtype=np.float64)
         store[f"{variant}_grad_maxabs"] = np.array(maxabs, dtype=np.float64)
         store[f"{variant}_grad_heads"] = np.stack(heads)
+    mg.record_f64_outputs(m, ref_loss, x, tgt, rng, drop_rate, store)
     store["meta"] = np.array([n, 256, seeds[0], seeds[1]], dtype=np.int64)
     np.savez_compressed(os.path.join(mg.OUT, "udeb4_train_n8.npz"), **store)
     print("wrote udeb4_train_n8.npz  (%d grads x 2 variants, seeds %s)" % (len(names), seeds))

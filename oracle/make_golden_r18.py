@@ -59,7 +59,11 @@ def main():
         pack(m(x), store, "eval_")
     F = torch.nn.functional
     orig = F.dropout
-    for variant, lam in (("full", LAMBDAS), ("smooth", dict(LAMBDAS, lambda_recons=0.0, lambda_freq=0.0))):
+    variants = (("full", LAMBDAS), ("smooth", dict(LAMBDAS, lambda_recons=0.0, lambda_freq=0.0)))
+    # the train passes once more with the reference run in FLOAT64 (keys prefixed 'f64_'): the scalar sf_coef gradients are
+    # sums with heavy cancellation whose fp32 value depends on the CPU's kernels, their float64 value does not
+    for prefix, dt, (variant, lam) in [(p, d, v) for p, d in (("", torch.float32), ("f64_", torch.float64)) for v in variants]:
+        m.to(dt)
         queue = [("dec_keep", 0.2), ("emb_keep", DROP), ("feat_keep", DROP)]
 
         def fake_dropout(inp, p=0.5, training=True, inplace=False):
@@ -70,7 +74,7 @@ def main():
         F.dropout = fake_dropout
         try:
             m.train()
-            out = m(x)
+            out = m(x.to(dt))
         finally:
             F.dropout = orig
         assert not queue
@@ -85,23 +89,23 @@ def main():
         m.zero_grad()
         total.backward()
         if variant == "full":
-            pack(out, store, "train_")
+            pack(out, store, prefix + "train_")
         for k, v in (("total_loss", total), ("cls_loss", cls), ("triplet_loss", trip), ("real_rec_loss", real_rec),
                      ("real_freq_loss", real_freq)):
-            store[f"{variant}_loss_{k}"] = np.array(v.item())
+            store[f"{prefix}{variant}_loss_{k}"] = np.array(v.item())
         names, norms, heads = [], [], []
         for k, p in m.named_parameters():
             if p.grad is None:
                 continue
             names.append(k)
             norms.append(p.grad.double().norm().item())
-            h = torch.zeros(8)
+            h = torch.zeros(8, dtype=dt)
             f = p.grad.flatten()[:8]
             h[: f.numel()] = f
             heads.append(h.numpy())
         store["grad_names"] = np.array(names)
-        store[f"{variant}_grad_norms"] = np.array(norms)
-        store[f"{variant}_grad_heads"] = np.stack(heads)
+        store[f"{prefix}{variant}_grad_norms"] = np.array(norms)
+        store[f"{prefix}{variant}_grad_heads"] = np.stack(heads)
     store["meta"] = np.array([N, SIZE, IN_SEED, MASK_SEED], dtype=np.int64)
     np.savez_compressed(os.path.join(OUT, "udr18_n8.npz"), **store)
     print("wrote udr18_n8.npz", len(names), "grads")
