@@ -467,7 +467,12 @@ int ud_affine3(const float* x, const float* M, float* out, int N, int HW, ud_str
  * The accumulators are caller-owned fp64 buffers that must be zero before the producing kernel runs.
  * Data shape arguments (G, R, C): G samples x R pixels x C channels (C % 4 == 0).
  * gate_alpha / gate_mode: an optional scalar factor read on the device: 0 none, 1 sigmoid(alpha[0]),
- * 2 1 - sigmoid(alpha[0])  (the sf_coef mix of exp.py:61-65 carried into the backward kernels). */
+ * 2 1 - sigmoid(alpha[0])  (the sf_coef mix of exp.py:61-65 carried into the backward kernels).
+ * EVAL FORM: sum == NULL with running_mean and running_var both set is an eval-mode BatchNorm: mean = running_mean and
+ * var = running_var (the fixed affine map of nn.BatchNorm2d.eval()); the running buffers are only read, never written,
+ * and sumsq / inv_count / unbias / momentum are ignored.  Every forward consumer takes it; every BACKWARD entry point
+ * (ud_coldot_bn, ud_normbwd_*, ud_se_scale_bwd_bn, ud_dwconv_bwd_data_bn, ud_dwtile_wgrad, ud_dwtile_bwd, ud_irfft2_dwbwd,
+ * ud_pw_bwd_fused, ud_pj_bwd_fused_a / _b) returns UD_EINVAL for it. */
 typedef struct {
     const double* sum;       /* [G][C] sum of x over the rows (and ranks) the statistics cover */
     const double* sumsq;     /* [G][C] sum of x^2 */
@@ -479,7 +484,7 @@ typedef struct {
     float momentum;
     int act;                 /* activation applied after the affine map: 0 none, 1 swish */
     int G;                   /* groups of the STATISTICS: 1 = batch norm (one set for all samples) */
-    float* running_mean;     /* optional [C]: updated once by the consuming kernel that is handed them */
+    float* running_mean;     /* optional [C]: updated once by the consuming kernel that is handed them (eval form: read) */
     float* running_var;
 } ud_bn_ref;
 
@@ -586,6 +591,20 @@ int ud_pj_fwd_fused_ok(int CE, int CO, int HW);
 int ud_pj_fwd_fused(const float* d, const ud_bn_ref* bn, const float* s, const float* w, int N, int HW, int CE, int CO, float* p,
                     double* sum, double* sumsq, ud_stream_t stream);
 long ud_pj_bwd_fused_grid(int N, int HW, int CE, int CO);
+/* Eval-mode MBConv, expand conv + BN0 + swish + depthwise conv + BN1 + swish in ONE pass over the thin block input
+ * (csrc/evalblk.hip): x [N][H][W][Ci], we [CE][Ci] (the expand conv), wt [K*K][CE] (tap-major depthwise weights), bn0 / bn1
+ * in the EVAL FORM of ud_bn_ref (anything else is UD_EINVAL).  e = swish(bn0(x we^T)) is formed per output tile from its input
+ * halo in LDS and never written; the depthwise conv has stride `stride` and SAME padding (pad_t, pad_l; e is zero outside the
+ * image).  d [N][Ho][Wo][CE] receives z = swish(bn1(dw)) (out_act = 1) or the raw depthwise output dw (out_act = 0, the input
+ * ud_pj_fwd_fused applies BN1 to); part [N][tiles][CE] (tiles = ud_mb_eval_dw_tiles) receives per output tile the sum of z,
+ * the SE squeeze (ud_group_colsum over the tiles gives the mean).  fp32 FMA throughout, no atomics: results are
+ * deterministic.  x and we 16-byte aligned.  ud_mb_eval_dw_ok: the (Ci, CE, K, stride) it takes (Ci % 4 == 0,
+ * CE % 16 == 0, K == 3, stride 1 or 2). */
+int ud_mb_eval_dw_ok(int Ci, int CE, int K, int stride);
+long ud_mb_eval_dw_tiles(int Ho, int Wo, int stride);
+int ud_mb_eval_dw(const float* x, const float* we, const ud_bn_ref* bn0, const float* wt, const ud_bn_ref* bn1, float* d, float* part,
+                  int N, int H, int W, int Ci, int CE, int Ho, int Wo, int K, int stride, int pad_t, int pad_l, int out_act,
+                  ud_stream_t stream);
 int ud_pj_bwd_fused_a(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* w, int N, int HW, int CE,
                       int CO, float* dw, double* dgate, float* part, ud_stream_t stream);
 int ud_pj_bwd_fused_b(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,

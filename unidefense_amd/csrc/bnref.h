@@ -15,18 +15,18 @@ __device__ __forceinline__ void atomic_add_f64(double* p, double v) { unsafeAtom
 struct Bn4 { f32x4 mu, is, ga, be; };
 
 // Coefficients of channel quad c4 from the fp64 sums; the designated thread of a kernel (update == true for exactly
-// one thread per channel quad per launch) also moves the running statistics (nn.BatchNorm2d training forward).
+// one thread per channel quad per launch) also moves the running statistics (nn.BatchNorm2d training forward).  The eval form
+// (sum == NULL) takes the running statistics as the moments and never writes them.
 __device__ __forceinline__ Bn4 bn_load(const ud_bn_ref& b, int g, int C4, int c4, bool update) {
     Bn4 o;
     const long i0 = ((long)(b.G == 1 ? 0 : g) * C4 + c4) * 4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const double m = b.sum[i0 + e] * b.inv_count;
-        double v = b.sumsq[i0 + e] * b.inv_count - m * m;
-        if (v < 0.0) v = 0.0;
+        double m, v;
+        ud_bn_moments(b, i0 + e, c4 * 4 + e, m, v);
         o.mu[e] = (float)m;
         o.is[e] = rsqrtf((float)(v + (double)b.eps));
-        if (update && b.running_mean) {
+        if (update && b.sum && b.running_mean) {
             const int c = c4 * 4 + e;
             b.running_mean[c] = (1.f - b.momentum) * b.running_mean[c] + b.momentum * (float)m;
             b.running_var[c] = (1.f - b.momentum) * b.running_var[c] + b.momentum * (float)(v * b.unbias);

@@ -758,6 +758,7 @@ int ud_dwtile(const void* src, const ud_bn_ref* bn_in, const float* wt, void* ou
 int ud_dwtile_wgrad(const void* src, const ud_bn_ref* bn_in, const void* dy, const float* gate_alpha, int gate_mode,
                     float* dwt, float* part, long part_rows, int N, int Hs, int Ws, int C, int Ho, int Wo, int K, int P_t,
                     int P_l, int stride, int f16, ud_stream_t stream) {
+    if (ud_bn_eval_form(bn_in)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!tile_args_ok(N, Hs, Ws, C, Ho, Wo, K) || !src || !dy || !part || part_rows < 1) return UD_EINVAL;
     if (bn_in && bn_in->G != 1) return UD_EINVAL;
     if (stride != 1 && stride != 2) return UD_EINVAL;
@@ -781,6 +782,7 @@ int ud_dwtile_wgrad(const void* src, const ud_bn_ref* bn_in, const void* dy, con
 int ud_dwtile_bwd(const void* dy, const void* x, const ud_bn_ref* bn, const float* wt, const float* gate_alpha, int gate_mode,
                   const void* add, void* dz, float* dwt, float* wpart, long part_rows, double* s1, double* s2, double* ws,
                   int N, int H, int W, int C, int K, int P_t, int P_l, int f16, ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!tile_args_ok(N, H, W, C, H, W, K) || !dy || !x || !wt || !dz || !wpart || part_rows < 1) return UD_EINVAL;
     if (P_t < 0 || P_t > K - 1 || P_l < 0 || P_l > K - 1) return UD_EINVAL;
     if (bn && (bn->G != 1 || !s1 || !s2 || !ws)) return UD_EINVAL;

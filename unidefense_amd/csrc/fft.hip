@@ -318,14 +318,13 @@ __global__ __launch_bounds__(NT) void rfft2_kernel(const T* __restrict__ x, T* _
         for (int w = 0; w < S; ++w) re[brev<S>(w)] = (float)src[(long)w * C];
         float mu = 0.f, is = 1.f, ga = 1.f, be = 0.f;
         if (EX && has_bn) {
-            const double m = bn.sum[chl] * bn.inv_count;
-            double vv = bn.sumsq[chl] * bn.inv_count - m * m;
-            if (vv < 0.0) vv = 0.0;
+            double m, vv;
+            ud_bn_moments(bn, chl, chl, m, vv);          // (the eval form: the running statistics, never written)
             mu = (float)m;
             is = (float)(1.0 / sqrt(vv + (double)bn.eps));
             ga = bn.gamma[chl];
             be = bn.beta[chl];
-            if (n == 0 && q == 0 && cok && bn.running_mean) {          // one thread per channel
+            if (n == 0 && q == 0 && cok && bn.sum && bn.running_mean) {          // one thread per channel
                 bn.running_mean[ch] = (1.f - bn.momentum) * bn.running_mean[ch] + bn.momentum * (float)m;
                 bn.running_var[ch] = (1.f - bn.momentum) * bn.running_var[ch] + bn.momentum * (float)(vv * bn.unbias);
             }
@@ -670,9 +669,8 @@ __global__ __launch_bounds__(NT, 4) void irfft2_dwbwd_kernel(const T* __restrict
     // ---- BatchNorm in front of the conv: coefficients of this channel
     float mu, is, ga, be;
     {
-        const double m = bn.sum[chl] * bn.inv_count;
-        double vv = bn.sumsq[chl] * bn.inv_count - m * m;
-        if (vv < 0.0) vv = 0.0;
+        double m, vv;
+        ud_bn_moments(bn, chl, chl, m, vv);          // (the eval form: the running statistics, never written)
         mu = (float)m;
         is = (float)(1.0 / sqrt(vv + (double)bn.eps));
         ga = bn.gamma[chl];
@@ -897,14 +895,13 @@ __global__ __launch_bounds__(NT2) void rows_fwd_kernel(const T* __restrict__ x, 
     if (ch >= C || h >= S) return;
     float mu = 0.f, is = 1.f, ga = 1.f, be = 0.f;
     if (EX && has_bn) {
-        const double m = bn.sum[ch] * bn.inv_count;
-        double vv = bn.sumsq[ch] * bn.inv_count - m * m;
-        if (vv < 0.0) vv = 0.0;
+        double m, vv;
+        ud_bn_moments(bn, ch, ch, m, vv);          // (the eval form: the running statistics, never written)
         mu = (float)m;
         is = (float)(1.0 / sqrt(vv + (double)bn.eps));
         ga = bn.gamma[ch];
         be = bn.beta[ch];
-        if (n == 0 && h == 0 && bn.running_mean) {          // one thread per channel
+        if (n == 0 && h == 0 && bn.sum && bn.running_mean) {          // one thread per channel
             bn.running_mean[ch] = (1.f - bn.momentum) * bn.running_mean[ch] + bn.momentum * (float)m;
             bn.running_var[ch] = (1.f - bn.momentum) * bn.running_var[ch] + bn.momentum * (float)(vv * bn.unbias);
         }
@@ -1176,14 +1173,13 @@ __global__ __launch_bounds__(NTW) void rfft2_wave_kernel(const T* __restrict__ x
     }
     float mu = 0.f, is = 1.f, ga = 1.f, be = 0.f;
     if (EX && has_bn) {
-        const double m = bn.sum[chl] * bn.inv_count;
-        double vv = bn.sumsq[chl] * bn.inv_count - m * m;
-        if (vv < 0.0) vv = 0.0;
+        double m, vv;
+        ud_bn_moments(bn, chl, chl, m, vv);          // (the eval form: the running statistics, never written)
         mu = (float)m;
         is = (float)(1.0 / sqrt(vv + (double)bn.eps));
         ga = bn.gamma[chl];
         be = bn.beta[chl];
-        if (n == 0 && wave == 0 && hh == 0 && cok && bn.running_mean) {          // one thread per channel
+        if (n == 0 && wave == 0 && hh == 0 && cok && bn.sum && bn.running_mean) {          // one thread per channel
             bn.running_mean[ch] = (1.f - bn.momentum) * bn.running_mean[ch] + bn.momentum * (float)m;
             bn.running_var[ch] = (1.f - bn.momentum) * bn.running_var[ch] + bn.momentum * (float)(vv * bn.unbias);
         }
@@ -1562,6 +1558,7 @@ int ud_rfft2_ex_plane_half(const void* x, uint16_t* plane, long panel_stride, fl
 int ud_irfft2_dwbwd(const void* Y, int N, int S, int C, float scale, float w_interior, const void* dd, const void* x,
                     const ud_bn_ref* bn, const float* wt, int K, const float* gate_alpha, int gate_mode, void* dz, double* s1,
                     double* s2, double* s3, float* wpart, float* wacc, int f16, ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (N < 1 || C < 1 || !Y || !dd || !x || !bn || bn->G != 1 || !wt || !dz || !s1 || !s2 || (!wpart && !wacc)) return UD_EINVAL;
     if (gate_mode < 0 || gate_mode > 2 || (gate_mode != 0 && !gate_alpha)) return UD_EINVAL;
     hipStream_t st = (hipStream_t)stream;

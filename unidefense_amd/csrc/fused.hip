@@ -990,6 +990,7 @@ int ud_colsum_bn_amax(const void* x, const ud_bn_ref* bn, int G, int R, int C, d
 
 int ud_coldot_bn(const void* dy, const void* x, const ud_bn_ref* bn, int G, int R, int C, double* out, double* ws,
                  int f16, ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!shape_ok(G, R, C) || !x || !dy || !bn || !out) return UD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     RedPlan pl = plan_reduce(G, R, C, true, ws);
@@ -1079,6 +1080,7 @@ int ud_se_scale_bn_plane_half(const void* x, const ud_bn_ref* bn, const float* s
 int ud_normbwd_sums(const void* x, const void* dy, const float* keep, float inv_keep, const ud_bn_ref* bn,
                     int dy_is_dz, int G, int R, int C, double* s1, double* s2, double* s3, double* ws, int f16,
                     ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!shape_ok(G, R, C) || !x || !dy || !bn || !s1 || !s2 || bn->G != 1) return UD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     RedPlan pl = plan_reduce(G, R, C, false, ws);
@@ -1093,6 +1095,7 @@ int ud_normbwd_apply(const void* x, const void* dy, const float* keep, float inv
                      int dy_is_dz, const double* s1, const double* s2, const double* s1_local,
                      const double* s2_local, int G, int R, int C, void* dx, float* dgamma, float* dbeta, int f16,
                      uint32_t* absmax, ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!shape_ok(G, R, C) || !x || !dy || !bn || !s1 || !s2 || !dx || bn->G != 1) return UD_EINVAL;
     if ((dgamma || dbeta) && (!s1_local || !s2_local)) return UD_EINVAL;
     RedGeom q = geom_ew(G, R, C);
@@ -1110,6 +1113,7 @@ int ud_normbwd_apply_planes(const float* x, const float* dy, const float* keep, 
                             const double* s2_local, const double* energy, int G, int R, int C, uint16_t* planes,
                             long panel_stride, long plane_stride, float* inv_scale, float* dgamma, float* dbeta,
                             ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!shape_ok(G, R, C) || !x || !dy || !bn || !s1 || !s2 || !energy || !planes || !inv_scale || bn->G != 1 || !bn->gamma)
         return UD_EINVAL;
     if ((dgamma || dbeta) && (!s1_local || !s2_local)) return UD_EINVAL;
@@ -1128,6 +1132,7 @@ int ud_normbwd_apply_plane_half(const void* x, const void* dy, const float* keep
                                 int dy_is_dz, const double* s1, const double* s2, const double* s1_local,
                                 const double* s2_local, int G, int R, int C, uint16_t* plane, long panel_stride,
                                 float* inv_scale, float* dgamma, float* dbeta, ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!shape_ok(G, R, C) || !x || !dy || !bn || !s1 || !s2 || !plane || !inv_scale || bn->G != 1) return UD_EINVAL;
     if ((dgamma || dbeta) && (!s1_local || !s2_local)) return UD_EINVAL;
     if (panel_stride < 32L * G * R) return UD_EINVAL;
@@ -1144,6 +1149,7 @@ int ud_normbwd_apply_mix(const void* x, const void* dz, const ud_bn_ref* bn, con
                          const double* s1_local, const double* s2_local, const void* diff, int G, int R, int C,
                          void* dd, double* dalpha_acc, float* dgamma, float* dbeta, double* energy, int f16,
                          ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!shape_ok(G, R, C) || !x || !dz || !bn || !s1 || !s2 || !dd || !diff || !dalpha_acc || bn->G != 1)
         return UD_EINVAL;
     if ((dgamma || dbeta) && (!s1_local || !s2_local)) return UD_EINVAL;
@@ -1194,6 +1200,7 @@ int ud_se_bwd_b(const double* ds1_acc, const float* s1, const float* Wr, const d
 int ud_se_scale_bwd_bn(const void* dc, const void* x, const ud_bn_ref* bn, const float* s, const float* dpool,
                        float inv_hw, void* dz, double* s1, double* s2, double* ws, int G, int R, int C, int f16,
                        ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!shape_ok(G, R, C) || !dc || !x || !bn || !s || !dpool || !dz || !s1 || !s2 || bn->G != 1) return UD_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     RedPlan pl = plan_reduce(G, R, C, false, ws);
@@ -1257,6 +1264,7 @@ int ud_dwconv_bwd_data_bn(const void* dy, const float* gate_alpha, int gate_mode
                           const void* x, const ud_bn_ref* bn, void* dz, double* s1, double* s2, double* ws, int N,
                           int H, int W, int C, int Ho, int Wo, int K, int stride, int pad_t, int pad_l, int f16,
                           ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!bn) return UD_EINVAL;
     UD_STORAGE_DISPATCH(f16, return dw_bwd_data_launch<T>((const T*)dy, gate_alpha, gate_mode, wt, (const T*)add,
                                                           (const T*)x, bn, (T*)dz, s1, s2, ws, N, H, W, C, Ho, Wo, K,

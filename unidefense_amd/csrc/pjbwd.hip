@@ -66,8 +66,10 @@ struct PjArgs {
     double* dgate;             // [N][CE] (kernel A) += sum_hw dc a
     double* s1;                // [CE] (kernel B) += sum dz, sum dz xhat
     double* s2;
-    const double* bsum;        // BatchNorm-1 statistics of d
+    const double* bsum;        // BatchNorm-1 statistics of d (NULL: the eval form, moments from rmean / rvar)
     const double* bsumsq;
+    const float* rmean;
+    const float* rvar;
     const float* gamma;
     const float* beta;
     double inv_count;
@@ -93,9 +95,15 @@ __device__ __forceinline__ float act_grad_sel(float z, bool swish) {
 // coefficients of channels c0 .. c0 + CC - 1
 __device__ __forceinline__ void load_coef(const PjArgs& a, float* coef, int c0, int CC, int tid) {
     for (int c = tid; c < CC; c += NTH) {
-        const double m = a.bsum[c0 + c] * a.inv_count;
-        double v = a.bsumsq[c0 + c] * a.inv_count - m * m;
-        if (v < 0.0) v = 0.0;
+        double m, v;
+        if (a.bsum) {
+            m = a.bsum[c0 + c] * a.inv_count;
+            v = a.bsumsq[c0 + c] * a.inv_count - m * m;
+            if (v < 0.0) v = 0.0;
+        } else {          // the eval form of ud_bn_ref (ud_common.h: ud_bn_moments)
+            m = (double)a.rmean[c0 + c];
+            v = (double)a.rvar[c0 + c];
+        }
         coef[c] = (float)m;
         coef[CC + c] = rsqrtf((float)(v + (double)a.eps));          // (bnref.h: bn_load's own form)
         coef[2 * CC + c] = a.gamma[c0 + c];
@@ -516,6 +524,8 @@ struct PjFwdArgs {
     double* sumsq;
     const double* bsum;
     const double* bsumsq;
+    const float* rmean;
+    const float* rvar;
     const float* gamma;
     const float* beta;
     double inv_count;
@@ -561,7 +571,7 @@ __global__ __launch_bounds__(NTH, 2) void pj_fwd_kernel(PjFwdArgs a) {
     prefetch(t0);
     {          // (CE > NTH never happens here: one pass of the loop)
         PjArgs ca;
-        ca.bsum = a.bsum; ca.bsumsq = a.bsumsq; ca.gamma = a.gamma; ca.beta = a.beta; ca.inv_count = a.inv_count; ca.eps = a.eps;
+        ca.bsum = a.bsum; ca.bsumsq = a.bsumsq; ca.rmean = a.rmean; ca.rvar = a.rvar; ca.gamma = a.gamma; ca.beta = a.beta; ca.inv_count = a.inv_count; ca.eps = a.eps;
         load_coef(ca, coef, 0, CE, tid);
     }
     // Wp as the B operand: lane holds Wp[n = 16 nb + u][k = 32 ks + 8 g + j] (k-contiguous in memory)
@@ -670,12 +680,12 @@ int chunk_of(int CE, int CO) {
 }
 
 bool args_ok(const void* d, const void* dp, const ud_bn_ref* bn, const void* s, const void* w, int N, int HW, int CE, int CO) {
-    return d && dp && bn && s && w && N >= 1 && HW >= R && ud_pj_bwd_fused_ok(CE, CO, HW) && bn->G == 1 && bn->gamma && bn->beta;
+    return d && dp && bn && !ud_bn_eval_form(bn) && s && w && N >= 1 && HW >= R && ud_pj_bwd_fused_ok(CE, CO, HW) && bn->G == 1 && bn->gamma && bn->beta;
 }
 
 void fill(PjArgs& a, const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* w, int N, int HW, int CE, int CO) {
     a.d = d; a.dp = dp; a.w = w; a.s = s;
-    a.bsum = bn->sum; a.bsumsq = bn->sumsq; a.gamma = bn->gamma; a.beta = bn->beta;
+    a.bsum = bn->sum; a.bsumsq = bn->sumsq; a.rmean = bn->running_mean; a.rvar = bn->running_var; a.gamma = bn->gamma; a.beta = bn->beta;
     a.inv_count = bn->inv_count; a.eps = bn->eps; a.act = bn->act; a.HW = HW;
     a.M = (long)N * HW; a.tiles = a.M / R;
     a.gc = (int)(ud_pj_bwd_fused_grid(N, HW, CE, CO) / (CE / chunk_of(CE, CO)));
@@ -698,11 +708,11 @@ long ud_pj_bwd_fused_grid(int N, int HW, int CE, int CO) {
 
 int ud_pj_fwd_fused(const float* d, const ud_bn_ref* bn, const float* s, const float* w, int N, int HW, int CE, int CO, float* p,
                      double* sum, double* sumsq, ud_stream_t stream) {
-    if (!d || !bn || !s || !w || !p || N < 1 || !ud_pj_fwd_fused_ok(CE, CO, HW) || bn->G != 1 || !bn->gamma || !bn->beta || (!sum != !sumsq))
+    if (!d || !bn || (!bn->sum && !ud_bn_eval_form(bn)) || !s || !w || !p || N < 1 || !ud_pj_fwd_fused_ok(CE, CO, HW) || bn->G != 1 || !bn->gamma || !bn->beta || (!sum != !sumsq))
         return UD_EINVAL;
     PjFwdArgs a;
     a.d = d; a.w = w; a.s = s; a.p = p; a.sum = sum; a.sumsq = sumsq;
-    a.bsum = bn->sum; a.bsumsq = bn->sumsq; a.gamma = bn->gamma; a.beta = bn->beta;
+    a.bsum = bn->sum; a.bsumsq = bn->sumsq; a.rmean = bn->running_mean; a.rvar = bn->running_var; a.gamma = bn->gamma; a.beta = bn->beta;
     a.inv_count = bn->inv_count; a.eps = bn->eps; a.act = bn->act; a.HW = HW;
     a.M = (long)N * HW; a.tiles = a.M / R;
     const int grid = (int)ud_pj_bwd_fused_grid(N, HW, CE, CO);

@@ -380,6 +380,7 @@ long ud_pw_bwd_fused_grid(long M) {
 int ud_pw_bwd_fused(const float* e, const float* dz, const ud_bn_ref* bn, const double* s1, const double* s2, const double* s1_local,
                     const double* s2_local, const float* x, const float* w, const float* add, long M, int CE, int CIN, float* dx,
                     float* dw, float* part, float* dgamma, float* dbeta, ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
     if (!e || !dz || !bn || !s1 || !s2 || !x || !w || !dx || !dw || !part || M < 1 || !ud_pw_bwd_fused_ok(CE, CIN) || bn->G != 1 ||
         !bn->gamma)
         return UD_EINVAL;

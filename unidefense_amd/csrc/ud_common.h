@@ -12,6 +12,23 @@
 
 static inline int ud_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// ud_bn_ref in its eval form (include/unidefense_hip.h: sum == NULL with both running buffers set): backward entry points
+// refuse it, forward consumers read the moments through ud_bn_moments
+static inline bool ud_bn_eval_form(const ud_bn_ref* b) { return b && !b->sum && b->running_mean && b->running_var; }
+
+// (mean, biased variance) of one channel of a ud_bn_ref: i indexes the [G][C] sums, c the [C] running buffers.  Eval form:
+// the running buffers as they are (never written by a consumer); training form: the fp64 sums.
+__device__ __forceinline__ void ud_bn_moments(const ud_bn_ref& b, long i, int c, double& m, double& v) {
+    if (!b.sum) {
+        m = (double)b.running_mean[c];
+        v = (double)b.running_var[c];
+        return;
+    }
+    m = b.sum[i] * b.inv_count;
+    v = b.sumsq[i] * b.inv_count - m * m;
+    if (v < 0.0) v = 0.0;
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));

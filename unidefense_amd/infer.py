@@ -1,0 +1,89 @@
+"""Graph-captured inference forward: InferenceRunner.
+
+The eval-mode forward (what TrainEngine.test() / .validate() run, and what a deployed detector runs) replayed as ONE hipGraph
+per (batch, size): the first call runs one eager warm-up (it settles the on-line GEMM tuner and every lazily made workspace
+for the shape), the second captures `model(x)` under no_grad into a graph with static input and output buffers, and every
+call copies the input in and replays.  K.begin_forward runs inside the graph and every BatchNorm reads the module's running
+buffers in place, so a runner captured before an optimizer step (or a load_state_dict, or a change of running statistics)
+gives the updated model's output afterwards without being rebuilt.
+
+UDEB4's block group 1 takes the eval-mode node (model.unidefense._mbconv_eval: the expand conv inside the depthwise pass,
+csrc/evalblk.hip) during the runner's warm-up and capture; every other layer, and the ResNet variants as a whole, are captured
+as their eager eval forward.  fp32 storage only.
+"""
+import contextlib
+
+import torch
+
+_MAX_RUNNERS = 4          # captured keys a model keeps (model.inference_runner), oldest evicted first
+
+
+@contextlib.contextmanager
+def _eval_nodes(model):
+    prev = model.__dict__.get("_eval_fused", False)
+    model.__dict__["_eval_fused"] = True
+    try:
+        yield
+    finally:
+        model.__dict__["_eval_fused"] = prev
+
+
+class InferenceRunner:
+    """runner = InferenceRunner(model, batch, size); out = runner(x) with x [batch, 3, size, size] fp32 on the model's GPU;
+    out is the dict model(x) returns under no_grad ({"cls_out", "rec", "loss_dict"}), held in the runner's static buffers: the
+    next call overwrites it (clone what must outlive it)."""
+
+    def __init__(self, model, batch, size):
+        from .model import MODEL
+        if not isinstance(model, tuple(MODEL.values())):
+            raise ValueError(f"InferenceRunner takes a UDEB4 / UDR18 / UDR50 model, got {type(model).__name__}")
+        if model.training:
+            raise ValueError("InferenceRunner needs model.eval(): the captured forward reads the running statistics")
+        p = next(model.parameters())
+        if not p.is_cuda:
+            raise ValueError("InferenceRunner needs a cuda model")
+        self.model, self.batch, self.size = model, int(batch), int(size)
+        self.shape = (self.batch, 3, self.size, self.size)
+        self.device = p.device
+        self.calls = 0
+        self.graph = self.x = self.out = None
+
+    def _check(self, x):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError("InferenceRunner takes a cuda tensor")
+        if tuple(x.shape) != self.shape or x.dtype != torch.float32:
+            raise ValueError(f"input {tuple(x.shape)} {x.dtype} differs from the runner's key {self.shape} torch.float32")
+        if self.model.training:
+            raise ValueError("the model is in training mode: call model.eval() before the runner")
+
+    @torch.no_grad()
+    def __call__(self, x):
+        self._check(x)
+        self.calls += 1
+        if self.calls == 1:
+            with _eval_nodes(self.model):           # eager warm-up of the same forward the graph records
+                return self.model(x.contiguous())
+        if self.graph is None:
+            self.x = x.detach().clone().contiguous()
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with _eval_nodes(self.model), torch.cuda.graph(g):
+                self.out = self.model(self.x)
+            self.graph = g
+        else:
+            self.x.copy_(x)
+        self.graph.replay()
+        return self.out
+
+
+def inference_runner(model, batch, size):
+    """The model's runner for (batch, size), made on first use; a model keeps at most _MAX_RUNNERS of them."""
+    runners = model.__dict__.setdefault("_ud_runners", {})
+    key = (int(batch), int(size))
+    r = runners.pop(key, None)
+    if r is None:
+        r = InferenceRunner(model, batch, size)
+        while len(runners) >= _MAX_RUNNERS:
+            del runners[next(iter(runners))]
+    runners[key] = r                                 # most recently used last
+    return r

@@ -2460,6 +2460,51 @@ class DeferredBN:
         return r
 
 
+class EvalBN:
+    """An eval-mode BatchNorm handed to the deferred-BatchNorm consumers: the EVAL FORM of ud_bn_ref (sum = NULL; mean and
+    variance are the module's running buffers, read in place by the kernel and never written — a captured graph follows
+    later changes of them).  `mod` is an nn.BatchNorm2d; act: 0 none, 1 swish."""
+
+    def __init__(self, mod, act):
+        self.mod, self.act, self.C = mod, int(act), mod.num_features
+        if mod.weight is not None:
+            self.gamma, self.beta = mod.weight, mod.bias
+        else:
+            self.gamma = torch.ones(self.C, dtype=torch.float32, device=mod.running_mean.device)
+            self.beta = torch.zeros(self.C, dtype=torch.float32, device=mod.running_mean.device)
+
+    def ref(self, update=False):
+        """ctypes struct for a kernel call (update is accepted for DeferredBN's signature and ignored)"""
+        m = self.mod
+        r = BnRef()
+        r.sum = r.sumsq = None
+        r.gamma, r.beta = self.gamma.data_ptr(), self.beta.data_ptr()
+        r.inv_count, r.unbias = 0.0, 1.0
+        r.eps, r.momentum, r.act, r.G = float(m.eps), 0.0, self.act, 1
+        r.running_mean, r.running_var = m.running_mean.data_ptr(), m.running_var.data_ptr()
+        return r
+
+
+def mb_eval_dw_ok(Ci, CE, k, stride):
+    """does ud_mb_eval_dw take an eval-mode block with these (input channels, expanded channels, kernel, stride)?"""
+    return _lib.call("ud_mb_eval_dw_ok", int(Ci), int(CE), int(k), int(stride)) == 1
+
+
+def mb_eval_dw(x, we2, bn0, wt, bn1, k, stride, pad_t, pad_l, Ho, Wo, out_act=True):
+    """Eval-mode expand conv + BN0 + swish + depthwise conv + BN1 + swish in one pass over x [N,H,W,Ci] (csrc/evalblk.hip);
+    bn0 / bn1: EvalBN.  Returns (d [N,Ho,Wo,CE]: swish(bn1(dw)) if out_act else the raw dw, pool [N,CE]: the mean of
+    swish(bn1(dw)) over the pixels, the SE squeeze)."""
+    _chk(x, we2, wt)
+    N, H, W, Ci = x.shape
+    CE = we2.shape[0]
+    tiles = _call("ud_mb_eval_dw_tiles", Ho, Wo, stride)
+    d = empty((N, Ho, Wo, CE), x)
+    part = empty((N, tiles, CE), x)
+    _call("ud_mb_eval_dw", _p(x), _p(we2), C.byref(bn0.ref()), _p(wt), C.byref(bn1.ref()), _p(d), _p(part), N, H, W, Ci, CE, Ho, Wo,
+          k, stride, pad_t, pad_l, 1 if out_act else 0, _stream())
+    return d, group_colsum(part.view(N * tiles, CE), N, tiles, 1.0 / (Ho * Wo))
+
+
 def _pd(t, off_doubles=0):
     return C.c_void_p(t.data_ptr() + 8 * off_doubles)
 

@@ -254,6 +254,11 @@ class UniDefenseModelEb4(nn.Module):
         if extractor_weights is not None:
             self.load_backbone_weights(extractor_weights)
 
+    def inference_runner(self, batch, size):
+        """The graph-captured eval forward for [batch, 3, size, size] inputs (unidefense_amd/infer.py: InferenceRunner)."""
+        from ..infer import inference_runner
+        return inference_runner(self, batch, size)
+
     # -- pretrained backbone (model/efficientnet/utils.py:589-634): missing sf_coef / freq_conv keys tolerated
     def load_backbone_weights(self, path):
         sd = torch.load(path, map_location="cpu")
@@ -347,6 +352,45 @@ class UniDefenseModelEb4(nn.Module):
                 x = T.residual(tape, x, inp)
         return x
 
+    # widest block input the eval-mode node takes: the expand conv runs on the FMA pipe inside ud_mb_eval_dw, which pays at the
+    # thin block group 1 (24 / 32 inputs) but not at the last group (272 / 448 inputs: 729 us per block at bs 96 on 8 x 8 maps,
+    # profiles/r07/infer.txt), where the expand GEMM on the matrix pipe + the composed kernels stay
+    EVAL_NODE_MAX_CIN = 32
+
+    @classmethod
+    def _eval_block_ok(cls, blk):
+        sp = blk.spec
+        return (sp.expand != 1 and sp.sf_norm is None and sp.cin <= cls.EVAL_NODE_MAX_CIN
+                and K.mb_eval_dw_ok(sp.cin, sp.cexp, sp.k, sp.stride))
+
+    def _mbconv_eval(self, x, blk):
+        """MBConvBlock.forward in eval mode on the eval-form BatchNorms (kernels.EvalBN): ud_mb_eval_dw makes d and the SE
+        squeeze from the thin input (the expanded tensor is never written), then the SE gate, the project conv and BN2 +
+        the residual — ud_pj_fwd_fused (gate and BN1 applied on load) + ud_residual_bn where the project pair is built for it,
+        ud_se_scale_fwd + the GEMM + ud_residual_bn elsewhere."""
+        sp = blk.spec
+        N, H, W, Ci = x.shape
+        k, s = sp.k, sp.stride
+        pl, pr, pt, pb = sp.pad
+        Ho = (H + pt + pb - k) // s + 1
+        Wo = (W + pl + pr - k) // s + 1
+        CE, Co, HW = sp.cexp, sp.cout, Ho * Wo
+        w = blk._depthwise_conv.weight
+        ent = T.DW_WT.get(id(w))
+        wt = ent[2] if (ent is not None and ent[0] is w) else w.view(CE, k * k).t().contiguous()
+        bn1 = K.EvalBN(blk._bn1, 1)
+        w2 = blk._project_conv.weight.view(Co, CE)
+        pj = K.project_fwd_fused_ok(x, w2, HW)
+        d, pool = K.mb_eval_dw(x, blk._expand_conv.weight.view(CE, Ci), K.EvalBN(blk._bn0, 1), wt, bn1, k, s, pt, pl, Ho, Wo,
+                               out_act=not pj)
+        s1 = K.fc_fwd(pool, blk._se_reduce.weight.view(sp.cse, CE), blk._se_reduce.bias, 0)
+        s2 = K.fc_fwd(s1, blk._se_expand.weight.view(CE, sp.cse), blk._se_expand.bias, 1)
+        if pj:
+            p, _ = K.project_fwd_fused(d, bn1, s2, w2, N, HW)
+        else:
+            p = K.gemm_nt(K.se_scale_fwd(d, s2).view(N * HW, CE), w2)
+        return K.residual_bn(p.view(N, Ho, Wo, Co), K.EvalBN(blk._bn2, 0), None, 1.0, x if sp.skip else None, N, HW)
+
     def _blocks(self, tape, x, stage, rng, lazy_in=None):
         """forward_backbone_block (model/unidefense.py:159-172)."""
         start = self.delimiter[stage - 1] if stage > 0 else 0
@@ -367,6 +411,9 @@ class UniDefenseModelEb4(nn.Module):
                 nxt = self.backbone._blocks[idx + 1] if idx + 1 < end else None          # (within the stage: its input IS this output)
                 x = T.mbconv_fused(tape, x, blk, keep, 1.0 - rate, fused["wt"][id(blk._depthwise_conv.weight)],
                                    fused["dp"], lazy_in if idx == 0 else None, next_blk=nxt)
+            elif tape is None and not self.training and self.__dict__.get("_eval_fused") and self._eval_block_ok(blk):
+                # eval-mode node of an InferenceRunner's forward (unidefense_amd/infer.py): expand conv inside the depthwise pass
+                x = self._mbconv_eval(x, blk)
             else:
                 dt = x.dtype                                   # the operator path computes in fp32 storage
                 if dt != torch.float32:

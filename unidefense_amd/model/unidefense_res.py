@@ -148,6 +148,11 @@ class UniDefenseModelRes18(nn.Module):
             if bad:
                 raise RuntimeError(f"pretrained weights mismatch: missing {bad}")
 
+    def inference_runner(self, batch, size):
+        """The graph-captured eval forward for [batch, 3, size, size] inputs (unidefense_amd/infer.py: InferenceRunner)."""
+        from ..infer import inference_runner
+        return inference_runner(self, batch, size)
+
     # ---------------------------------------------------------------------------------------
     def _conv(self, tape, x, conv, stride):
         if isinstance(conv, _SFConv2dParams):
