@@ -472,7 +472,11 @@ int ud_affine3(const float* x, const float* M, float* out, int N, int HW, ud_str
  * var = running_var (the fixed affine map of nn.BatchNorm2d.eval()); the running buffers are only read, never written,
  * and sumsq / inv_count / unbias / momentum are ignored.  Every forward consumer takes it; every BACKWARD entry point
  * (ud_coldot_bn, ud_normbwd_*, ud_se_scale_bwd_bn, ud_dwconv_bwd_data_bn, ud_dwtile_wgrad, ud_dwtile_bwd, ud_irfft2_dwbwd,
- * ud_pw_bwd_fused, ud_pj_bwd_fused_a / _b) returns UD_EINVAL for it. */
+ * ud_pw_bwd_fused, ud_pj_bwd_fused_a / _b) returns UD_EINVAL for it.
+ * STATISTICS OFF IN EVAL: a forward whose BatchNorms are all in the eval form needs no batch statistics, so producers
+ * whose statistics epilogue is optional skip it when handed no accumulator, and ud_colstats is not launched at all.
+ * ud_dwtile (stats 0), ud_gemm (stat_sum NULL) and ud_pj_fwd_fused (sum == sumsq == NULL) always took this; ud_irfft2_mix and
+ * ud_irfft2_two_pass take sum == sumsq == NULL since the fp16 inference forward. */
 typedef struct {
     const double* sum;       /* [G][C] sum of x over the rows (and ranks) the statistics cover */
     const double* sumsq;     /* [G][C] sum of x^2 */
@@ -605,6 +609,17 @@ long ud_mb_eval_dw_tiles(int Ho, int Wo, int stride);
 int ud_mb_eval_dw(const float* x, const float* we, const ud_bn_ref* bn0, const float* wt, const ud_bn_ref* bn1, float* d, float* part,
                   int N, int H, int W, int Ci, int CE, int Ho, int Wo, int K, int stride, int pad_t, int pad_l, int out_act,
                   ud_stream_t stream);
+/* The same node in half storage (the fp16 inference forward): x and d are _Float16, we / wt / part fp32.  The expand conv runs
+ * on v_mfma_f32_16x16x32_f16 (halo pixels x input channels from LDS, We rounded to fp16 as it is staged, fp32 accumulation);
+ * BN0 + swish, the zero padding, the depthwise conv and BN1 + swish in fp32.  d receives z rounded to fp16 (out_act = 1) or the
+ * raw dw rounded to fp16 (out_act = 0); part receives per tile the sum of what a consumer reads back: the stored z, or
+ * swish(bn1(.)) of the stored raw value.  No atomics.  x 16-byte aligned.  ud_mb_eval_dw_h_ok: Ci % 8 == 0, CE % 16 == 0,
+ * K == 3, stride 1 or 2; ud_mb_eval_dw_h_tiles == ud_mb_eval_dw_tiles. */
+int ud_mb_eval_dw_h_ok(int Ci, int CE, int K, int stride);
+long ud_mb_eval_dw_h_tiles(int Ho, int Wo, int stride);
+int ud_mb_eval_dw_h(const void* x, const float* we, const ud_bn_ref* bn0, const float* wt, const ud_bn_ref* bn1, void* d, float* part,
+                    int N, int H, int W, int Ci, int CE, int Ho, int Wo, int K, int stride, int pad_t, int pad_l, int out_act,
+                    ud_stream_t stream);
 int ud_pj_bwd_fused_a(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* w, int N, int HW, int CE,
                       int CO, float* dw, double* dgate, float* part, ud_stream_t stream);
 int ud_pj_bwd_fused_b(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,
@@ -677,7 +692,7 @@ int ud_rfft2_ex_planes(const void* x, uint16_t* planes, long panel_stride, long 
                        const float* dw_wt, void* dw_out, int dw_k, ud_stream_t stream);
 /* irfft2 + SF mix + BN1 statistics (exp.py:60-65, stride 1):  freq = irfft2(Y) * scale;
  * y = (1 - a) spat + a freq, a = sigmoid(alpha[0]);  diff_out = freq - spat (what the backward needs of the two
- * branches: neither has to be kept);  sum[c] += sum y, sumsq[c] += sum y^2 */
+ * branches: neither has to be kept);  sum[c] += sum y, sumsq[c] += sum y^2 (both NULL: no statistics) */
 int ud_irfft2_mix(const void* Y, void* y, int N, int S, int C, float scale, float w_interior, const void* spat,
     const float* alpha, void* diff_out, double* sum, double* sumsq, int f16, ud_stream_t stream);
 

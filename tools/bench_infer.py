@@ -2,9 +2,14 @@
 (unidefense_amd/infer.py), in one process on one GPU.  Per row: ms per batch and img/s of both paths (median of --reps timed
 windows of --steps calls each, after --warmup untimed calls).  Launch counts and per-kernel times come from a run under
 rocprofv3 --kernel-trace --stats with --runner-only / --eager-only (profiles/r07/infer.txt).
+--precision fp32 | fp16 | both: which runners a row times (fp16: UDEB4 only; the UDR50 row keeps fp32); with both, the two
+runners' windows are taken alternately in the same process (profiles/r08/infer_fp16.txt).
+--ab-node-h: the fp16 runner captured three times, UniDefenseModelEb4.EVAL_NODE_H_MAX_CIN = 0 (composed half kernels only), 32
+(the half-storage eval node on block group 1) and 448 (also on the last group), timed alternately.
 
   python tools/bench_infer.py                       # the four rows below
   python tools/bench_infer.py --rows udeb4-256-96 --runner-only --steps 20    # e.g. under rocprofv3 --kernel-trace --stats
+  python tools/bench_infer.py --rows udeb4-256-64,udeb4-256-96,udeb4-380-96 --precision both --runner-only
 """
 import argparse
 import json
@@ -29,20 +34,31 @@ def _model(name):
     return m.cuda().eval()
 
 
-def _time(fn, steps, warmup, reps):
-    for _ in range(warmup):
+def _window(fn, steps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
         fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(steps):
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def _time_alternating(fns, steps, warmup, reps):
+    """median ms per call of each fn, its windows interleaved with the others' (box drift hits all of them alike)"""
+    for fn in fns:
+        for _ in range(warmup):
             fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / steps)
-    return sorted(ms)[len(ms) // 2]
+    torch.cuda.synchronize()
+    ms = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            ms[i].append(_window(fn, steps))
+    return [sorted(v)[len(v) // 2] for v in ms]
+
+
+def _time(fn, steps, warmup, reps):
+    return _time_alternating([fn], steps, warmup, reps)[0]
 
 
 def main():
@@ -53,6 +69,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--runner-only", action="store_true", help="skip the eager timing (profiling runs)")
     ap.add_argument("--eager-only", action="store_true", help="skip the runner (profiling runs)")
+    ap.add_argument("--precision", choices=("fp32", "fp16", "both"), default="fp32", help="the runner(s) a row times")
+    ap.add_argument("--ab-node-h", action="store_true", help="A/B of the half-storage eval node's block groups (fp16 runner)")
     args = ap.parse_args()
     dev = torch.cuda.get_device_name(0)
     for key in args.rows.split(","):
@@ -61,6 +79,24 @@ def main():
         m = _model(name)
         x = torch.randn(bs, 3, size, size, device="cuda").clamp_(-1, 1)
         row = {"row": key, "model": name, "size": size, "batch": bs, "device": dev}
+        if args.ab_node_h:
+            from unidefense_amd.infer import InferenceRunner
+            cls, keep, runners = type(m), type(m).EVAL_NODE_H_MAX_CIN, {}
+            try:
+                for cin in (0, 32, 448):
+                    cls.EVAL_NODE_H_MAX_CIN = cin          # read while the runner warms up and captures
+                    r = InferenceRunner(m, bs, size, "fp16")
+                    r(x)
+                    r(x)
+                    runners[cin] = r
+            finally:
+                cls.EVAL_NODE_H_MAX_CIN = keep
+            ts = _time_alternating([lambda r=r: r(x) for r in runners.values()], args.steps, args.warmup, args.reps)
+            row.update({f"fp16_node_max_cin_{cin}_ms": round(t, 3) for cin, t in zip(runners, ts)})
+            print(json.dumps(row), flush=True)
+            del runners, r, m
+            torch.cuda.empty_cache()
+            continue
         if not args.runner_only:
             with torch.no_grad():
                 t = _time(lambda: m(x), args.steps, args.warmup, args.reps)
@@ -68,15 +104,25 @@ def main():
         if args.eager_only:
             print(json.dumps(row), flush=True)
             continue
-        r = m.inference_runner(bs, size)
-        r(x)                                   # eager warm-up
-        r(x)                                   # capture + first replay
-        t = _time(lambda: r(x), args.steps, args.warmup, args.reps)
-        row.update(runner_ms=round(t, 3), runner_img_s=round(bs * 1000.0 / t, 1))
-        if "eager_ms" in row:
-            row["speedup"] = round(row["eager_ms"] / t, 3)
+        precs = {"fp32": ["fp32"], "fp16": ["fp16"], "both": ["fp32", "fp16"]}[args.precision]
+        if name != "UDEB4":
+            precs = ["fp32"]
+        runners = []
+        for prec in precs:
+            r = m.inference_runner(bs, size, prec)
+            r(x)                                   # eager warm-up
+            r(x)                                   # capture + first replay
+            runners.append(r)
+        ts = _time_alternating([lambda r=r: r(x) for r in runners], args.steps, args.warmup, args.reps)
+        for prec, t in zip(precs, ts):
+            tag = "runner" if prec == "fp32" else "runner_fp16"
+            row.update({f"{tag}_ms": round(t, 3), f"{tag}_img_s": round(bs * 1000.0 / t, 1)})
+        if "eager_ms" in row and "runner_ms" in row:
+            row["speedup"] = round(row["eager_ms"] / row["runner_ms"], 3)
+        if "runner_ms" in row and "runner_fp16_ms" in row:
+            row["fp16_speedup"] = round(row["runner_ms"] / row["runner_fp16_ms"], 3)
         print(json.dumps(row), flush=True)
-        del r, m
+        del runners, r, m
         torch.cuda.empty_cache()
 
 

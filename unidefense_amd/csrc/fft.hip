@@ -537,7 +537,7 @@ __global__ __launch_bounds__(NT) void irfft2_kernel(const T* __restrict__ Y, T* 
             }
         }
     }
-    if (MIX) {
+    if (MIX && sum) {          // (sum == NULL: an eval-form consumer wants no statistics)
         // fold the S row-threads of every channel: the FFT's LDS planes are free now
         __syncthreads();
         double* red = reinterpret_cast<double*>(lds);
@@ -1049,7 +1049,7 @@ __global__ __launch_bounds__(NT2) void rows_inv_kernel(const float* __restrict__
             }
         }
     }
-    if (MIX) {
+    if (MIX && sum) {
         red[threadIdx.x * 2] = tot1;
         red[threadIdx.x * 2 + 1] = tot2;
         __syncthreads();
@@ -1324,7 +1324,7 @@ __global__ __launch_bounds__(NTW) void irfft2_wave_kernel(const T* __restrict__ 
             }
         }
     }
-    if (MIX) {
+    if (MIX && sum) {
         // per-channel totals: the two lane halves by a wavefront shuffle, the 16 waves through LDS (the planes are free now)
         tot1 += __shfl_xor(tot1, 32, 64);
         tot2 += __shfl_xor(tot2, 32, 64);
@@ -1576,7 +1576,7 @@ int ud_irfft2_dwbwd(const void* Y, int N, int S, int C, float scale, float w_int
 
 int ud_irfft2_mix(const void* Y, void* y, int N, int S, int C, float scale, float w_interior, const void* spat,
                   const float* alpha, void* freq_out, double* sum, double* sumsq, int f16, ud_stream_t stream) {
-    if (N < 1 || C < 1 || !Y || !y || !spat || !alpha || !freq_out || !sum || !sumsq) return UD_EINVAL;
+    if (N < 1 || C < 1 || !Y || !y || !spat || !alpha || !freq_out || !sum != !sumsq) return UD_EINVAL;
     IrfftMix m{spat, alpha, freq_out, sum, sumsq};
     UD_STORAGE_DISPATCH(f16, return irfft2_dispatch<T>((const T*)Y, (T*)y, N, S, C, scale, w_interior, &m,
                                                        (hipStream_t)stream));
@@ -1608,7 +1608,7 @@ int ud_irfft2_two_pass(const void* Y, void* y, float* ws, int N, int S, int C, f
                        const void* spat, const float* alpha, void* freq_out, double* sum, double* sumsq, int f16,
                        ud_stream_t stream) {
     if (N < 1 || C < 1 || !Y || !y || !ws || (S != 32 && S != 64)) return UD_EINVAL;
-    if (spat && (!alpha || !freq_out || !sum || !sumsq)) return UD_EINVAL;
+    if (spat && (!alpha || !freq_out || !sum != !sumsq)) return UD_EINVAL;
     IrfftMix mv{spat, alpha, freq_out, sum, sumsq};
     const IrfftMix* m = spat ? &mv : nullptr;
     hipStream_t s = (hipStream_t)stream;

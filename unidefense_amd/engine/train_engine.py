@@ -206,16 +206,18 @@ class TrainEngine(AbstractEngine):
     def _score(self, batches):
         """p(real) = softmax(cls_out)[:, 0] of `batches` test batches (forgery_engine.py:349,437), gathered over the
         ranks with two device all_gathers (engine/metrics.py:gather_scores replaces dist.all_gather_object, :374-375).
-        config['config']['inference_graph'] (default false): the forward replays the model's InferenceRunner graph."""
+        config['config']['inference_graph'] (default false): the forward replays the model's InferenceRunner graph;
+        config['config']['inference_precision'] ("fp32" default, "fp16"): that runner's precision (with inference_graph only)."""
         from .metrics import gather_scores
         self.model.eval()
         graphed = bool(self.config["config"].get("inference_graph", False))     # opt-in: unidefense_amd/infer.py
+        precision = self.config["config"].get("inference_precision", "fp32")
         scores, labels = [], []
         for step in range(1, batches + 1):
             xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
             x = torch.cat([xr, xf], 0).contiguous()
             if graphed:
-                out = self.model_without_ddp.inference_runner(x.shape[0], x.shape[-1])(x)     # one hipGraph replay per batch
+                out = self.model_without_ddp.inference_runner(x.shape[0], x.shape[-1], precision)(x)     # one hipGraph replay per batch
             else:
                 out = self.model(x)          # inference forward: no tape, running statistics
             scores.append(torch.softmax(out["cls_out"], 1)[:, 0])

@@ -9,40 +9,57 @@ gives the updated model's output afterwards without being rebuilt.
 
 UDEB4's block group 1 takes the eval-mode node (model.unidefense._mbconv_eval: the expand conv inside the depthwise pass,
 csrc/evalblk.hip) during the runner's warm-up and capture; every other layer, and the ResNet variants as a whole, are captured
-as their eager eval forward.  fp32 storage only.
+as their eager eval forward.
+
+precision="fp16" (UDEB4 only): the MBConv trunk in half storage with the storage boundaries of the fp16 training mode — the stem
+conv's output rounded once to half, the 32 blocks' activations fp16 in memory (fp32 arithmetic in registers, fp16 MFMA 1x1
+convs with fp32 accumulation), the decoder, attention, head and losses fp32 — on eval-form BatchNorms with no batch statistics
+(tape.mbconv_eval_half).  Selected by a runner-scoped flag; the eager eval forward and the fp32 runner do not change.
 """
 import contextlib
 
 import torch
 
 _MAX_RUNNERS = 4          # captured keys a model keeps (model.inference_runner), oldest evicted first
+PRECISIONS = ("fp32", "fp16")
 
 
 @contextlib.contextmanager
-def _eval_nodes(model):
-    prev = model.__dict__.get("_eval_fused", False)
-    model.__dict__["_eval_fused"] = True
+def _eval_nodes(model, half=False):
+    flag = "_eval_half" if half else "_eval_fused"
+    prev = model.__dict__.get(flag, False)
+    model.__dict__[flag] = True
     try:
         yield
     finally:
-        model.__dict__["_eval_fused"] = prev
+        model.__dict__[flag] = prev
+
+
+def _check_precision(model, precision):
+    from .model.unidefense import UniDefenseModelEb4
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    if precision == "fp16" and not isinstance(model, UniDefenseModelEb4):
+        raise ValueError(f"precision 'fp16' is built for UDEB4 only; {type(model).__name__} has no half-storage path")
 
 
 class InferenceRunner:
-    """runner = InferenceRunner(model, batch, size); out = runner(x) with x [batch, 3, size, size] fp32 on the model's GPU;
-    out is the dict model(x) returns under no_grad ({"cls_out", "rec", "loss_dict"}), held in the runner's static buffers: the
-    next call overwrites it (clone what must outlive it)."""
+    """runner = InferenceRunner(model, batch, size[, precision]); out = runner(x) with x [batch, 3, size, size] fp32 on the
+    model's GPU; out is the dict model(x) returns under no_grad ({"cls_out", "rec", "loss_dict"}, every tensor fp32), held in the
+    runner's static buffers: the next call overwrites it (clone what must outlive it).  precision: "fp32" or "fp16" (UDEB4)."""
 
-    def __init__(self, model, batch, size):
+    def __init__(self, model, batch, size, precision="fp32"):
         from .model import MODEL
         if not isinstance(model, tuple(MODEL.values())):
             raise ValueError(f"InferenceRunner takes a UDEB4 / UDR18 / UDR50 model, got {type(model).__name__}")
+        _check_precision(model, precision)
         if model.training:
             raise ValueError("InferenceRunner needs model.eval(): the captured forward reads the running statistics")
         p = next(model.parameters())
         if not p.is_cuda:
             raise ValueError("InferenceRunner needs a cuda model")
-        self.model, self.batch, self.size = model, int(batch), int(size)
+        self.model, self.batch, self.size, self.precision = model, int(batch), int(size), precision
+        self.half = precision == "fp16"
         self.shape = (self.batch, 3, self.size, self.size)
         self.device = p.device
         self.calls = 0
@@ -61,13 +78,13 @@ class InferenceRunner:
         self._check(x)
         self.calls += 1
         if self.calls == 1:
-            with _eval_nodes(self.model):           # eager warm-up of the same forward the graph records
+            with _eval_nodes(self.model, self.half):           # eager warm-up of the same forward the graph records
                 return self.model(x.contiguous())
         if self.graph is None:
             self.x = x.detach().clone().contiguous()
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
-            with _eval_nodes(self.model), torch.cuda.graph(g):
+            with _eval_nodes(self.model, self.half), torch.cuda.graph(g):
                 self.out = self.model(self.x)
             self.graph = g
         else:
@@ -76,13 +93,14 @@ class InferenceRunner:
         return self.out
 
 
-def inference_runner(model, batch, size):
-    """The model's runner for (batch, size), made on first use; a model keeps at most _MAX_RUNNERS of them."""
+def inference_runner(model, batch, size, precision="fp32"):
+    """The model's runner for (batch, size[, precision]), made on first use; a model keeps at most _MAX_RUNNERS of them."""
+    _check_precision(model, precision)
     runners = model.__dict__.setdefault("_ud_runners", {})
-    key = (int(batch), int(size))
+    key = (int(batch), int(size)) if precision == "fp32" else (int(batch), int(size), precision)
     r = runners.pop(key, None)
     if r is None:
-        r = InferenceRunner(model, batch, size)
+        r = InferenceRunner(model, batch, size, precision)
         while len(runners) >= _MAX_RUNNERS:
             del runners[next(iter(runners))]
     runners[key] = r                                 # most recently used last

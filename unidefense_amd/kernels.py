@@ -2505,6 +2505,28 @@ def mb_eval_dw(x, we2, bn0, wt, bn1, k, stride, pad_t, pad_l, Ho, Wo, out_act=Tr
     return d, group_colsum(part.view(N * tiles, CE), N, tiles, 1.0 / (Ho * Wo))
 
 
+def mb_eval_dw_h_ok(Ci, CE, k, stride):
+    """does ud_mb_eval_dw_h (the half-storage eval node) take a block with these (input / expanded channels, kernel, stride)?"""
+    return _lib.call("ud_mb_eval_dw_h_ok", int(Ci), int(CE), int(k), int(stride)) == 1
+
+
+def mb_eval_dw_h(x, we2, bn0, wt, bn1, k, stride, pad_t, pad_l, Ho, Wo, out_act=True):
+    """mb_eval_dw in half storage (csrc/evalblk.hip: the expand conv on fp16 MFMA): x [N,H,W,Ci] fp16, we2 / wt fp32.  Returns
+    (d [N,Ho,Wo,CE] fp16: swish(bn1(dw)) if out_act else the raw dw, pool [N,CE] fp32: the mean over the pixels of what a consumer
+    reads back — the stored activated value, or swish(bn1(.)) of the stored raw one)."""
+    _chk(we2, wt)
+    if not (x.is_cuda and x.dtype == torch.float16 and x.is_contiguous()):
+        raise ValueError(f"expected a contiguous fp16 CUDA tensor, got {x.dtype} {x.device} contiguous={x.is_contiguous()}")
+    N, H, W, Ci = x.shape
+    CE = we2.shape[0]
+    tiles = _call("ud_mb_eval_dw_h_tiles", Ho, Wo, stride)
+    d = empty((N, Ho, Wo, CE), x, torch.float16)
+    part = empty((N, tiles, CE), x)
+    _call("ud_mb_eval_dw_h", _p(x), _p(we2), C.byref(bn0.ref()), _p(wt), C.byref(bn1.ref()), _p(d), _p(part), N, H, W, Ci, CE, Ho,
+          Wo, k, stride, pad_t, pad_l, 1 if out_act else 0, _stream())
+    return d, group_colsum(part.view(N * tiles, CE), N, tiles, 1.0 / (Ho * Wo))
+
+
 def _pd(t, off_doubles=0):
     return C.c_void_p(t.data_ptr() + 8 * off_doubles)
 
@@ -2930,7 +2952,8 @@ def rfft2_ex_planes(x, scale, w_interior=1.0, bn=None, want_act=False, gate_alph
 
 
 def irfft2_mix(Y, scale, spat, alpha, acc):
-    """(y, diff) = SF mix of spat with freq = irfft2(Y), and freq - spat; acc += [sum y | sum y^2]."""
+    """(y, diff) = SF mix of spat with freq = irfft2(Y), and freq - spat; acc += [sum y | sum y^2] (acc None: no statistics,
+    the eval-form forward)."""
     h = _act(Y, spat)
     _chk(alpha)
     N, S, Wh, C2 = Y.shape
@@ -2938,12 +2961,12 @@ def irfft2_mix(Y, scale, spat, alpha, acc):
     assert spat.shape == (N, S, S, Cc)
     y = torch.empty_like(spat)
     fr = torch.empty_like(spat)
+    s1, s2 = (_pd(acc), _pd(acc, Cc)) if acc is not None else (None, None)
     if _fft_two_pass("irfft_mix", S, h):
         _call("ud_irfft2_two_pass", _p(Y), _p(y), _p(_fft_ws(N, S, Cc, Y)), N, S, Cc, float(scale), 1.0, _p(spat), _p(alpha),
-              _p(fr), _pd(acc), _pd(acc, Cc), h, _stream())
+              _p(fr), s1, s2, h, _stream())
     else:
-        _call("ud_irfft2_mix", _p(Y), _p(y), N, S, Cc, float(scale), 1.0, _p(spat), _p(alpha), _p(fr), _pd(acc),
-              _pd(acc, Cc), h, _stream())
+        _call("ud_irfft2_mix", _p(Y), _p(y), N, S, Cc, float(scale), 1.0, _p(spat), _p(alpha), _p(fr), s1, s2, h, _stream())
     return y, fr
 
 

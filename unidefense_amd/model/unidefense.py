@@ -254,10 +254,11 @@ class UniDefenseModelEb4(nn.Module):
         if extractor_weights is not None:
             self.load_backbone_weights(extractor_weights)
 
-    def inference_runner(self, batch, size):
-        """The graph-captured eval forward for [batch, 3, size, size] inputs (unidefense_amd/infer.py: InferenceRunner)."""
+    def inference_runner(self, batch, size, precision="fp32"):
+        """The graph-captured eval forward for [batch, 3, size, size] inputs (unidefense_amd/infer.py: InferenceRunner);
+        precision "fp16": the MBConv trunk in half storage (tape.mbconv_eval_half)."""
         from ..infer import inference_runner
-        return inference_runner(self, batch, size)
+        return inference_runner(self, batch, size, precision)
 
     # -- pretrained backbone (model/efficientnet/utils.py:589-634): missing sf_coef / freq_conv keys tolerated
     def load_backbone_weights(self, path):
@@ -356,6 +357,10 @@ class UniDefenseModelEb4(nn.Module):
     # thin block group 1 (24 / 32 inputs) but not at the last group (272 / 448 inputs: 729 us per block at bs 96 on 8 x 8 maps,
     # profiles/r07/infer.txt), where the expand GEMM on the matrix pipe + the composed kernels stay
     EVAL_NODE_MAX_CIN = 32
+    # the same for the half-storage node of the fp16 InferenceRunner (ud_mb_eval_dw_h: the expand conv on fp16 MFMA), from the A/B
+    # of tools/bench_infer.py --ab-node-h (profiles/r08/infer_fp16.txt): whole fp16 replay at 256^2 bs 96 16.93 ms without the node,
+    # 17.00 with it on group 1 (Ci 24 / 32), 17.20 also on group 7 (Ci 272 / 448); 380^2 bs 96 42.95 / 43.12 / 43.89
+    EVAL_NODE_H_MAX_CIN = 0          # measured slower than the composed half kernels on both groups: off
 
     @classmethod
     def _eval_block_ok(cls, blk):
@@ -411,6 +416,11 @@ class UniDefenseModelEb4(nn.Module):
                 nxt = self.backbone._blocks[idx + 1] if idx + 1 < end else None          # (within the stage: its input IS this output)
                 x = T.mbconv_fused(tape, x, blk, keep, 1.0 - rate, fused["wt"][id(blk._depthwise_conv.weight)],
                                    fused["dp"], lazy_in if idx == 0 else None, next_blk=nxt)
+            elif rng.get("_eval16") is not None and (blk.spec.sf_norm is None or K.fft_kernel_size(x.shape[1])):
+                # the fp16 InferenceRunner's forward: half storage, eval-form BatchNorms, no statistics (an SF block on a map side
+                # with no in-register transform — 95 at 380 x 380 — takes the operator path below, in fp32 between two casts)
+                x = T.mbconv_eval_half(x, blk, rng["_eval16"][id(blk._depthwise_conv.weight)], lazy_in if idx == start else None,
+                                       self.EVAL_NODE_H_MAX_CIN)
             elif tape is None and not self.training and self.__dict__.get("_eval_fused") and self._eval_block_ok(blk):
                 # eval-mode node of an InferenceRunner's forward (unidefense_amd/infer.py): expand conv inside the depthwise pass
                 x = self._mbconv_eval(x, blk)
@@ -532,7 +542,9 @@ class UniDefenseModelEb4(nn.Module):
         # registers, fp64 BatchNorm sums, fp32 weights / weight gradients, fp16 MFMA); stem conv, decoder, attention,
         # head and losses stay fp32 — T.cast at the boundaries.  Fused training path only.
         fused = self.training and _fused_mbconv()
-        st16 = fused and _half_storage(self)
+        # the fp16 InferenceRunner (unidefense_amd/infer.py): the eval forward with the same storage boundaries
+        ev16 = tape is None and not self.training and bool(self.__dict__.get("_eval_half"))
+        st16 = (fused and _half_storage(self)) or ev16
         f32 = torch.float32
         if fused:
             dp = T.DataParallelCtx(self._sync_group(bb._bn0), getattr(self, "_bn_exchange", None))
@@ -542,6 +554,11 @@ class UniDefenseModelEb4(nn.Module):
             h, lazy = T.stem_fused(tape, x_pix, bb._conv_stem.weight, bb._bn0, 2, pt, pl, Ho, Wo, dp,
                                    torch.float16 if st16 else f32)
             x_b0 = self._blocks(tape, h, 0, rng, lazy)
+        elif ev16:
+            # the stem conv's output rounded once to half; its eval BatchNorm + swish applied on load by block 0's depthwise conv
+            rng["_eval16"] = wts
+            h = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False).to(torch.float16)
+            x_b0 = self._blocks(tape, h, 0, rng, K.EvalBN(bb._bn0, 1))
         else:
             h = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False)
             h = self._bn(tape, h, bb._bn0, 1)

@@ -148,10 +148,11 @@ class UniDefenseModelRes18(nn.Module):
             if bad:
                 raise RuntimeError(f"pretrained weights mismatch: missing {bad}")
 
-    def inference_runner(self, batch, size):
-        """The graph-captured eval forward for [batch, 3, size, size] inputs (unidefense_amd/infer.py: InferenceRunner)."""
+    def inference_runner(self, batch, size, precision="fp32"):
+        """The graph-captured eval forward for [batch, 3, size, size] inputs (unidefense_amd/infer.py: InferenceRunner);
+        fp32 only (precision "fp16" raises ValueError: the ResNet variants have no half-storage path)."""
         from ..infer import inference_runner
-        return inference_runner(self, batch, size)
+        return inference_runner(self, batch, size, precision)
 
     # ---------------------------------------------------------------------------------------
     def _conv(self, tape, x, conv, stride):

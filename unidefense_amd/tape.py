@@ -1468,3 +1468,68 @@ def mbconv_fused(tape, x, blk, keep, keep_prob, wt, dp, lazy_in=None, next_blk=N
         tape.add_grad(x, dx)
     tape.record(bwd)
     return out
+
+
+def mbconv_eval_half(x, blk, wt, lazy_bn=None, node_max_cin=0):
+    """MBConvBlock.forward in eval mode, half storage (the fp16 InferenceRunner, unidefense_amd/infer.py): the forward of
+    mbconv_fused with every BatchNorm in the eval form (kernels.EvalBN: the running buffers, read in place) and no batch
+    statistics anywhere — no accumulator is handed to a producer and ud_colstats is never launched.  No tape.
+    x [N,H,W,Cin] fp16 (for block 0: the raw stem output, lazy_bn its eval BatchNorm + swish, applied on load);
+    wt: the depthwise weight tap-major [k*k][C].  Activations are stored as fp16, computed in fp32 registers; the 1x1 convs
+    are fp16 MFMA products with fp32 accumulation, selected per GEMM descriptor by the half operands (ud_gemm_desc.half_mask),
+    the fp32 weights converted as the kernel loads them.
+    node_max_cin: an expanding non-SF block with at most this many input channels takes the half-storage eval node instead
+    (ud_mb_eval_dw_h: expand conv on fp16 MFMA + BN0 + swish + depthwise + SE squeeze in one pass; e is never written)."""
+    sp = blk.spec
+    N, H, W, Cin = x.shape
+    M = N * H * W
+    k, stride = sp.k, sp.stride
+    pl, pr, pt, pb = sp.pad
+    Ho = (H + pt + pb - k) // stride + 1
+    Wo = (W + pl + pr - k) // stride + 1
+    HWo, Mo = Ho * Wo, N * Ho * Wo
+    Ce, Co = sp.cexp, sp.cout
+    assert x.dtype == torch.float16 and not (sp.skip and lazy_bn is not None)
+    bn1 = K.EvalBN(blk._bn1, 1)
+    if (sp.expand != 1 and sp.sf_norm is None and Cin <= node_max_cin and K.mb_eval_dw_h_ok(Cin, Ce, k, stride)):
+        # d raw (BN1 + swish applied on load by se_scale_bn); pool: the mean of swish(bn1(.)) of the stored values
+        d, pmean = K.mb_eval_dw_h(x, blk._expand_conv.weight.view(Ce, Cin), K.EvalBN(blk._bn0, 1), wt, bn1, k, stride, pt, pl, Ho,
+                                  Wo, out_act=False)
+        s1 = K.fc_fwd(pmean, blk._se_reduce.weight.view(sp.cse, Ce), blk._se_reduce.bias, 0)
+        return _eval_half_tail(x, blk, d, bn1, s1, N, HWo, Mo)
+    if sp.expand != 1:
+        e = K.gemm_nt(x.view(M, Cin), blk._expand_conv.weight.view(Ce, Cin))
+        src, src_bn = e.view(N, H, W, Ce), K.EvalBN(blk._bn0, 1)
+    else:
+        src, src_bn = x, lazy_bn
+    # depthwise conv of act(bn0(e)) from LDS halo tiles (the activation applied on load); SF blocks: the transform of the
+    # same activated tensor, the spectral 1x1 conv, and the inverse transform mixed with the spatial branch
+    spat = K.dwtile_fwd(src, wt, k, pt, pl, Ho, Wo, bn=src_bn, stride=stride)
+    if sp.sf_norm is not None:
+        S = H
+        s_f, s_i = _fft_scales(S, sp.sf_norm)
+        dwm = blk._depthwise_conv
+        xf, _ = K.rfft2_ex(src, s_f, 1.0, bn=src_bn)
+        yf = K.gemm_nt(xf.view(-1, 2 * Ce), dwm.freq_conv.weight.view(2 * Ce, 2 * Ce)).view(xf.shape)
+        if stride == 1:
+            d, _ = K.irfft2_mix(yf, s_i, spat, dwm.sf_coef, None)
+        else:
+            d = K.sfmix_fwd(spat, K.irfft2(yf, s_i, 1.0), dwm.sf_coef, True)
+    else:
+        d = spat
+    # squeeze-excite on swish(bn1(d)), then the gated tensor -> project conv -> BN2 (+ skip)
+    pool = K.zeros64(N * Ce, x)
+    K.colsum_bn(d, bn1, N, HWo, pool)
+    s1 = K.fc_fwd_d(pool, 1.0 / HWo, blk._se_reduce.weight.view(sp.cse, Ce), blk._se_reduce.bias, N)
+    return _eval_half_tail(x, blk, d, bn1, s1, N, HWo, Mo)
+
+
+def _eval_half_tail(x, blk, d, bn1, s1, N, HWo, Mo):
+    """the rest of mbconv_eval_half after the SE squeeze's first FC: gate, project conv, BN2 (+ skip)"""
+    sp = blk.spec
+    Ce, Co = sp.cexp, sp.cout
+    Ho, Wo = d.shape[1], d.shape[2]
+    s2 = K.fc_fwd(s1, blk._se_expand.weight.view(Ce, sp.cse), blk._se_expand.bias, 1)
+    c = K.se_scale_bn(d, bn1, s2, N, HWo)
+    p = K.gemm_nt(c.view(Mo, Ce), blk._project_conv.weight.view(Co, Ce))
+    return K.residual_bn(p.view(N, Ho, Wo, Co), K.EvalBN(blk._bn2, 0), None, 1.0, x if sp.skip else None, N, HWo)
