@@ -1,19 +1,22 @@
 """bench.py — images/sec of ONE forward+backward of UniDefenseModelEb4 (pass-1 loss of the train step,
 engine/abstract_engine.py:210-281 in the reference) at 256x256, bs=32 per GPU, fp32, synthetic inputs.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0 (metric/unit from BASELINE.json; value = whole-job images/s with inputs
-resident in HBM; weak scaling: bs=32 per GPU).  Extra objects:
+resident in HBM; weak scaling: bs=32 per GPU).  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line; its `roofline` holds only the whole-step fractions derived from the headline
+figure.  Everything that takes runs of its own is measured only with --full:
   roofline     — dominant kernels = the matrix-pipe GEMM family: gemm_p3_kernel<prec 2> (operands pre-split into two fp16
                  planes, THREE fp16 MFMAs per fp32 product tile) + gemm_x3_kernel (in-kernel bf16 x 3 split, SIX MFMAs):
                  algorithmic FLOPs (2MNK) of their launches / their HIP-event durations (3 eager instrumented steps after
                  the timed region); peak = the pipe's dense 16-bit peak (2.5 PFLOP/s) / executed MFMAs per algorithmic
                  product, so frac = executed MFMA work / pipe peak (`frac_six_product_equiv`: the same work priced at six
                  MFMAs per product, the round-3 definition); `hbm`: the same launches' algorithmic bytes against 8 TB/s;
-                 `traffic`: PMC-measured HBM bytes per launch (profiles/).
+                 `traffic`: PMC-measured HBM bytes per launch (profiles/).  Also --gemm-table and, at N > 1 or with
+                 UD_FORCE_COLLECTIVES=1, `data_parallel` (SyncBN / all-reduce device times of the same eager steps).
   extra        — bounded child-process measurements of the other BASELINE configs ([4] f16 bs 64, [3] UDR50 320^2 bs 16,
                  [0] UDR18 128^2 bs 8), the engine's two-pass train step and UDEB4 at 380^2 (N = 1 only).
   cpu_baseline — the oracle (CPU restatement, "port") timed on the host cores (CPU quota of the job) on a bounded
@@ -25,6 +28,7 @@ import os
 import sys
 import time
 
+T_START = time.perf_counter()          # the stderr phase line: what a run spends outside its timed steps
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -123,7 +127,7 @@ def cpu_baseline(timeout_s=300):
 
 def train_step_measure(bs):
     """the engine's full two-pass train step (AbstractEngine.train_unidefense_model, abstract_engine.py:207-381: clean pass +
-    perturbed pass, two AdamW steps) on UDEB4 256x256 — informational, run in a child process of the default bench"""
+    perturbed pass, two AdamW steps) on UDEB4 256x256 — informational, run in a child process of `bench.py --full`"""
     from unidefense_amd.engine import AbstractEngine
     from unidefense_amd.engine.optim import build_optimizer
     from unidefense_amd.loss import LOSSES
@@ -187,10 +191,11 @@ def train_step_measure(bs):
 
 def extra_measurements(budget_s=100):
     """Driver-visible numbers of the other BASELINE configs: bounded 5-step runs in CHILD processes after the timed region
-    (configs[4] f16 bs 64, configs[3] UDR50 320^2 bs 16, configs[0] UDR18 128^2 bs 8, the two-pass train step, UDEB4 at 380^2)."""
+    (configs[4] f16 bs 64, configs[3] UDR50 320^2 bs 16, configs[0] UDR18 128^2 bs 8, the two-pass train step, UDEB4 at 380^2).
+    The children are plain runs: what is read from them comes from their headline figure."""
     import subprocess
     me = os.path.abspath(__file__)
-    common = ["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extra"]
+    common = ["--steps", "5", "--warmup", "2"]
     jobs = [("configs[4]: UDEB4 256x256 fp16 MFMA + half storage, bs 64", ["--dtype", "f16", "--batch", "64"] + common),
             ("configs[3]: UDR50 320x320 bs 16", ["--model", "UDR50", "--size", "320", "--batch", "16"] + common),
             ("configs[0]: UDR18 128x128 bs 8", ["--model", "UDR18", "--size", "128", "--batch", "8"] + common),
@@ -352,6 +357,112 @@ def _committed(args, bs, name, sha_key, sha):
     return None
 
 
+def gemm_roofline(args, bs, prof, prof_steps):
+    """--full: the matrix-pipe GEMM family's figures from the launches of the eager instrumented steps (`prof`: one
+    (start event, end event, FLOPs, shape key, pipe, algorithmic bytes) per ud_gemm launch) and the committed summaries
+    of the same workload under profiles/"""
+    # GEMM families on the matrix pipe: gemm_p3_kernel prec 2 (path 4: pre-split fp16 x 2 planes, THREE fp16 MFMAs per
+    # product tile), gemm_x3_kernel (path 2: in-kernel bf16 x 3 split, SIX bf16 MFMAs; path 3: its one-MFMA fp16 mode);
+    # everything else is gemm_kernel on the fp32 pipe.  The roofline's kernel is the family with the most time.
+    p2 = [p for p in prof if p[4] == 4]
+    x3 = [p for p in prof if p[4] in (2, 3)]
+    f32 = [p for p in prof if p[4] not in (2, 3, 4)]
+
+    def fam(ps, mfma_per_product):
+        ms = sum(p[0].elapsed_time(p[1]) for p in ps)
+        fl = sum(p[2] for p in ps)
+        ach = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+        by = sum(p[5] for p in ps)
+        return {"launches_per_step": len(ps) / prof_steps, "ms_per_step": ms / prof_steps, "gflop_per_step": fl / 1e9 / prof_steps,
+                "achieved_tflops_fp32_equiv": ach, "mfma_per_product": mfma_per_product,
+                "executed_mfma_tflops": ach * mfma_per_product, "frac_of_pipe": ach * mfma_per_product / BF16_PEAK_TFLOPS,
+                "algorithmic_bytes_per_launch": by / max(len(ps), 1),
+                "hbm_gbs": by / (ms * 1e-3) / 1e9 if ms > 0 else 0.0}
+    fam_p2 = fam(p2, 3)
+    fam_x3 = fam(x3, 1 if args.dtype == "f16" else X3_MFMA_PER_PRODUCT)
+    # the roofline's kernel: BOTH matrix-pipe kernels as one family (they share the pipe, and which of the two has more time
+    # flips with the host pacing of the eager instrumented steps): achieved = their algorithmic fp32 FLOPs / their time,
+    # executed MFMA work = 3 x the planes kernel's + 6 x the in-kernel-split kernel's algorithmic FLOPs
+    dom_name = "matrix-pipe GEMM family: gemm_p3_kernel<prec 2> + gemm_x3_kernel"
+    pipe_ms = fam_p2["ms_per_step"] + fam_x3["ms_per_step"]
+    pipe_gf = fam_p2["gflop_per_step"] + fam_x3["gflop_per_step"]
+    exec_gf = fam_p2["gflop_per_step"] * fam_p2["mfma_per_product"] + fam_x3["gflop_per_step"] * fam_x3["mfma_per_product"]
+    n_pipe = max(len(p2) + len(x3), 1)
+    dom = {"achieved_tflops_fp32_equiv": pipe_gf / pipe_ms if pipe_ms > 0 else 0.0,
+           "mfma_per_product": exec_gf / pipe_gf if pipe_gf > 0 else 6.0,
+           "algorithmic_bytes_per_launch": (sum(p[5] for p in p2) + sum(p[5] for p in x3)) / n_pipe,
+           "hbm_gbs": (sum(p[5] for p in p2) + sum(p[5] for p in x3)) / prof_steps / (pipe_ms * 1e-3) / 1e9 if pipe_ms > 0 else 0.0,
+           "launches_per_step": n_pipe / prof_steps}
+    mfma_per_product = dom["mfma_per_product"]
+    x3_ms = sum(p[0].elapsed_time(p[1]) for p in x3)
+    x3_flops = sum(p[2] for p in x3)
+    f32_ms = sum(p[0].elapsed_time(p[1]) for p in f32)
+    f32_flops = sum(p[2] for p in f32)
+    gemm_ms = x3_ms + f32_ms + fam_p2["ms_per_step"] * prof_steps
+    gemm_flops = x3_flops + f32_flops + fam_p2["gflop_per_step"] * 1e9 * prof_steps
+    achieved = dom["achieved_tflops_fp32_equiv"]                                   # algorithmic fp32 TFLOP/s of the dominant family
+    achieved_all = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+    alg_bytes = dom["algorithmic_bytes_per_launch"]
+    hbm_gbs = dom["hbm_gbs"]
+    n_dom = dom["launches_per_step"]
+    traffic, traffic_src = _pmc_traffic(args, bs)
+    r = {"kernel": dom_name + ".  gemm_p3_kernel<prec 2> "
+                   "(csrc/gemm_p3.hip): fp32-accurate GEMM from operands pre-split into two fp16 pieces (one "
+                   "power-of-two scale per tensor), LDS-DMA loader waves + MFMA waves, THREE "
+                   "v_mfma_f32_32x32x16_f16 per fp32 product tile; gemm_x3_kernel (csrc/gemm_x3.hip): every fp32 "
+                   "operand split in the k-loop into 3 bf16 pieces, SIX v_mfma_f32_32x32x16_bf16 per tile.  "
+                   "achieved = algorithmic fp32 FLOPs (2MNK) of the family's launches / their HIP-event time; "
+                   "peak = the pipe's dense 16-bit peak (2500 TFLOP/s) / executed MFMAs per algorithmic product, "
+                   "so frac = executed MFMA work / pipe peak",
+         "achieved": achieved, "peak": BF16_PEAK_TFLOPS / mfma_per_product, "unit": "TFLOP/s",
+         "frac": achieved * mfma_per_product / BF16_PEAK_TFLOPS,
+         "executed_mfma_tflops": achieved * mfma_per_product, "pipe_peak": BF16_PEAK_TFLOPS,
+         "mfma_per_product": mfma_per_product,
+         "frac_of_pipe": achieved * mfma_per_product / BF16_PEAK_TFLOPS,
+         # for comparison with rounds 1-3, whose GEMMs all executed six MFMAs per product: the same algorithmic
+         # throughput priced at six (what the round-3 kernel would have had to execute for it)
+         "frac_six_product_equiv": achieved * X3_MFMA_PER_PRODUCT / BF16_PEAK_TFLOPS,
+         # the same launches priced as fp32 work against the fp32 matrix peak (bounded by 2.67, not 1)
+         "frac_fp32_equiv": achieved / MFMA_F32_PEAK_TFLOPS,
+         # HBM side of the same launches: algorithmic operand + result bytes (storage types as launched) /
+         # their HIP-event time, against 8 TB/s — the bound that matters in the f16 mode, where one fp16
+         # MFMA per product tile leaves the GEMMs memory-bound
+         "hbm": {"achieved": hbm_gbs, "peak": 8000.0, "unit": "GB/s", "frac": hbm_gbs / 8000.0},
+         "traffic": traffic,
+         "traffic_unit": "HBM bytes per launch (mean over the dominant family's launches of a step)",
+         "traffic_source": traffic_src, "algorithmic_bytes_per_launch": alg_bytes,
+         "launches_per_step": n_dom,
+         "families": {"gemm_p3_kernel<prec 2>": fam_p2, "gemm_x3_kernel": fam_x3},
+         "x3_ms_per_step": x3_ms / prof_steps, "x3_gflop_per_step": x3_flops / 1e9 / prof_steps,
+         # the rest of the GEMM family: gather-mode 3x3 convs / tiny shapes on v_mfma_f32_32x32x2_f32
+         "fp32_pipe_kernel": {"launches_per_step": len(f32) / prof_steps, "ms_per_step": f32_ms / prof_steps,
+                              "gflop_per_step": f32_flops / 1e9 / prof_steps,
+                              "achieved_tflops": f32_flops / (f32_ms * 1e-3) / 1e12 if f32_ms > 0 else 0.0,
+                              "peak": MFMA_F32_PEAK_TFLOPS},
+         "gemm_ms_per_step": gemm_ms / prof_steps,
+         "gemm_gflop_per_step": gemm_flops / 1e9 / prof_steps,
+         "gemm_family_tflops_fp32_equiv": achieved_all,
+         "measured": f"{prof_steps} EAGER steps after the timed region, HIP events around every launch on its "
+                     "stream (events cannot be read inside the replayed graph the headline number comes "
+                     "from; these steps launch every product by itself — the replayed step sends the data and "
+                     "weight gradient of a 1x1 conv out as ONE grid of the planes kernel, ud_gemm_p3_pair, "
+                     "which is ~0.5 ms per step faster than the sum timed here); profiles/r06/ holds the rocprofv3 --kernel-trace --stats summary of the "
+                     "graph-replayed steps of this same command (tools/gpu_round.sh), and "
+                     "tools/roofline_from_rocprof.py recomputes these numbers from it"}
+    # the same quantities from the rocprofv3 summary of the graph-REPLAYED steps of this command (committed under profiles/,
+    # printed only when stamped with this tree's GEMM sources): what `frac` above under-states by timing eager, un-paired launches
+    rep = _committed(args, bs, "roofline_replayed.json", "gemm_src_sha", _gemm_src_sha())
+    r["replayed"] = rep
+    # per kernel CLASS (SURVEY 8(d)): launches, ms, GB moved and GB/s from the PMC passes (tools/hbm_bw_table.py --json)
+    cls = _committed(args, bs, "hbm_classes.json", "csrc_sha", _csrc_sha())
+    r["classes"] = cls
+    if args.dtype == "f16":
+        # informational f16 line: the HBM side is the roofline (bound "hbm"); the matrix-pipe numbers move to "mfma"
+        r["mfma"] = {k: r[k] for k in ("achieved", "peak", "unit", "frac")}
+        r.update(achieved=hbm_gbs, peak=8000.0, unit="GB/s", frac=hbm_gbs / 8000.0)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -366,12 +477,17 @@ def main():
                          "operands + fp32 accumulation in every plain GEMM (ud_gemm path 3); use --batch 64")
     ap.add_argument("--storage", default="f16", choices=["f16", "f32"],
                     help="with --dtype f16: activation storage of the MBConv trunk (f16: half storage, the full configs[4] mode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the per-kernel roofline "
+                         "(and data-parallel diagnostics) from eager instrumented steps, the other BASELINE configs and the "
+                         "engine's two-pass train step in child processes, and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--eager", action="store_true", help="do not capture the step into a hipGraph")
-    ap.add_argument("--gemm-table", default=None, help="write a per-shape GEMM timing table to this file")
+    ap.add_argument("--gemm-table", default=None, help="with --full: write a per-shape GEMM timing table to this file")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the bounded secondary measurements (the other BASELINE configs, the engine's two-pass train step)")
+                    help="with --full: skip the bounded secondary measurements (the other BASELINE configs, the engine's "
+                         "two-pass train step)")
     ap.add_argument("--train-step", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write the loss, the model's outputs and the gradients of the last timed step "
@@ -379,6 +495,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.gemm_table and not args.full:
+        ap.error("--gemm-table times the eager instrumented steps of --full; add --full")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_measure()), flush=True)
         return
@@ -442,6 +560,7 @@ def main():
     # ---- execution mode: the whole step (zero grads, forward, loss, backward [, gradient exchange]) is
     # captured once into a hipGraph and replayed — ~2000 kernel launches per step with no host work between
     # them.  Any capture failure falls back to eager launches (reported in "exec").
+    t_ready = time.perf_counter()
     exec_mode = "eager"
     run = step
     side = torch.cuda.Stream()
@@ -510,37 +629,38 @@ def main():
         ones = torch.ones(1, device=dev)
         dist.all_reduce(ones)                                  # every rank that really took part adds 1 (over RCCL)
         n_ranks_seen = int(ones.item())
-    # ---- roofline of the dominant kernel: the same step, eager, every ud_gemm launch bracketed by HIP events
-    # on its launch stream (events cannot be read back from inside a replayed graph)
-    prof_steps = min(args.steps, 3)
-    from unidefense_amd import tape as T
-    K.GEMM_PROFILE = []
-    if dist.is_initialized():
-        T.DP_PROFILE = {"bn": [], "ar": []}
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize()
-    prof, K.GEMM_PROFILE = K.GEMM_PROFILE, None
-    # ---- data-parallel diagnostics (N > 1, or UD_FORCE_COLLECTIVES=1 on one GPU): the same eager instrumented steps.
-    # syncbn_exchange_ms: device time of the ~210 SyncBN sums of a step (HIP events around each on its stream: at N > 1 this
-    # INCLUDES the wait for the slowest peer, i.e. rank skew + xGMI latency on the forward's / backward's dependency chain);
-    # allreduce_exposed_ms: end of the backward's own kernels -> last gradient collective waited for (what the overlap did
-    # not hide); both the MAX over the ranks.
-    dp_diag = None
-    if T.DP_PROFILE is not None:
-        dpp, T.DP_PROFILE = T.DP_PROFILE, None
-        bn_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in dpp["bn"]) / prof_steps
-        ar_ms = sum(e0.elapsed_time(e1) for e0, e1, _, _ in dpp["ar"]) / prof_steps
-        worst = torch.tensor([bn_ms, ar_ms], device=dev, dtype=torch.float64)
-        dist.all_reduce(worst, op=dist.ReduceOp.MAX)
-        dp_diag = {"syncbn_exchanges_per_step": len(dpp["bn"]) / prof_steps,
-                   "syncbn_exchange_ms": float(worst[0]), "syncbn_exchange_ms_rank0": bn_ms,
-                   "syncbn_doubles_per_step": sum(n for _, _, n in dpp["bn"]) / prof_steps,
-                   "allreduce_exposed_ms": float(worst[1]), "allreduce_exposed_ms_rank0": ar_ms,
-                   "allreduce_bytes": sum(b for _, _, b, _ in dpp["ar"]) / prof_steps,
-                   "allreduce_collectives": sum(c for _, _, _, c in dpp["ar"]) / prof_steps,
-                   "measured": f"{prof_steps} eager instrumented steps after the timed region, HIP events on the launch stream; "
-                               "MAX over the ranks"}
+    # ---- --full only: the roofline of the dominant kernel, from the same step run eagerly with every ud_gemm launch
+    # bracketed by HIP events on its launch stream (events cannot be read back from inside a replayed graph)
+    prof, prof_steps, dp_diag = None, 0, None
+    if args.full:
+        prof_steps = min(args.steps, 3)
+        from unidefense_amd import tape as T
+        K.GEMM_PROFILE = []
+        if dist.is_initialized():
+            T.DP_PROFILE = {"bn": [], "ar": []}
+        for _ in range(prof_steps):
+            step()
+        torch.cuda.synchronize()
+        prof, K.GEMM_PROFILE = K.GEMM_PROFILE, None
+        # ---- data-parallel diagnostics (N > 1, or UD_FORCE_COLLECTIVES=1 on one GPU): the same eager instrumented steps.
+        # syncbn_exchange_ms: device time of the ~210 SyncBN sums of a step (HIP events around each on its stream: at N > 1 this
+        # INCLUDES the wait for the slowest peer, i.e. rank skew + xGMI latency on the forward's / backward's dependency chain);
+        # allreduce_exposed_ms: end of the backward's own kernels -> last gradient collective waited for (what the overlap did
+        # not hide); both the MAX over the ranks.
+        if T.DP_PROFILE is not None:
+            dpp, T.DP_PROFILE = T.DP_PROFILE, None
+            bn_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in dpp["bn"]) / prof_steps
+            ar_ms = sum(e0.elapsed_time(e1) for e0, e1, _, _ in dpp["ar"]) / prof_steps
+            worst = torch.tensor([bn_ms, ar_ms], device=dev, dtype=torch.float64)
+            dist.all_reduce(worst, op=dist.ReduceOp.MAX)
+            dp_diag = {"syncbn_exchanges_per_step": len(dpp["bn"]) / prof_steps,
+                       "syncbn_exchange_ms": float(worst[0]), "syncbn_exchange_ms_rank0": bn_ms,
+                       "syncbn_doubles_per_step": sum(n for _, _, n in dpp["bn"]) / prof_steps,
+                       "allreduce_exposed_ms": float(worst[1]), "allreduce_exposed_ms_rank0": ar_ms,
+                       "allreduce_bytes": sum(b for _, _, b, _ in dpp["ar"]) / prof_steps,
+                       "allreduce_collectives": sum(c for _, _, _, c in dpp["ar"]) / prof_steps,
+                       "measured": f"{prof_steps} eager instrumented steps after the timed region, HIP events on the launch stream; "
+                                   "MAX over the ranks"}
 
     if rank == 0 and args.gemm_table:
         agg = {}
@@ -557,51 +677,6 @@ def main():
                 fh.write("%7d %5d %6d %d %d %3d %3d %d | %4d %8.3f %8.3f %7.1f %9.3f\n" %
                          (*key, cnt, ms, ms / prof_steps, fl / (ms * 1e-3) / 1e12 if ms > 0 else 0, fl / 1e9 / prof_steps))
     if rank == 0:
-        # GEMM families on the matrix pipe: gemm_p3_kernel prec 2 (path 4: pre-split fp16 x 2 planes, THREE fp16 MFMAs per
-        # product tile), gemm_x3_kernel (path 2: in-kernel bf16 x 3 split, SIX bf16 MFMAs; path 3: its one-MFMA fp16 mode);
-        # everything else is gemm_kernel on the fp32 pipe.  The roofline's kernel is the family with the most time.
-        p2 = [p for p in prof if p[4] == 4]
-        x3 = [p for p in prof if p[4] in (2, 3)]
-        f32 = [p for p in prof if p[4] not in (2, 3, 4)]
-
-        def fam(ps, mfma_per_product):
-            ms = sum(p[0].elapsed_time(p[1]) for p in ps)
-            fl = sum(p[2] for p in ps)
-            ach = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-            by = sum(p[5] for p in ps)
-            return {"launches_per_step": len(ps) / prof_steps, "ms_per_step": ms / prof_steps, "gflop_per_step": fl / 1e9 / prof_steps,
-                    "achieved_tflops_fp32_equiv": ach, "mfma_per_product": mfma_per_product,
-                    "executed_mfma_tflops": ach * mfma_per_product, "frac_of_pipe": ach * mfma_per_product / BF16_PEAK_TFLOPS,
-                    "algorithmic_bytes_per_launch": by / max(len(ps), 1),
-                    "hbm_gbs": by / (ms * 1e-3) / 1e9 if ms > 0 else 0.0}
-        fam_p2 = fam(p2, 3)
-        fam_x3 = fam(x3, 1 if args.dtype == "f16" else X3_MFMA_PER_PRODUCT)
-        # the roofline's kernel: BOTH matrix-pipe kernels as one family (they share the pipe, and which of the two has more time
-        # flips with the host pacing of the eager instrumented steps): achieved = their algorithmic fp32 FLOPs / their time,
-        # executed MFMA work = 3 x the planes kernel's + 6 x the in-kernel-split kernel's algorithmic FLOPs
-        dom_name = "matrix-pipe GEMM family: gemm_p3_kernel<prec 2> + gemm_x3_kernel"
-        pipe_ms = fam_p2["ms_per_step"] + fam_x3["ms_per_step"]
-        pipe_gf = fam_p2["gflop_per_step"] + fam_x3["gflop_per_step"]
-        exec_gf = fam_p2["gflop_per_step"] * fam_p2["mfma_per_product"] + fam_x3["gflop_per_step"] * fam_x3["mfma_per_product"]
-        n_pipe = max(len(p2) + len(x3), 1)
-        dom = {"achieved_tflops_fp32_equiv": pipe_gf / pipe_ms if pipe_ms > 0 else 0.0,
-               "mfma_per_product": exec_gf / pipe_gf if pipe_gf > 0 else 6.0,
-               "algorithmic_bytes_per_launch": (sum(p[5] for p in p2) + sum(p[5] for p in x3)) / n_pipe,
-               "hbm_gbs": (sum(p[5] for p in p2) + sum(p[5] for p in x3)) / prof_steps / (pipe_ms * 1e-3) / 1e9 if pipe_ms > 0 else 0.0,
-               "launches_per_step": n_pipe / prof_steps}
-        mfma_per_product = dom["mfma_per_product"]
-        x3_ms = sum(p[0].elapsed_time(p[1]) for p in x3)
-        x3_flops = sum(p[2] for p in x3)
-        f32_ms = sum(p[0].elapsed_time(p[1]) for p in f32)
-        f32_flops = sum(p[2] for p in f32)
-        gemm_ms = x3_ms + f32_ms + fam_p2["ms_per_step"] * prof_steps
-        gemm_flops = x3_flops + f32_flops + fam_p2["gflop_per_step"] * 1e9 * prof_steps
-        achieved = dom["achieved_tflops_fp32_equiv"]                                   # algorithmic fp32 TFLOP/s of the dominant family
-        achieved_all = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        alg_bytes = dom["algorithmic_bytes_per_launch"]
-        hbm_gbs = dom["hbm_gbs"]
-        n_dom = dom["launches_per_step"]
-        traffic, traffic_src = _pmc_traffic(args, bs)
         line = {
             "metric": ("images/sec fwd+bwd (256x256, EffNet-b4)" if (args.model, args.size) == ("UDEB4", 256)
                        else f"images/sec fwd+bwd ({args.size}x{args.size}, {args.model})")
@@ -624,65 +699,12 @@ def main():
                        # the plain step's gradients)
                        "grad_l1": float(sum(p.grad.double().abs().sum() for p in params if p.grad is not None)),
                        "deterministic": cfg.deterministic},
-            "roofline": {"bound": "hbm" if args.dtype == "f16" else "mfma",
-                         "kernel": dom_name + ".  gemm_p3_kernel<prec 2> "
-                                   "(csrc/gemm_p3.hip): fp32-accurate GEMM from operands pre-split into two fp16 pieces (one "
-                                   "power-of-two scale per tensor), LDS-DMA loader waves + MFMA waves, THREE "
-                                   "v_mfma_f32_32x32x16_f16 per fp32 product tile; gemm_x3_kernel (csrc/gemm_x3.hip): every fp32 "
-                                   "operand split in the k-loop into 3 bf16 pieces, SIX v_mfma_f32_32x32x16_bf16 per tile.  "
-                                   "achieved = algorithmic fp32 FLOPs (2MNK) of the family's launches / their HIP-event time; "
-                                   "peak = the pipe's dense 16-bit peak (2500 TFLOP/s) / executed MFMAs per algorithmic product, "
-                                   "so frac = executed MFMA work / pipe peak",
-                         "achieved": achieved, "peak": BF16_PEAK_TFLOPS / mfma_per_product, "unit": "TFLOP/s",
-                         "frac": achieved * mfma_per_product / BF16_PEAK_TFLOPS,
-                         "executed_mfma_tflops": achieved * mfma_per_product, "pipe_peak": BF16_PEAK_TFLOPS,
-                         "mfma_per_product": mfma_per_product,
-                         "frac_of_pipe": achieved * mfma_per_product / BF16_PEAK_TFLOPS,
-                         # for comparison with rounds 1-3, whose GEMMs all executed six MFMAs per product: the same algorithmic
-                         # throughput priced at six (what the round-3 kernel would have had to execute for it)
-                         "frac_six_product_equiv": achieved * X3_MFMA_PER_PRODUCT / BF16_PEAK_TFLOPS,
-                         # the same launches priced as fp32 work against the fp32 matrix peak (bounded by 2.67, not 1)
-                         "frac_fp32_equiv": achieved / MFMA_F32_PEAK_TFLOPS,
-                         # HBM side of the same launches: algorithmic operand + result bytes (storage types as launched) /
-                         # their HIP-event time, against 8 TB/s — the bound that matters in the f16 mode, where one fp16
-                         # MFMA per product tile leaves the GEMMs memory-bound
-                         "hbm": {"achieved": hbm_gbs, "peak": 8000.0, "unit": "GB/s", "frac": hbm_gbs / 8000.0},
-                         "traffic": traffic,
-                         "traffic_unit": "HBM bytes per launch (mean over the dominant family's launches of a step)",
-                         "traffic_source": traffic_src, "algorithmic_bytes_per_launch": alg_bytes,
-                         "launches_per_step": n_dom,
-                         "families": {"gemm_p3_kernel<prec 2>": fam_p2, "gemm_x3_kernel": fam_x3},
-                         "x3_ms_per_step": x3_ms / prof_steps, "x3_gflop_per_step": x3_flops / 1e9 / prof_steps,
-                         # the rest of the GEMM family: gather-mode 3x3 convs / tiny shapes on v_mfma_f32_32x32x2_f32
-                         "fp32_pipe_kernel": {"launches_per_step": len(f32) / prof_steps, "ms_per_step": f32_ms / prof_steps,
-                                              "gflop_per_step": f32_flops / 1e9 / prof_steps,
-                                              "achieved_tflops": f32_flops / (f32_ms * 1e-3) / 1e12 if f32_ms > 0 else 0.0,
-                                              "peak": MFMA_F32_PEAK_TFLOPS},
-                         "gemm_ms_per_step": gemm_ms / prof_steps,
-                         "gemm_gflop_per_step": gemm_flops / 1e9 / prof_steps,
-                         "gemm_family_tflops_fp32_equiv": achieved_all,
-                         "measured": f"{prof_steps} EAGER steps after the timed region, HIP events around every launch on its "
-                                     "stream (events cannot be read inside the replayed graph the headline number comes "
-                                     "from; these steps launch every product by itself — the replayed step sends the data and "
-                                     "weight gradient of a 1x1 conv out as ONE grid of the planes kernel, ud_gemm_p3_pair, "
-                                     "which is ~0.5 ms per step faster than the sum timed here); profiles/r06/ holds the rocprofv3 --kernel-trace --stats summary of the "
-                                     "graph-replayed steps of this same command (tools/gpu_round.sh), and "
-                                     "tools/roofline_from_rocprof.py recomputes these numbers from it"},
         }
-        # the same quantities from the rocprofv3 summary of the graph-REPLAYED steps of this command (committed under profiles/,
-        # printed only when stamped with this tree's GEMM sources): what `frac` above under-states by timing eager, un-paired launches
-        rep = _committed(args, bs, "roofline_replayed.json", "gemm_src_sha", _gemm_src_sha())
-        line["roofline"]["replayed"] = rep
-        # per kernel CLASS: launches, ms, GB moved and GB/s from the PMC passes (tools/hbm_bw_table.py --json)
-        cls = _committed(args, bs, "hbm_classes.json", "csrc_sha", _csrc_sha())
-        line["roofline"]["classes"] = cls
+        line["roofline"] = {"bound": "hbm" if args.dtype == "f16" else "mfma"}
+        if args.full:
+            line["roofline"].update(gemm_roofline(args, bs, prof, prof_steps))
         if dp_diag is not None:
             line["data_parallel"] = dp_diag
-        if args.dtype == "f16":
-            # informational f16 line: the HBM side is the roofline (bound "hbm"); the matrix-pipe numbers move to "mfma"
-            r = line["roofline"]
-            r["mfma"] = {k: r[k] for k in ("achieved", "peak", "unit", "frac")}
-            r.update(achieved=hbm_gbs, peak=8000.0, unit="GB/s", frac=hbm_gbs / 8000.0)
         if (args.model, args.size) == ("UDEB4", 256):
             # whole-step fractions from the algorithmic work per image (fwd+bwd, fp32):
             # 68.9 GFLOP and 1044 MB at bs 32 — per GPU, against the fp32 matrix peak and 8 TB/s
@@ -694,10 +716,10 @@ def main():
             b_alg = (act_mb + 3 * 4 * 128.31 / bs) * 1e6
             line["roofline"]["step_algorithmic_bytes_per_image"] = b_alg
             line["roofline"]["step_achieved_hbm_frac"] = b_alg * ips / 8e12
-        if world == 1 and not args.no_extra and (args.model, args.size, bs, args.dtype) == ("UDEB4", 256, 32, "f32"):
+        if args.full and world == 1 and not args.no_extra and (args.model, args.size, bs, args.dtype) == ("UDEB4", 256, 32, "f32"):
             torch.cuda.empty_cache()
             line["extra"] = extra_measurements()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
     if dist.is_initialized():
         dist.destroy_process_group()
@@ -709,6 +731,9 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except OSError:
             pass
+        t_end = time.perf_counter()
+        print(f"[bench] {t_end - T_START:.1f} s in all: {t_ready - T_START:.1f} s imports + model + inputs, {t0 - t_ready:.1f} s "
+              f"warm-up (eager steps, capture, replays), {elapsed:.1f} s timed, {t_end - t0 - elapsed:.1f} s after", file=sys.stderr)
         print(json.dumps(line), flush=True)
 
 

@@ -15,11 +15,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def _bench(extra_env, *flags):
+def _bench(extra_env, *flags, full=True):
     env = dict(os.environ, **extra_env)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--no-cpu-baseline", *flags]
+           *(("--full", "--no-cpu-baseline") if full else ()), *flags]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -65,6 +65,23 @@ def test_bench_line_contract():
     assert 0.0 < d["syncbn_exchange_ms"] < 10.0, d
     assert abs(d["allreduce_bytes"] - 4 * 128.31e6) < 2e6, d             # every trainable parameter's gradient, fp32, once
     assert 20 <= d["allreduce_collectives"] <= 80, d                     # ~34 in-place spectral weights + the packed buckets
+
+
+def test_bench_plain_line():
+    """Without --full the line carries the headline figure and nothing measured by runs of its own."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    line, err = _bench({}, full=False)
+    for k, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
+                   ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str), ("config", dict), ("roofline", dict)):
+        assert isinstance(line[k], typ), (k, line.get(k))
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["config"]["exec"] == "hipgraph", err[-1500:]
+    assert abs(line["value"] - 8 * 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+    assert line["config"]["grad_l1"] > 0
+    assert not {"extra", "cpu_baseline", "data_parallel"} & set(line), sorted(line)
+    r = line["roofline"]
+    assert set(r) == {"bound", "step_achieved_mfma_frac", "step_algorithmic_bytes_per_image", "step_achieved_hbm_frac"}, r
+    assert 0.0 < r["step_achieved_mfma_frac"] < 1.0 and 0.0 < r["step_achieved_hbm_frac"] < 1.0
 
 
 @pytest.mark.parametrize("flags", [(), ("--eager",)])

@@ -13,13 +13,13 @@ if [ "$2" != "nopytest" ]; then
   echo "pytest exit $?"; grep -E "passed|failed|error" $out/pytest_gpu.log | tail -3
 fi
 export UD_GEMM_TUNE_CACHE=$PWD/$out/gemm_plans.json      # the profiled runs below repeat the benchmarked plans
-echo "== bench (default flags)"
-timeout 1200 python bench.py --gemm-table $out/gemm_table.txt > $out/bench.json 2> $out/bench.err
+echo "== bench --full"
+timeout 1200 python bench.py --full --gemm-table $out/gemm_table.txt > $out/bench.json 2> $out/bench.err
 echo "bench exit $?"; tail -1 $out/bench.json | cut -c1-400
 echo "== rocprofv3 kernel stats (STEPS executed: 2 eager warm-ups + 3 + 10 replays + 3 eager instrumented = 18)"
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o bench -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra > $out/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o bench -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extra > $out/bench_under_rocprof.log 2>&1
 echo "rocprof exit $?"
 find $out/prof -name "*kernel_trace.csv" -delete
 f=$(find $out/prof -name "*kernel_stats.csv" | head -1)

@@ -6,7 +6,7 @@ mkdir -p $out
 export PYTHONDONTWRITEBYTECODE=1
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o bench -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o bench -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $out/bench.log 2>&1
 find $out/prof -name "*kernel_trace.csv" -delete
 f=$(find $out/prof -name "*kernel_stats.csv" | head -1)
 cp "$f" $out/kernel_stats.csv
