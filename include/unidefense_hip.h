@@ -430,6 +430,23 @@ long ud_conv_small_wgrad_ws_floats(int Cin, int Ma);
 int ud_conv_small_wgrad(const ud_conv_geom* g, const float* a, const float* x, float* part, float* out, int Ma,
                         ud_stream_t stream);
 
+/* ---- gradient with respect to the input image (csrc/inputgrad.hip): x.grad of model(x) ----------------------------
+ * ud_stem_dgrad   : dx[N][3][Hin][Win] (+= when accumulate) the data gradient of the stem conv g (F.conv2d geometry, Cin 3,
+ *                   stride 2) from dy[N][Hout][Wout][Cout] (pixel-major) and the module weight w[Cout][3][KH][KW]
+ *                   (model/efficientnet/model.py:185, 3x3 -> 48 with static SAME pads; model/resnet/exp.py:395, 7x7 -> 64,
+ *                   pad 3).  dx is x's planes layout; accumulate adds onto the gradient already there.  dy 16-byte aligned.
+ *                   ud_stem_dgrad_supported: 1 for (Cin, Cout, KH, KW, stride) = (3, 48, 3, 3, 2) or (3, 64, 7, 7, 2), else 0;
+ *                   any other geometry (or a pad outside [0, KH)) is UD_EINVAL.
+ * ud_absdiff_bwd  : gradients of out = |a - b|: da = sign(a - b) g, db = -sign(a - b) g, sign(0) = 0 as in torch.abs
+ *                   (model/unidefense.py:138,148: the attention's difference inputs); da or db may be NULL.
+ * ud_outer        : out[M][D] = u[M] v[D] (the difference inputs' gradient of a dynamic filter, model/modules.py:94-104:
+ *                   dlogit times the filter weights of those channels). */
+int ud_stem_dgrad_supported(int Cin, int Cout, int KH, int KW, int stride);
+int ud_stem_dgrad(const ud_conv_geom* g, const float* dy, const float* w, float* dx, int Cout, int accumulate,
+                  ud_stream_t stream);
+int ud_absdiff_bwd(const float* a, const float* b, const float* g, float* da, float* db, long total, ud_stream_t stream);
+int ud_outer(const float* u, const float* v, float* out, long M, int D, ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

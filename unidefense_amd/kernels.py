@@ -1399,6 +1399,53 @@ def conv_gather_nt(x, wmat, g):
     return out
 
 
+_STEM_DGRAD_OK = {}
+
+
+def stem_dgrad_supported(Ci, Co, KH, KW, stride):
+    key = (Ci, Co, KH, KW, stride)
+    if key not in _STEM_DGRAD_OK:
+        _STEM_DGRAD_OK[key] = _call("ud_stem_dgrad_supported", Ci, Co, KH, KW, stride) == 1
+    return _STEM_DGRAD_OK[key]
+
+
+def stem_dgrad(dy, w, g, out=None):
+    """Data gradient of a stem conv (3 input channels, stride 2; csrc/inputgrad.hip) straight into x's planes layout:
+    dy [N, Hout, Wout, Co] pixel-major, w the module weight [Co, 3, KH, KW], g the forward's ud_conv_geom.  Returns dx
+    [N, 3, Hin, Win]; with `out` (x's gradient so far) the result is added onto it in place."""
+    Co = w.shape[0]
+    if not stem_dgrad_supported(g.Cin, Co, g.KH, g.KW, g.stride):
+        raise ValueError(f"no stem data-gradient kernel for Cin {g.Cin}, Cout {Co}, {g.KH}x{g.KW} / {g.stride}")
+    dy = dy.contiguous()
+    w = w.contiguous()
+    _chk(dy, w, out)
+    assert dy.numel() == g.N * g.Hout * g.Wout * Co and w.numel() == Co * 3 * g.KH * g.KW and dy.data_ptr() % 16 == 0
+    acc = out is not None
+    if acc:
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == g.N * 3 * g.Hin * g.Win
+    else:
+        out = empty((g.N, 3, g.Hin, g.Win), dy)
+    _call("ud_stem_dgrad", C.byref(g), _p(dy), _p(w), _p(out), Co, 1 if acc else 0, _stream())
+    return out
+
+
+def absdiff_bwd(a, b, g):
+    """gradient of |a - b| with respect to b: -sign(a - b) g (sign(0) = 0, as torch.abs)"""
+    _chk(a, b, g)
+    db = torch.empty_like(b)
+    _call("ud_absdiff_bwd", _p(a), _p(b), _p(g), None, _p(db), b.numel(), _stream())
+    return db
+
+
+def outer(u, v):
+    """out[M, D] = u[M] v[D]"""
+    _chk(u, v)
+    M, D = u.numel(), v.numel()
+    out = empty((M, D), u)
+    _call("ud_outer", _p(u), _p(v), _p(out), M, D, _stream())
+    return out
+
+
 def conv_gather_wgrad(a, x, g):
     """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)]."""
     _chk(a, x)
@@ -1895,13 +1942,13 @@ def fc_fwd(x, W, b, act_in=0):
     return y
 
 
-def fc_bwd(dy, W, x, act_in=0, need_dx=True, need_db=True):
+def fc_bwd(dy, W, x, act_in=0, need_dx=True, need_db=True, need_dw=True):
     _chk(dy, W, x)
     N, I = x.shape
     O = W.shape[0]
     dx = empty((N, I), x) if need_dx else None
-    dW = empty((O, I), x)
-    db = empty((O,), x) if need_db else None
+    dW = empty((O, I), x) if need_dw else None
+    db = empty((O,), x) if (need_db and need_dw) else None
     _call("ud_fc_bwd", _p(dy), _p(W), _p(x), _p(dx), _p(dW), _p(db), N, I, O, act_in, _stream())
     return dx, dW, db
 

@@ -142,6 +142,12 @@ class _NetFunction(torch.autograd.Function):
     def forward(ctx, model, x, noise_x, rng, *params):
         K.begin_forward(model)     # fresh zero blocks (a captured step fills every block it carves from); weight planes in two launches
         tape = T.Tape()
+        # x.grad: the input image is tracked when it requires grad and feeds the encoder itself (a perturbed copy does not
+        # pass a gradient back: no gradient through the perturbation functions); a model with no parameter requiring grad in
+        # eval mode (frozen, the tape exists only for x) launches no weight-gradient work
+        if ctx.needs_input_grad[1] and noise_x is None:
+            tape.input = x
+        tape.wgrad_on = model.training or any(ctx.needs_input_grad[4:])
         debug = getattr(model, "_debug_watch", False)
         if debug:
             tape.kinks = {}
@@ -159,6 +165,7 @@ class _NetFunction(torch.autograd.Function):
         ctx.tape = tape
         ctx.outs = outs
         ctx.params = params
+        ctx.x_tracked = tape.input is not None
         ctx.model = model
         ctx.keys = model._out_keys
         return tuple(outs[k] for k in ctx.keys)
@@ -169,8 +176,10 @@ class _NetFunction(torch.autograd.Function):
         K.reset_zero_pool()
         # data parallel (engine/parallel.py): scaling the incoming gradient by 1/world turns the reducer's SUM into
         # the mean; gradients are handed over as they become final so that their all-reduce overlaps the rest of
-        # this backward (use counts per parameter are learned on the first backward, which reduces at its end)
-        reducer = getattr(model, "_grad_reducer", None)
+        # this backward (use counts per parameter are learned on the first backward, which reduces at its end).  A frozen
+        # model's backward (tape.wgrad_on False: only x.grad) has no parameter gradient to exchange: it leaves the reducer,
+        # its prescale and the learned use counts alone
+        reducer = getattr(model, "_grad_reducer", None) if tape.wgrad_on else None
         scale = getattr(model, "_grad_prescale", 1.0) if reducer is not None else 1.0
         uses = getattr(model, "_param_uses", None)
         if reducer is not None:
@@ -195,8 +204,12 @@ class _NetFunction(torch.autograd.Function):
             red = reducer.finish()
             grads = [None if g is None else red[id(p)] for p, g in zip(ctx.params, grads)]
         grads = _accumulate_in_place(model, ctx.params, grads)
+        dx = tape.input_grad if ctx.x_tracked else None
+        if dx is not None and scale != 1.0:
+            dx = K.axpby(dx, 1.0 / scale)          # x.grad stays the rank's own gradient (as with DistributedDataParallel)
+        tape.input = tape.input_grad = None
         ctx.tape = ctx.outs = ctx.model = None
-        return (None, None, None, None) + tuple(grads)
+        return (None, dx, None, None) + tuple(grads)
 
 
 class UniDefenseModelEb4(nn.Module):
@@ -290,9 +303,15 @@ class UniDefenseModelEb4(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("unidefense_amd runs on the GPU only (no CPU path); move the model and input to cuda")
         x = x.contiguous().to(torch.float32)
+        if cfg.side_branch and noise_x is None and x.requires_grad and torch.is_grad_enabled() and \
+                isinstance(self, UniDefenseModelEb4):
+            # refused before anything runs (no BatchNorm statistics moved): the branch's second stream does not form x.grad
+            raise RuntimeError("cfg.side_branch = 1 does not compute gradients with respect to the input image (UDEB4): set "
+                               "cfg.side_branch = 0, or run the forward with an input that does not require grad")
         # a tape is built whenever autograd would record: training, or an eval-mode forward outside no_grad() whose
-        # parameters require gradients (fine-tuning on frozen BatchNorm statistics; the reference is plain autograd)
-        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())):
+        # parameters or input require gradients (fine-tuning on frozen BatchNorm statistics; x.grad of a frozen model for an
+        # attack or a saliency map; the reference is plain autograd)
+        if torch.is_grad_enabled() and (self.training or x.requires_grad or any(p.requires_grad for p in self.parameters())):
             params = tuple(self.parameters())
             vals = _NetFunction.apply(self, x, noise_x, rng, *params)
             outs = dict(zip(self._out_keys, vals))
@@ -452,25 +471,21 @@ class UniDefenseModelEb4(nn.Module):
         return x
 
     def _attention(self, tape, pred_planes, x_planes, emb, rng):
-        """UniDefenseModelEb4.attention (model/unidefense.py:125-157); pred/x carry no gradient."""
+        """UniDefenseModelEb4.attention (model/unidefense.py:125-157); pred carries no gradient, x when the tape tracks it."""
         N, h, w, Cc = emb.shape
         norm = self.freq_norm
-        pred = K.planes_to_pix(K.bilinear_fwd(pred_planes, h, w))       # [N,h,w,3]
-        xs = K.planes_to_pix(K.bilinear_fwd(x_planes, h, w))
-        sf, _ = T._fft_scales(h, norm)
-        freq_diff = K.absdiff(K.rfft2(pred, sf), K.rfft2(xs, sf))       # [N,h,w/2+1,6]
+        freq_diff, spat_diff, dg = T.attention_diffs(tape, pred_planes, x_planes, h, w, norm)   # [N,h,w/2+1,6], [N,h,w,3]
         emb_freq = T.rfft2_cat(tape, emb, norm)                         # [N,h,w/2+1,2C]
         ff = self.freq_filter
         proj = T.bias_add(tape, T.conv1x1(tape, emb_freq, ff.layer1[0].weight), ff.layer1[0].bias)
         proj = self._bn(tape, proj, ff.layer1[1], 1)
-        f_out, freq_mask = T.dynamic_filter(tape, emb_freq, proj, freq_diff, ff.layer2[0].weight, ff.layer2[0].bias)
+        f_out, freq_mask = T.dynamic_filter(tape, emb_freq, proj, freq_diff, ff.layer2[0].weight, ff.layer2[0].bias, dg)
         freq_filtered = T.irfft2_split(tape, f_out, norm)
 
-        spat_diff = K.absdiff(pred, xs)                                  # [N,h,w,3]
         sfm = self.spat_filter
         proj = T.bias_add(tape, T.conv_dense(tape, emb, sfm.layer1[0].weight, 1, 1, 1, h, w), sfm.layer1[0].bias)
         proj = self._bn(tape, proj, sfm.layer1[1], 1)
-        s_out, spat_mask = T.dynamic_filter(tape, emb, proj, spat_diff, sfm.layer2[0].weight, sfm.layer2[0].bias)
+        s_out, spat_mask = T.dynamic_filter(tape, emb, proj, spat_diff, sfm.layer2[0].weight, sfm.layer2[0].bias, dg)
 
         out = T.gate_mix(tape, s_out, freq_filtered, self.fuse_coef)
         e = emb
@@ -538,6 +553,7 @@ class UniDefenseModelEb4(nn.Module):
         T.DW_WT = {id(w): (w, w._version, wts[id(w)]) for w in ws}       # looked up by the unfused tape.dwconv
 
         x_pix = K.planes_to_pix(x if noise_x is None else noise_x)       # [N,H,W,3]
+        x_in = x if noise_x is None else None                            # the stem's data gradient goes to x (tape.input)
         # Half storage (BASELINE configs[4]): the MBConv trunk keeps its activations and their gradients in fp16 (fp32
         # registers, fp64 BatchNorm sums, fp32 weights / weight gradients, fp16 MFMA); stem conv, decoder, attention,
         # head and losses stay fp32 — T.cast at the boundaries.  Fused training path only.
@@ -552,7 +568,7 @@ class UniDefenseModelEb4(nn.Module):
             if bb._bn0.num_batches_tracked is not None:
                 self.__dict__.setdefault("_nbt_pending", []).append(bb._bn0.num_batches_tracked)
             h, lazy = T.stem_fused(tape, x_pix, bb._conv_stem.weight, bb._bn0, 2, pt, pl, Ho, Wo, dp,
-                                   torch.float16 if st16 else f32)
+                                   torch.float16 if st16 else f32, x_planes=x_in)
             x_b0 = self._blocks(tape, h, 0, rng, lazy)
         elif ev16:
             # the stem conv's output rounded once to half; its eval BatchNorm + swish applied on load by block 0's depthwise conv
@@ -560,7 +576,7 @@ class UniDefenseModelEb4(nn.Module):
             h = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False).to(torch.float16)
             x_b0 = self._blocks(tape, h, 0, rng, K.EvalBN(bb._bn0, 1))
         else:
-            h = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False)
+            h = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False, x_planes=x_in)
             h = self._bn(tape, h, bb._bn0, 1)
             x_b0 = self._blocks(tape, h, 0, rng)
         x_b1 = self._blocks(tape, x_b0, 1, rng)

@@ -194,7 +194,7 @@ class UniDefenseModelRes18(nn.Module):
         rng = self._prepare_rng(rng)
         ex = self.extractor
         x_pix = K.planes_to_pix(x if noise_x is None else noise_x)
-        h = T.conv_dense_any(tape, x_pix, ex.conv1.weight, 2, 3, need_dx=False)
+        h = T.conv_dense_any(tape, x_pix, ex.conv1.weight, 2, 3, need_dx=False, x_planes=x if noise_x is None else None)
         h = self._bn(tape, h, ex.bn1, 2)
         p1 = self._basic_block(tape, self._basic_block(tape, h, ex.layer1[0]), ex.layer1[1])
         p2 = self._basic_block(tape, self._basic_block(tape, p1, ex.layer2[0]), ex.layer2[1])
@@ -228,21 +228,17 @@ class UniDefenseModelRes18(nn.Module):
         # attention (model/unidefense.py:326-361) with ReLU filters
         n_, hh, ww, Cc = emb.shape
         norm = self.freq_norm
-        pred = K.planes_to_pix(K.bilinear_fwd(dec2, hh, ww))
-        xs = K.planes_to_pix(K.bilinear_fwd(x, hh, ww))
-        sf, _ = T._fft_scales(hh, norm)
-        freq_diff = K.absdiff(K.rfft2(pred, sf), K.rfft2(xs, sf))
+        freq_diff, spat_diff, dg = T.attention_diffs(tape, dec2, x, hh, ww, norm)
         emb_freq = T.rfft2_cat(tape, emb, norm)
         ff = self.freq_filter
         proj = T.bias_add(tape, T.conv1x1(tape, emb_freq, ff.layer1[0].weight), ff.layer1[0].bias)
         proj = self._bn(tape, proj, ff.layer1[1], 2)
-        f_out, freq_mask = T.dynamic_filter(tape, emb_freq, proj, freq_diff, ff.layer2[0].weight, ff.layer2[0].bias)
+        f_out, freq_mask = T.dynamic_filter(tape, emb_freq, proj, freq_diff, ff.layer2[0].weight, ff.layer2[0].bias, dg)
         freq_filtered = T.irfft2_split(tape, f_out, norm)
-        spat_diff = K.absdiff(pred, xs)
         sfm = self.spat_filter
         proj = T.bias_add(tape, T.conv_dense_any(tape, emb, sfm.layer1[0].weight, 1, 1), sfm.layer1[0].bias)
         proj = self._bn(tape, proj, sfm.layer1[1], 2)
-        s_out, spat_mask = T.dynamic_filter(tape, emb, proj, spat_diff, sfm.layer2[0].weight, sfm.layer2[0].bias)
+        s_out, spat_mask = T.dynamic_filter(tape, emb, proj, spat_diff, sfm.layer2[0].weight, sfm.layer2[0].bias, dg)
         att = T.gate_mix(tape, s_out, freq_filtered, self.fuse_coef)
         e = emb
         if self.training and self.drop_rate > 0:

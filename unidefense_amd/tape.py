@@ -42,6 +42,16 @@ class Tape:
         self.side_nodes = set()  # id(fn) of the closures recorded on it
         self._in_side = False
         self._side_param_grads = []
+        # gradient with respect to the input image: `input` is the tracked x planes [N,3,H,W] (model(x) with x.requires_grad
+        # and no perturbation), its gradient is left in `input_grad` by backward().  wgrad_on = False: no parameter takes a
+        # gradient (a frozen eval-mode model), so the operators launch no weight-gradient work
+        self.input = None
+        self.input_grad = None
+        self.wgrad_on = True
+
+    def tracks(self, t) -> bool:
+        """is t the tracked input image?"""
+        return self.input is not None and t is self.input
 
     # -- recording -------------------------------------------------------------------------
     def record(self, fn):
@@ -68,6 +78,8 @@ class Tape:
         return g
 
     def add_param_grad(self, p, g: torch.Tensor):
+        if not self.wgrad_on:
+            return
         cur = self.param_grads.get(p)
         deferred = getattr(g, "_ud_deferred", False)
         if (deferred or id(p) in self._deferred) and (cur is not None or self.param_ready is not None):
@@ -106,6 +118,8 @@ class Tape:
                 self._backward_two_streams()
         finally:
             K.flush_wgrad_folds(end=True)
+        if self.input is not None:
+            self.input_grad = self.grads.get(id(self.input))
         self.nodes = []
         self.grads = {}
         self._keep = []
@@ -156,6 +170,14 @@ def _needs(tape):
     return tape is not None
 
 
+def _tracks(tape, t):
+    return tape is not None and tape.tracks(t)
+
+
+def _wgrad(tape):
+    return tape.wgrad_on
+
+
 _SIDE_STREAMS = {}
 
 
@@ -170,6 +192,8 @@ class side_branch:
     def __init__(self, tape, like, inputs=()):
         self.tape = tape
         self.on = bool(tape is not None and cfg.side_branch and like.is_cuda and tape.side is None)
+        # (UniDefenseModelEb4.forward refuses a tracked input with the branch on before the forward starts)
+        assert not (self.on and tape.input is not None), "side branch with a tracked input image"
         self.like, self.inputs = like, inputs
         self.ctx = None
 
@@ -237,7 +261,8 @@ def bias_add(tape, y, b):
             if d is None:
                 return
             tape.add_grad(y, d)
-            tape.add_param_grad(b, d.reshape(-1, d.shape[-1]).sum(0))
+            if _wgrad(tape):
+                tape.add_param_grad(b, d.reshape(-1, d.shape[-1]).sum(0))
         tape.record(bwd)
     return out
 
@@ -259,7 +284,10 @@ def conv1x1(tape, x, w, need_dx=True):
         if dy is None:
             return
         dy2 = dy.reshape(-1, Co)
-        if need_dx:
+        if not _wgrad(tape):
+            if need_dx:
+                tape.add_grad(x, K.spectral_dgrad(ctx, dy2).view(x.shape))
+        elif need_dx:
             dx, dw = K.spectral_bwd(ctx, dy2)          # (one launch on the planes GEMM where both plans allow)
             tape.add_param_grad(w, dw)
             tape.add_grad(x, dx.view(x.shape))
@@ -284,25 +312,41 @@ def _conv_im2col(tape, x, w, wmat, g, need_dx):
             dy2 = dy.reshape(-1, Co)
             if not dy2.is_contiguous():
                 dy2 = dy2.contiguous()
-            if need_dx:
+            if not _wgrad(tape):
+                dcol, dw = (K.spectral_dgrad(ctx, dy2) if need_dx else None), None
+            elif need_dx:
                 dcol, dw = K.spectral_bwd(ctx, dy2)                    # dw [Co, KH*KW*Ci]
             else:
                 dcol, dw = None, K.spectral_wgrad(ctx, dy2)
-            tape.add_param_grad(w, dw.view(Co, KH, KW, Ci).permute(0, 3, 1, 2).contiguous())
+            if dw is not None:
+                tape.add_param_grad(w, dw.view(Co, KH, KW, Ci).permute(0, 3, 1, 2).contiguous())
             if need_dx:
                 tape.add_grad(x, K.col2im(dcol, g))
         tape.record(bwd)
     return y
 
 
-def conv_dense(tape, x, w, stride, pad_t, pad_l, Hout, Wout, need_dx=True):
+def _stem_dgrad(tape, dy, w, g, x_planes):
+    """the stem conv's data gradient (kernels.stem_dgrad) added onto the tracked input image's gradient: the stem's backward
+    runs last, so the attention's and the reconstruction losses' parts are already there and one pass completes dx"""
+    cur = tape.grads.pop(id(x_planes), None)
+    if cur is not None and not (cur.is_contiguous() and cur.dtype == torch.float32 and cur.shape == x_planes.shape):
+        tape.grads[id(x_planes)], cur = cur, None
+    tape.add_grad(x_planes, K.stem_dgrad(dy, w, g, out=cur))
+
+
+def conv_dense(tape, x, w, stride, pad_t, pad_l, Hout, Wout, need_dx=True, x_planes=None):
     """Dense k x k F.conv2d (weight [Cout,Cin,kh,kw]) as an implicit GEMM (model/unidefense.py:60,67,...;
-    model/modules.py:111; stem conv model/efficientnet/model.py:185 with its static asymmetric pad)."""
+    model/modules.py:111; stem conv model/efficientnet/model.py:185 with its static asymmetric pad).
+    x_planes: the stem's input image as planes — when it is the tape's tracked input, its data gradient is formed
+    (kernels.stem_dgrad) instead of the need_dx gather."""
     N, Hin, Win, Ci = x.shape
     Co, _, KH, KW = w.shape
     g = K.conv_geom(N, Hin, Win, Ci, Hout, Wout, KH, KW, stride, pad_t, pad_l, 0)
     wmat = K.weight_layout(w, 0)
+    stem_dx = _tracks(tape, x_planes)
     if K.conv_im2col_ok(g, Co, x):
+        assert not stem_dx
         return _conv_im2col(tape, x, w, wmat, g, need_dx)
     y = K.conv_gather_nt(x, wmat, g)
     if _needs(tape):
@@ -317,8 +361,11 @@ def conv_dense(tape, x, w, stride, pad_t, pad_l, Hout, Wout, need_dx=True):
                 assert stride == 1 and Hout == Hin and Wout == Win, "data gradient implemented for stride 1 'same'"
                 gd = K.conv_geom(N, Hout, Wout, Co, Hin, Win, KH, KW, 1, KH - 1 - pad_t, KW - 1 - pad_l, 0)
                 tape.add_grad(x, K.conv_gather_nt(dy, wd, gd))
-            dw = K.conv_gather_wgrad(dy.view(-1, Co), x, g)            # [Co, KH*KW*Ci]
-            tape.add_param_grad(w, dw.view(Co, KH, KW, Ci).permute(0, 3, 1, 2).contiguous())
+            elif stem_dx:
+                _stem_dgrad(tape, dy, w, g, x_planes)
+            if _wgrad(tape):
+                dw = K.conv_gather_wgrad(dy.view(-1, Co), x, g)        # [Co, KH*KW*Ci]
+                tape.add_param_grad(w, dw.view(Co, KH, KW, Ci).permute(0, 3, 1, 2).contiguous())
         tape.record(bwd)
     return y
 
@@ -342,8 +389,9 @@ def conv_transpose_s2(tape, x, w):
             # dX[n,ih,iw,ci] = sum dY[n,2ih-1+kh,2iw-1+kw,co] W[ci,co,kh,kw]: a stride-2 conv over dY
             gd = K.conv_geom(N, Ho, Wo, Co, H, W, KH, KW, 2, 1, 1, 0)
             tape.add_grad(x, K.conv_gather_nt(dy, wd, gd))
-            dw = K.conv_gather_wgrad(x.view(-1, Ci), dy, gd)           # [Ci, KH*KW*Co]
-            tape.add_param_grad(w, dw.view(Ci, KH, KW, Co).permute(0, 3, 1, 2).contiguous())
+            if _wgrad(tape):
+                dw = K.conv_gather_wgrad(x.view(-1, Ci), dy, gd)       # [Ci, KH*KW*Co]
+                tape.add_param_grad(w, dw.view(Ci, KH, KW, Co).permute(0, 3, 1, 2).contiguous())
         tape.record(bwd)
     return y
 
@@ -356,10 +404,12 @@ def linear(tape, x, w, b):
             dy = tape.pop_grad(y)
             if dy is None:
                 return
-            dx, dW, db = K.fc_bwd(dy, w, x, 0)
+            wg = _wgrad(tape)
+            dx, dW, db = K.fc_bwd(dy, w, x, 0, need_dw=wg)
             tape.add_grad(x, dx)
-            tape.add_param_grad(w, dW)
-            tape.add_param_grad(b, db)
+            if wg:
+                tape.add_param_grad(w, dW)
+                tape.add_param_grad(b, db)
         tape.record(bwd)
     return y
 
@@ -467,7 +517,8 @@ def dwconv(tape, x, w, stride, pad):
             if cur is not None and not (cur.is_contiguous() and cur.shape == x.shape and cur.dtype == torch.float32):
                 tape.grads[id(x)], cur = cur, None
             tape.add_grad(x, K.dwconv_bwd_data(dy, wt, k, stride, pt, pl, H, W, add=cur))
-            tape.add_param_grad(w, K.dwconv_bwd_weight(x, dy, k, stride, pt, pl))     # already [C, k*k]
+            if _wgrad(tape):
+                tape.add_param_grad(w, K.dwconv_bwd_weight(x, dy, k, stride, pt, pl))     # already [C, k*k]
         tape.record(bwd)
     return y
 
@@ -640,8 +691,12 @@ def batchnorm_act(tape, x, weight, bias, running_mean, running_var, eps, momentu
                 # eval mode: the statistics are constants (running_mean / running_var), so dx = gamma * invstd * dz with
                 # dz = dy * act'(z) — the training formula with its two mean terms dropped (sums passed as zeros) — and
                 # dgamma = sum dz * xhat, dbeta = sum dz as in training
-                s, dg, db = K.norm_bwd_sums(x2, dy.view(-1, Cc), 1, R, mean, invstd, weight, bias, act)
-                dx = K.norm_bwd_apply(x2, dy.view(-1, Cc), 1, R, mean, invstd, weight, bias, torch.zeros_like(s), 0.0, act)
+                if _wgrad(tape):
+                    s, dg, db = K.norm_bwd_sums(x2, dy.view(-1, Cc), 1, R, mean, invstd, weight, bias, act)
+                    zs = torch.zeros_like(s)
+                else:                      # a frozen model: no dgamma / dbeta, and dx needs no sums
+                    zs, dg = K.zeros((2, 1, Cc), x2), None     # (carved from the zero pool: no launch)
+                dx = K.norm_bwd_apply(x2, dy.view(-1, Cc), 1, R, mean, invstd, weight, bias, zs, 0.0, act)
             elif synced:
                 import torch.distributed as dist
                 s, dg, db = K.norm_bwd_sums(x2, dy.view(-1, Cc), 1, R, mean, invstd, weight, bias, act)
@@ -651,7 +706,7 @@ def batchnorm_act(tape, x, weight, bias, running_mean, running_var, eps, momentu
             else:
                 dx, dg, db = (K.norm_bwd_fused if one else K.norm_bwd)(x2, dy.view(-1, Cc), 1, R, mean, invstd, weight, bias, act)
             tape.add_grad(x, dx.view(x.shape))
-            if affine:
+            if affine and dg is not None:
                 tape.add_param_grad(weight, dg)
                 if bias.requires_grad:
                     tape.add_param_grad(bias, db)
@@ -757,9 +812,12 @@ def squeeze_excite(tape, x, w_r, b_r, w_e, b_e):
                 return
             ds2 = K.group_coldot(dy.view(-1, Cc), x.view(-1, Cc), N, H * W)
             K.sigmoid_grad_mul_(s2, ds2)
-            ds1, dWe, dbe = K.fc_bwd(ds2, we2, s1, 1)
-            dpool, dWr, dbr = K.fc_bwd(ds1, wr2, pool, 0)
+            wg = _wgrad(tape)
+            ds1, dWe, dbe = K.fc_bwd(ds2, we2, s1, 1, need_dw=wg)
+            dpool, dWr, dbr = K.fc_bwd(ds1, wr2, pool, 0, need_dw=wg)
             tape.add_grad(x, K.se_scale_bwd(dy, s2, dpool))
+            if not wg:
+                return
             tape.add_param_grad(w_e, dWe)
             tape.add_param_grad(b_e, dbe)
             tape.add_param_grad(w_r, dWr)
@@ -860,10 +918,51 @@ def bilinear(tape, x, Ho, Wo):
     return y
 
 
+def planes_to_pix(tape, x):
+    """[N,C,H,W] planes -> pixel-major [N,H,W,C] (the attention's resized input image, model/unidefense.py:130-131)."""
+    y = K.planes_to_pix(x)
+    if _needs(tape):
+        def bwd():
+            dy = tape.pop_grad(y)
+            if dy is not None:
+                tape.add_grad(x, K.pix_to_planes(dy.contiguous()))
+        tape.record(bwd)
+    return y
+
+
+def absdiff(tape, a, b):
+    """|a - b| with a gradient to b only (a carries none): -sign(a - b) g, sign(0) = 0 as in torch.abs."""
+    y = K.absdiff(a, b)
+    if _needs(tape):
+        def bwd():
+            dy = tape.pop_grad(y)
+            if dy is not None:
+                tape.add_grad(b, K.absdiff_bwd(a, b, dy.contiguous()))
+        tape.record(bwd)
+    return y
+
+
+def attention_diffs(tape, pred_planes, x, h, w, norm):
+    """The dynamic filters' difference inputs (model/unidefense.py:130-150; :326-361, :521-554 for the ResNet models):
+    pred and x bilinearly resized to the h x w attention map, freq_diff = |rfft2(pred) - rfft2(x)| [N,h,w/2+1,6] and
+    spat_diff = |pred - x| [N,h,w,3].  pred (the reconstruction) is read detached, as in the reference.  When x is the tape's
+    tracked input the x side is recorded (bilinear, layout, rfft2, |.| nodes) and the third value is True: the dynamic filters
+    then hand back d(diff).  Otherwise the same kernels run untaped."""
+    pred = K.planes_to_pix(K.bilinear_fwd(pred_planes, h, w))       # [N,h,w,3]
+    sf, _ = _fft_scales(h, norm)
+    if not _tracks(tape, x):
+        xs = K.planes_to_pix(K.bilinear_fwd(x, h, w))
+        return K.absdiff(K.rfft2(pred, sf), K.rfft2(xs, sf)), K.absdiff(pred, xs), False
+    xs = planes_to_pix(tape, bilinear(tape, x, h, w))
+    freq_diff = absdiff(tape, K.rfft2(pred, sf), rfft2_cat(tape, xs, norm))
+    return freq_diff, absdiff(tape, pred, xs), True
+
+
 def rec_losses(tape, rec, x, norm):
     """spatial = mean|rec - x| ; freq = mean(|Re D| + |Im D|), D = rfft2(rec) - rfft2(x) = rfft2(rec - x)
     (model/unidefense.py:245-253), per sample.  rec, x: planes [N,3,S,S].
-    `rec` itself is also a model output, so its external gradient is added in the same backward."""
+    `rec` itself is also a model output, so its external gradient is added in the same backward.  x takes the negative
+    of the losses' gradient to rec when it is the tape's tracked input."""
     N, Cc, S, _ = rec.shape
     assert norm == "ortho", "frequency reconstruction loss implemented for freq_norm='ortho'"
     cnt_s = Cc * S * S
@@ -886,6 +985,8 @@ def rec_losses(tape, rec, x, norm):
                 total = K.dft_rfft2_planes_adjoint(dY, S).view(rec.shape)
             if gs is not None:
                 total = K.l1_bwd(rec, x, gs, 1.0 / cnt_s, out=total)
+            if total is not None and _tracks(tape, x):
+                tape.add_grad(x, K.axpby(total, -1.0))        # d/dx of |rec - x| and of rfft2(rec - x): the negative
             if grec is not None:
                 total = grec if total is None else K.axpby(total, 1.0, grec, 1.0)
             tape.grads[id(rec)] = total      # hand the summed gradient to rec's producer
@@ -894,10 +995,11 @@ def rec_losses(tape, rec, x, norm):
     return spatial, freq
 
 
-def dynamic_filter(tape, x, proj, diff, w2, b2=None):
+def dynamic_filter(tape, x, proj, diff, w2, b2=None, diff_grad=False):
     """mask = sigmoid(conv1x1([mean_c proj, max_c proj, diff]) (+ b2)), out = mask * x
-    (model/modules.py:94-104, 123-133).  x, proj: [N,h,w,*]; diff: [N,h,w,D] (no grad); w2: [1,2+D,1,1]; b2: [1] — the bias of
-    the bias=True variant rides as the weight of one more, constant-1 difference channel (the kernels take any D)."""
+    (model/modules.py:94-104, 123-133).  x, proj: [N,h,w,*]; diff: [N,h,w,D]; w2: [1,2+D,1,1]; b2: [1] — the bias of
+    the bias=True variant rides as the weight of one more, constant-1 difference channel (the kernels take any D).
+    diff_grad: diff depends on the tracked input image and takes d(diff) = dlogit (x) w2[2:2+D]; otherwise no gradient."""
     Cx, Cp, D = x.shape[-1], proj.shape[-1], diff.shape[-1]
     x2, p2, d2 = x.view(-1, Cx), proj.view(-1, Cp), diff.view(-1, D)
     w2f = w2.view(-1)
@@ -919,6 +1021,10 @@ def dynamic_filter(tape, x, proj, diff, w2, b2=None):
                                                 x2, mask, argmax, w2f, Cp)
             tape.add_grad(x, dx.view(x.shape))
             tape.add_grad(proj, dproj.view(proj.shape))
+            if diff_grad:
+                tape.add_grad(diff, K.outer(dlogit, w2f[2:2 + D]).view(diff.shape))
+            if not _wgrad(tape):
+                return
             # dw2[j] = sum_m dlogit[m] * pre[m][j]   (8 or 5 numbers)
             g = K.gemm_tn(dlogit.view(-1, 1), pre)                 # [1, 2 + D (+ 1)]
             if b2 is None:
@@ -933,17 +1039,19 @@ def dynamic_filter(tape, x, proj, diff, w2, b2=None):
 # ---------------------------------------------------------------------------------------------
 # ResNet-variant operators
 # ---------------------------------------------------------------------------------------------
-def conv_dense_any(tape, x, w, stride, pad, need_dx=True):
+def conv_dense_any(tape, x, w, stride, pad, need_dx=True, x_planes=None):
     """Dense k x k F.conv2d with symmetric padding and any stride (ResNet convs, model/resnet/exp.py:95-111;
     7x7/2 stem :395; 1x1/2 downsample :235-246).  The data gradient is the transposed-conv gather
-    (t = ih + pad - kh, oh = t / stride) with the un-flipped weights."""
+    (t = ih + pad - kh, oh = t / stride) with the un-flipped weights.  x_planes: as in conv_dense (the stem)."""
     N, Hin, Win, Ci = x.shape
     Co, _, KH, KW = w.shape
     Hout = (Hin + 2 * pad - KH) // stride + 1
     Wout = (Win + 2 * pad - KW) // stride + 1
     g = K.conv_geom(N, Hin, Win, Ci, Hout, Wout, KH, KW, stride, pad, pad, 0)
     wmat = K.weight_layout(w, 0)
+    stem_dx = _tracks(tape, x_planes)
     if K.conv_im2col_ok(g, Co, x):
+        assert not stem_dx
         return _conv_im2col(tape, x, w, wmat, g, need_dx)
     y = K.conv_gather_nt(x, wmat, g)
     if _needs(tape):
@@ -956,8 +1064,11 @@ def conv_dense_any(tape, x, w, stride, pad, need_dx=True):
             if need_dx:
                 gd = K.conv_geom(N, Hout, Wout, Co, Hin, Win, KH, KW, stride, pad, pad, 1)
                 tape.add_grad(x, K.conv_gather_nt(dy, wd, gd))
-            dw = K.conv_gather_wgrad(dy.view(-1, Co), x, g)
-            tape.add_param_grad(w, dw.view(Co, KH, KW, Ci).permute(0, 3, 1, 2).contiguous())
+            elif stem_dx:
+                _stem_dgrad(tape, dy, w, g, x_planes)
+            if _wgrad(tape):
+                dw = K.conv_gather_wgrad(dy.view(-1, Co), x, g)
+                tape.add_param_grad(w, dw.view(Co, KH, KW, Ci).permute(0, 3, 1, 2).contiguous())
         tape.record(bwd)
     return y
 
@@ -1105,10 +1216,11 @@ def cast(tape, x, dtype):
     return y
 
 
-def stem_fused(tape, x_pix, w, bn_mod, stride, pad_t, pad_l, Ho, Wo, dp, storage=torch.float32):
+def stem_fused(tape, x_pix, w, bn_mod, stride, pad_t, pad_l, Ho, Wo, dp, storage=torch.float32, x_planes=None):
     """Stem conv (model/efficientnet/model.py:185-186) whose BatchNorm + swish is left to block 0's depthwise conv.
-    storage: dtype the trunk keeps its activations in (torch.float16: the raw conv output is handed on rounded)."""
-    h32 = conv_dense(tape, x_pix, w, stride, pad_t, pad_l, Ho, Wo, need_dx=False)
+    storage: dtype the trunk keeps its activations in (torch.float16: the raw conv output is handed on rounded).
+    x_planes: the input image as planes (its gradient is formed when it is the tape's tracked input; conv_dense)."""
+    h32 = conv_dense(tape, x_pix, w, stride, pad_t, pad_l, Ho, Wo, need_dx=False, x_planes=x_planes)
     h = h32 if storage == torch.float32 else h32.to(storage)
     Cc = h.shape[-1]
     M = h.numel() // Cc
