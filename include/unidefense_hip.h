@@ -447,6 +447,31 @@ int ud_stem_dgrad(const ud_conv_geom* g, const float* dy, const float* w, float*
 int ud_absdiff_bwd(const float* a, const float* b, const float* g, float* da, float* db, long total, ud_stream_t stream);
 int ud_outer(const float* u, const float* v, float* out, long M, int D, ud_stream_t stream);
 
+/* ---- iterated input-gradient attacks (csrc/attack.hip; unidefense_amd/attack.py: AttackRunner) ---------------------
+ * All fp32 tensors are contiguous planes [N][3][H][W]: per = 3 H W elements per sample, total = N per; neither needs to be
+ * a multiple of 4.  No atomics and no data-dependent partition: the results are a function of shapes and inputs only.
+ * UD_EINVAL: a NULL tensor, total <= 0 / N < 1 / per < 1, eps < 0, lo > hi, a scratch buffer that is too small.
+ * ud_attack_step_linf  : in place  x_adv <- clamp(clamp(x_adv + step sign(g), x0 - eps, x0 + eps), lo, hi), evaluated in
+ *                        that order with one fp32 rounding per operation (bitwise what the same torch fp32 expression
+ *                        gives); sign(0) = 0; a NaN in g becomes a NaN in x_adv at that element; step may be negative.
+ * ud_sample_sumsq      : out[n] = sum_i (a[n][i] - b[n][i])^2 as double, difference, square and sum formed in double
+ *                        (b NULL: the plain sum of squares).  per is cut into fixed 4096-element parts; with more than one
+ *                        part the partial sums go to ws (ud_sample_sumsq_ws_bytes(N, per) bytes, 0 for one part; ws_bytes
+ *                        is what the caller holds) and a second launch adds them in index order.
+ * ud_attack_step_l2    : in place  x_adv[n] += step g[n] / max(sqrt(gss[n]), 1e-12)   (gss[n] = |g[n]|^2, double)
+ * ud_attack_project_l2 : in place, with d = x_adv - x0 and dss[n] = |d[n]|^2 (double):
+ *                        x_adv[n] <- clamp(x0[n] + d[n] min(1, eps / max(sqrt(dss[n]), 1e-12)), lo, hi); a factor of
+ *                        exactly 1 leaves x_adv[n] as it is before the clamp.  Both L2 kernels form the factor and the
+ *                        new value in double and round once to fp32. */
+int ud_attack_step_linf(float* x_adv, const float* x0, const float* g, long total, float step, float eps, float lo, float hi,
+                        ud_stream_t stream);
+long ud_sample_sumsq_ws_bytes(int N, long per);
+int ud_sample_sumsq(const float* a, const float* b, int N, long per, double* out, double* ws, long ws_bytes,
+                    ud_stream_t stream);
+int ud_attack_step_l2(float* x_adv, const float* g, const double* gss, int N, long per, float step, ud_stream_t stream);
+int ud_attack_project_l2(float* x_adv, const float* x0, const double* dss, int N, long per, float eps, float lo, float hi,
+                         ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

@@ -239,6 +239,56 @@ class TrainEngine(AbstractEngine):
                     ret["EER"], ret["ACER"], ret["TPR5%"], ret["AUC"], ret["ACC"]))
         return ret
 
+    def _metrics(self, scores, labels, tag):
+        """what test() returns for gathered (scores, labels), its line printed as `tag`"""
+        from .metrics import cal_metrics
+        sc, lb = scores.float().cpu().numpy(), labels.cpu().numpy()
+        ret = {"scores": scores.cpu(), "labels": labels.cpu(), "acc": float(((sc < 0.5).astype(int) == lb).mean())}
+        if len(set(lb.tolist())) == 2:
+            ret.update(cal_metrics(lb, sc, threshold=0.5))
+            if self.local_rank == 0:
+                print("%s | EER %.4f, HTER %.4f, TPR 5%% %.4f, AUC %.4f, ACC %.4f" % (
+                    tag, ret["EER"], ret["ACER"], ret["TPR5%"], ret["AUC"], ret["ACC"]))
+        return ret
+
+    def test_robust(self, batches=4, attack=None):
+        """test() on clean and on attacked inputs: every test batch is scored as _score does, attacked with the true labels by
+        the model's AttackRunner (unidefense_amd/attack.py) and scored again the same way.  attack (default
+        config['config']['attack']): the runner's keyword arguments, e.g. {"norm": "linf", "eps": 4/255, "steps": 10} — eps in
+        model-input units (after Normalize(0.5, 0.5) one 8-bit grey level is 2/255).  Returns {"clean": what test() returns,
+        "adv": the same keys on x_adv, "attack": the resolved arguments}.  inference_graph / inference_precision keep their
+        meaning for the two scoring forwards.  Data parallel: each rank attacks its own batches on the un-wrapped model (a
+        frozen pass has no collective of its own) and the scores are gathered over the ranks as in _score."""
+        from .metrics import gather_scores
+        attack = attack if attack is not None else self.config["config"].get("attack")
+        if not attack:
+            raise ValueError("test_robust needs an attack: pass attack={...} or set config['config']['attack']")
+        self._select_gemm_path()
+        self.model.eval()
+        graphed = bool(self.config["config"].get("inference_graph", False))
+        precision = self.config["config"].get("inference_precision", "fp32")
+
+        @torch.no_grad()
+        def score(x):
+            if graphed:
+                out = self.model_without_ddp.inference_runner(x.shape[0], x.shape[-1], precision)(x)
+            else:
+                out = self.model(x)
+            return torch.softmax(out["cls_out"], 1)[:, 0]
+
+        clean, adv, labels, runner = [], [], [], None
+        for step in range(1, batches + 1):
+            xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
+            x, y = torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
+            clean.append(score(x))
+            runner = self.model_without_ddp.attack_runner(x.shape[0], x.shape[-1], **attack)
+            adv.append(score(runner(x, y)))
+            labels.append(y)
+        labels = torch.cat(labels)
+        return {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"),
+                "adv": self._metrics(*gather_scores(torch.cat(adv), labels), "Test(adv)"),
+                "attack": dict(runner.args)}
+
     def validate(self, step, batches=4):
         """The reference's validate (forgery_engine.py:320-421) without the figure / wandb plumbing: metrics over all
         ranks, best-so-far record (AUC + ACC), best_model.bin / latest_model.bin on rank 0."""

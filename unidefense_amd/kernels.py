@@ -1446,6 +1446,70 @@ def outer(u, v):
     return out
 
 
+# ---- iterated input-gradient attacks (csrc/attack.hip): every tensor a contiguous fp32 [N, ...] batch of samples -------------
+def _chk_same(*ts):
+    _chk(*ts)
+    if any(t.shape != ts[0].shape for t in ts):
+        raise ValueError(f"shapes differ: {[tuple(t.shape) for t in ts]}")
+
+
+def _chk_f64(t, n):
+    if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() >= n):
+        raise ValueError(f"expected a contiguous float64 CUDA tensor of at least {n} values, got {t.dtype} {t.device} "
+                         f"shape={tuple(t.shape)}")
+
+
+def attack_step_linf(x_adv, x0, g, step, eps, lo, hi):
+    """In place: x_adv <- clamp(clamp(x_adv + step sign(g), x0 - eps, x0 + eps), lo, hi), bitwise the torch fp32
+    expression; sign(0) = 0, a NaN in g becomes a NaN in x_adv."""
+    _chk_same(x_adv, x0, g)
+    _call("ud_attack_step_linf", _p(x_adv), _p(x0), _p(g), x_adv.numel(), float(step), float(eps), float(lo), float(hi),
+          _stream())
+    return x_adv
+
+
+def sample_sumsq_ws_bytes(N, per):
+    return _call("ud_sample_sumsq_ws_bytes", int(N), int(per))
+
+
+def sample_sumsq(a, b=None, out=None, ws=None):
+    """out[n] = sum over sample n of (a - b)^2 in double (b None: of a^2), deterministic.  out [N] float64 and ws (a float64
+    scratch of sample_sumsq_ws_bytes(N, per) bytes) are allocated unless given (a graph-captured caller gives its own)."""
+    _chk_same(*((a,) if b is None else (a, b)))
+    N = a.shape[0]
+    per = a.numel() // N
+    need = sample_sumsq_ws_bytes(N, per)
+    if out is None:
+        out = torch.empty(N, dtype=torch.float64, device=a.device)
+    _chk_f64(out, N)
+    if ws is None and need:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=a.device)
+    if need:
+        _chk_f64(ws, need // 8)
+    _call("ud_sample_sumsq", _p(a), _p(b), N, per, _p(out), _p(ws) if need else None, ws.numel() * 8 if need else 0, _stream())
+    return out
+
+
+def attack_step_l2(x_adv, g, gss, step):
+    """In place: x_adv[n] += step g[n] / max(sqrt(gss[n]), 1e-12), gss [N] float64 (sample_sumsq(g))."""
+    _chk_same(x_adv, g)
+    N = x_adv.shape[0]
+    _chk_f64(gss, N)
+    _call("ud_attack_step_l2", _p(x_adv), _p(g), _p(gss), N, x_adv.numel() // N, float(step), _stream())
+    return x_adv
+
+
+def attack_project_l2(x_adv, x0, dss, eps, lo, hi):
+    """In place: x_adv[n] <- clamp(x0[n] + d[n] min(1, eps / max(sqrt(dss[n]), 1e-12)), lo, hi), d = x_adv - x0,
+    dss [N] float64 (sample_sumsq(x_adv, x0))."""
+    _chk_same(x_adv, x0)
+    N = x_adv.shape[0]
+    _chk_f64(dss, N)
+    _call("ud_attack_project_l2", _p(x_adv), _p(x0), _p(dss), N, x_adv.numel() // N, float(eps), float(lo), float(hi),
+          _stream())
+    return x_adv
+
+
 def conv_gather_wgrad(a, x, g):
     """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)]."""
     _chk(a, x)

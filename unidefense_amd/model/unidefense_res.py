@@ -154,6 +154,18 @@ class UniDefenseModelRes18(nn.Module):
         from ..infer import inference_runner
         return inference_runner(self, batch, size, precision)
 
+    def input_grad_runner(self, batch, size, objective="cross_entropy"):
+        """The graph-replayed gradient of objective(model(x), y) with respect to x for [batch, 3, size, size] inputs
+        (unidefense_amd/attack.py: InputGradRunner), cached per argument tuple."""
+        from ..attack import input_grad_runner
+        return input_grad_runner(self, batch, size, objective)
+
+    def attack_runner(self, batch, size, **kwargs):
+        """The graph-replayed FGSM / PGD attack for [batch, 3, size, size] inputs (unidefense_amd/attack.py: AttackRunner;
+        kwargs: norm, eps, steps, step, random_start, targeted, clip, objective), cached per argument tuple."""
+        from ..attack import attack_runner
+        return attack_runner(self, batch, size, **kwargs)
+
     # ---------------------------------------------------------------------------------------
     def _conv(self, tape, x, conv, stride):
         if isinstance(conv, _SFConv2dParams):
