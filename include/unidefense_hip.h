@@ -76,7 +76,7 @@ typedef struct {
     /* Tile of the BF16-pipe kernel: 0 = chosen by the library's cost model; 1..4 = 128x128, 128x64, 64x128, 64x64 —
      * for callers that tune per shape by measurement (unidefense_amd/kernels.py does, on the thin expand / project
      * GEMMs whose few tiles leave the k-loop latency exposed).
-     * bit 8 (0x100): each XCD takes a contiguous range of the tile order (measured neutral; off in the shipped plans). */
+     * bit 8: reserved, ignored. */
     int tile_cfg;
     long slice_stride;       /* out_mode 3: elements between the splits' slices (>= M * ldc) */
 } ud_gemm_desc;
@@ -131,7 +131,7 @@ int ud_gemm_query_path(const ud_gemm_desc* d);
  * (a_mode, b_mode): prec 3 any; prec 2 (0,0) (0,1) (1,1).  K % 32 == 0.  *_npanel: panels reachable from the pointer (mode 1 clamps
  * its tile to them).  out_mode / split_k / slice_stride / stat_sum / stat_sumsq as in ud_gemm_desc (statistics: out_mode 0,
  * split_k 1; one slot array [N] while M <= 64 * 128, else 64 slots).
- * tile_cfg bit 8: each XCD takes a contiguous range of the tile order; bit 9 (0x200): XCD-aware grouped raster — XCD x takes a
+ * tile_cfg bit 8: reserved, ignored; bit 9 (0x200): XCD-aware grouped raster — XCD x takes a
  * contiguous range of an order that walks groups of GM = bits 12-15 (0: 4) tile rows column by column, so the workgroups of one L2
  * share GM A panels and 32 / GM B panels; bit 11 (0x800): stream-K — one workgroup per CU, the
  * (tile, K-tile) units dealt evenly; out_mode 0 (C zeroed by the caller: whole-tile segments store, partial ones add
@@ -237,20 +237,6 @@ int ud_norm_apply_fwd(const float* x, int G, int R, int C, const float* mean, co
 int ud_norm_bwd(const float* x, const float* dy, int G, int R, int C, const float* mean, const float* invstd,
                 const float* gamma, const float* beta, int act, double* ws, float* s1, float* s2, float* dgamma,
                 float* dbeta, float* dx, ud_stream_t stream);
-/* One-launch forms of the two above (csrc/norm.hip, round 6): statistics + apply / sums + apply in ONE kernel — the P workgroups
- * sharing a (group, column group) publish their fp64 partials with returning agent-scope atomic exchanges, meet at a counter and
- * fold the partials in a fixed order (deterministic; no fence, no L2 write-back), then apply out of L2.  For the launch-bound
- * InstanceNorms of the decoder (model/unidefense.py:59-102) and the ResNet variants' BatchNorms (model/resnet/exp.py:79-232).
- * slots: ud_norm_fused_ws_doubles doubles (contents arbitrary); counters: ud_norm_fused_counters ZERO 32-bit words.
- * ud_norm_bwd_fused: G > 1 needs s1 / s2 [G][C] (one extra launch sums them into dgamma / dbeta); dx may be NULL. */
-long ud_norm_fused_ws_doubles(int G, int R, int C);
-int ud_norm_fused_counters(int G, int R, int C);
-int ud_norm_fwd_fused(const float* x, int G, int R, int C, const float* gamma, const float* beta, int act, float eps,
-                      double* slots, uint32_t* counters, float* mean, float* invstd, float momentum, float* running_mean,
-                      float* running_var, float* y, ud_stream_t stream);
-int ud_norm_bwd_fused(const float* x, const float* dy, int G, int R, int C, const float* mean, const float* invstd,
-                      const float* gamma, const float* beta, int act, double* slots, uint32_t* counters, float* s1,
-                      float* s2, float* dgamma, float* dbeta, float* dx, ud_stream_t stream);
 /* the elementwise half of ud_norm_bwd with caller-provided sums (already all-reduced over the ranks) and
  * inv_count = 1 / (rows of all ranks): SyncBatchNorm backward (engine/forgery_engine.py:142) */
 int ud_norm_bwd_apply(const float* x, const float* dy, int G, int R, int C, const float* mean,
@@ -831,12 +817,11 @@ int ud_rfft2_ex_plane_half(const void* x, uint16_t* plane, long panel_stride, fl
  * [N][S][S][C], x the conv's raw input and bn the BatchNorm in front of it:
  *   dz = (gate * conv_flipped(dd) + da_f) * act'(bn(x));  s1 += sum dz, s2 += sum dz * xhat;  s3 (optional) += sum dz^2, rounded
  *   up (the energy bound ud_normbwd_apply_planes takes);
- *   wpart[n][K*K][C] = sum_pixels act(bn(x))(window) * dd   of image n  (ud_dwtile_wgrad_finalize sums the N rows) — or, wacc
- *   given (C * K*K floats, zeroed): wacc[c][tap] += gate * that sum by fp32 atomics, no fold launch (N adds per address).
+ *   wpart[n][K*K][C] = sum_pixels act(bn(x))(window) * dd   of image n  (ud_dwtile_wgrad_finalize sums the N rows).
  * Replaces ud_irfft2 + the depthwise weight-gradient kernel + its finalize + the depthwise data-gradient kernel. */
 int ud_irfft2_dwbwd(const void* Y, int N, int S, int C, float scale, float w_interior, const void* dd, const void* x,
                     const ud_bn_ref* bn, const float* wt, int K, const float* gate_alpha, int gate_mode, void* dz, double* s1,
-                    double* s2, double* s3, float* wpart, float* wacc, int f16, ud_stream_t stream);
+                    double* s2, double* s3, float* wpart, int f16, ud_stream_t stream);
 
 /* ---- large real 2-D FFT of image planes (csrc/fft_large.hip), S in {128, 256, 320} ------------------------------------
  * torch.fft.rfft2 on [N,3,S,S] images: the frequency reconstruction loss (model/unidefense.py:246-253; ResNet variants

@@ -343,42 +343,6 @@ def test_perturbed_training_forward_leaves_x_grad_none():
     assert m.classifier.fc.weight.grad is not None
 
 
-def test_side_branch_refuses_tracked_input_before_any_state_changes():
-    """cfg.side_branch = 1 does not form x.grad on UDEB4: a training forward with x requiring grad raises a clear error before
-    anything runs — no BatchNorm running statistic or num_batches_tracked moves, and the next forward counts once."""
-    from unidefense_amd.config import override
-    dev = _dev()
-    n = 2
-    m = _udeb4(dev).train()
-    x = param_fill.make_input(n, 256, 71).to(dev)
-    before = {k: v.clone() for k, v in m.state_dict().items() if "running" in k or "num_batches" in k}
-    with override(side_branch=True), pytest.raises(RuntimeError, match="side_branch"):
-        m(x.clone().requires_grad_(), rng=ou.make_rng(n, 72, 0.5))
-    torch.cuda.synchronize()
-    after = m.state_dict()
-    assert all(torch.equal(v, after[k]) for k, v in before.items())
-    assert not m.__dict__.get("_nbt_pending")
-    m(x, rng=ou.make_rng(n, 72, 0.5))
-    assert int(m.backbone._bn0.num_batches_tracked) == int(before["backbone._bn0.num_batches_tracked"]) + 1
-
-
-def test_resnet_input_grad_unaffected_by_side_branch_switch():
-    """The ResNet models have no side branch: with cfg.side_branch = 1 they form x.grad as with the switch off."""
-    from unidefense_amd.config import override
-    dev = _dev()
-    n = 2
-    m = _resnet("UDR18", dev).eval()
-    x = param_fill.make_input(n, 128, 73).to(dev)
-    res = []
-    for on in (False, True):
-        xg = x.clone().requires_grad_()
-        with override(side_branch=on):
-            _smooth(m(xg)).backward()
-        torch.cuda.synchronize()
-        res.append(xg.grad)
-    assert torch.equal(res[0], res[1])
-
-
 def test_frozen_input_grad_under_data_parallel():
     """HipDataParallel in a world of one rank with cfg.force_collectives (the gradient reducer on the model): a frozen x.grad
     pass before and after training backwards leaves the reducer and its learned use counts alone — it gives the plain frozen

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of one module-level knob (tools/run_with.py) inside ONE gpurun call: tools/gpu_ab_knob.sh kernels._NORM_FUSED False True [bench args]
+# A/B of one module-level knob (tools/run_with.py) inside ONE call on the GPU box: tools/gpu_ab_knob.sh kernels._P3_PAIR True False [bench args]
 # three rounds each, interleaved; prints img/s and ms per step of the bench line
 knob=$1; a=$2; b=$3; shift 3
 mkdir -p gpurun_out/ab_knob

@@ -235,13 +235,6 @@ def main():
             if trial(f"32 x 32 transforms: auto -> {'one lane per row' if mode == 1 else 'lane pairs'}",
                      lambda: _lib.call("ud_fft32_set_wave", mode), lambda: _lib.call("ud_fft32_set_wave", 0), state):
                 kept.append(("ud_fft32_set_wave", mode, True))
-        for name, vals in (("_P3_PAIR_ORDER", (0, 1)), ("_RESIDUAL_PLANES", (False,)), ("_NORMBWD_PLANES", (False,)), ("_RFFT_DW", (False,)),
-                           ("_WGRAD_FOLD_DEFER", (False,))):
-            v0 = getattr(K, name)
-            for v in vals:
-                if trial(f"kernels.{name}: {v0} -> {v}", lambda: setattr(K, name, v), lambda: setattr(K, name, v0), state):
-                    kept.append(("kernels." + name, v, True))
-                    v0 = v
         final = min(measure(), measure())
         print(f"# step {final:.3f} ms; kept: {kept}", flush=True)
         sys.stdout.flush()

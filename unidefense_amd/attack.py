@@ -12,8 +12,7 @@ AttackRunner's graph holds ONE iteration — forward on the static leaf x_adv, o
 place by csrc/attack.hip (L-infinity: one launch; L2: norm, step, norm, projection) — and a call replays it `steps` times.
 
 fp32 only: the half-storage eval forward (InferenceRunner's precision="fp16") has no backward — every backward entry point
-refuses the eval form of ud_bn_ref — so these runners take no precision argument.  UDEB4 with cfg.side_branch = 1 keeps the
-RuntimeError the model raises for a tracked input.
+refuses the eval form of ud_bn_ref — so these runners take no precision argument.
 """
 import contextlib
 

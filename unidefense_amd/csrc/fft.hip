@@ -588,10 +588,9 @@ __global__ __launch_bounds__(NT, 4) void irfft2_dwbwd_kernel(const T* __restrict
                                                          const float* __restrict__ gate_alpha, int gate_mode,
                                                          T* __restrict__ dz, double* __restrict__ s1,
                                                          double* __restrict__ s2, double* __restrict__ s3,
-                                                         float* __restrict__ wpart, float* __restrict__ wacc, int xcd_remap) {
+                                                         float* __restrict__ wpart, int xcd_remap) {
     using L = Lds<S, CB>;
     static_assert(S * CB == NT, "one row-thread per (h, c)");
-    const float gsw = gate_factor_f(gate_alpha, gate_mode);
     constexpr int P = (K - 1) / 2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Lre = lds;
@@ -749,12 +748,7 @@ __global__ __launch_bounds__(NT, 4) void irfft2_dwbwd_kernel(const T* __restrict
         float sum = 0.f;
 #pragma unroll
         for (int r = 0; r < S; ++r) sum += F[(r * K * K + tap) * CB + cc];
-        if (cgroup * CB + cc < C) {
-            // wacc: fp32 atomics straight onto the parameter-layout gradient [C][K*K] (zeroed by the caller; N adds per address,
-            // the gate applied here) instead of a partial row + the fold launch — the default; cfg.deterministic keeps the fold
-            if (wacc) atomicAdd(wacc + (long)(cgroup * CB + cc) * K * K + tap, sum * gsw);
-            else wpart[((long)n * K * K + tap) * C + cgroup * CB + cc] = sum;
-        }
+        if (cgroup * CB + cc < C) wpart[((long)n * K * K + tap) * C + cgroup * CB + cc] = sum;
     }
     __syncthreads();
     double* red = reinterpret_cast<double*>(lds);
@@ -778,7 +772,7 @@ __global__ __launch_bounds__(NT, 4) void irfft2_dwbwd_kernel(const T* __restrict
 template <typename T, int S, int CB, int K>
 int launch_irfft2_dwbwd(const T* Y, int N, int C, float scale, float w_int, const T* dd, const T* x,
                         const ud_bn_ref& bn, const float* wt, const float* gate_alpha, int gate_mode, T* dz, double* s1,
-                        double* s2, double* s3, float* wpart, float* wacc, hipStream_t s) {
+                        double* s2, double* s3, float* wpart, hipStream_t s) {
     using LB = LdsBwd<S, CB, K>;
     static bool attr_set = false;
     if (LB::BYTES > 65536 && !attr_set) {
@@ -789,7 +783,7 @@ int launch_irfft2_dwbwd(const T* Y, int N, int C, float scale, float w_int, cons
     }
     dim3 grid((unsigned)ud_cdiv(C, CB), (unsigned)N);
     hipLaunchKernelGGL((irfft2_dwbwd_kernel<T, S, CB, K>), grid, dim3(NT), LB::BYTES, s, Y, C, scale, w_int, dd, x, bn, wt,
-                       gate_alpha, gate_mode, dz, s1, s2, s3, wpart, wacc, xcd_remap_on(CB * (int)sizeof(float)));
+                       gate_alpha, gate_mode, dz, s1, s2, s3, wpart, xcd_remap_on(CB * (int)sizeof(float)));
     UD_LAUNCH_CHECK();
     return 0;
 }
@@ -1557,15 +1551,15 @@ int ud_rfft2_ex_plane_half(const void* x, uint16_t* plane, long panel_stride, fl
 
 int ud_irfft2_dwbwd(const void* Y, int N, int S, int C, float scale, float w_interior, const void* dd, const void* x,
                     const ud_bn_ref* bn, const float* wt, int K, const float* gate_alpha, int gate_mode, void* dz, double* s1,
-                    double* s2, double* s3, float* wpart, float* wacc, int f16, ud_stream_t stream) {
+                    double* s2, double* s3, float* wpart, int f16, ud_stream_t stream) {
     if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
-    if (N < 1 || C < 1 || !Y || !dd || !x || !bn || bn->G != 1 || !wt || !dz || !s1 || !s2 || (!wpart && !wacc)) return UD_EINVAL;
+    if (N < 1 || C < 1 || !Y || !dd || !x || !bn || bn->G != 1 || !wt || !dz || !s1 || !s2 || !wpart) return UD_EINVAL;
     if (gate_mode < 0 || gate_mode > 2 || (gate_mode != 0 && !gate_alpha)) return UD_EINVAL;
     hipStream_t st = (hipStream_t)stream;
 #define UD_IDW(SS, CC, KK)                                                                                                       \
     UD_STORAGE_DISPATCH(f16, return (launch_irfft2_dwbwd<T, SS, CC, KK>((const T*)Y, N, C, scale, w_interior, (const T*)dd,     \
                                                                         (const T*)x, *bn, wt, gate_alpha, gate_mode, (T*)dz, s1, \
-                                                                        s2, s3, wpart, wacc, st)))
+                                                                        s2, s3, wpart, st)))
     if (S == 8 && K == 5) UD_IDW(8, 64, 5);
     if (S == 8 && K == 3) UD_IDW(8, 64, 3);
     if (S == 16 && K == 5) UD_IDW(16, 32, 5);

@@ -462,12 +462,7 @@ __device__ __forceinline__ void p3_body(const ud_gemm_p3_desc& d, int tiles_m, i
     };
 
     if constexpr (!SK) {
-        int bt = bx;
-        if (d.tile_cfg & 0x100) {          // each XCD takes a contiguous range of the tile order (see gemm_x3.hip)
-            const int Tn = tiles_m * tiles_n, q = Tn >> 3, r = Tn & 7, x = bt & 7;
-            bt = x * q + (x < r ? x : r) + (bt >> 3);
-        }
-        int tile_m = bt % tiles_m, tile_n = bt / tiles_m;
+        int tile_m = bx % tiles_m, tile_n = bx / tiles_m;
         if (d.tile_cfg & 0x200) {
             // XCD-aware raster: XCD x (= blockIdx % 8, its own L2) takes a CONTIGUOUS range of an order that walks groups of GM
             // tile rows column by column, so the ~32 workgroups it runs at a time cover a GM x (32 / GM) block of tiles — they

@@ -371,14 +371,7 @@ __global__ __launch_bounds__(NTHREADS, (kWavesPerSimd<BM, BN>)) void gemm_x3_ker
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WGN, wn = wave % WGN;
     const int l31 = lane & 31, half = lane >> 5;
-    // Workgroups are dealt round-robin over the 8 XCDs (block b runs on XCD b % 8), each with its own 4 MiB L2.  With
-    // tile_cfg bit 8 every XCD gets one CONTIGUOUS range of the (column-major) tile order instead of every eighth tile, so
-    // that the A / B panels its workgroups share are fetched into ONE L2 (a bijection for any tile count: no padding).
-    int bt = blockIdx.x;
-    if (d.tile_cfg & 0x100) {
-        const int T = tiles_m * tiles_n, q = T >> 3, r = T & 7, x = bt & 7;
-        bt = x * q + (x < r ? x : r) + (bt >> 3);
-    }
+    const int bt = blockIdx.x;
     const int split = blockIdx.y, bz = blockIdx.z;
     const int kt_total = (d.K + BK - 1) / BK;
     const int kt_per = (kt_total + d.split_k - 1) / d.split_k;
@@ -603,7 +596,7 @@ constexpr XCfg kX[NXCFG] = {{128, 128, 1.00}, {128, 64, 1.20}, {64, 128, 1.20}, 
 // tile configuration of a descriptor: d.tile_cfg (1 + index, set by the caller's per-shape tuner) > UD_GEMM_X3_CFG > the
 // cost model over the first three (the 64x64 tile is only ever chosen by measurement)
 int pick_cfg(const ud_gemm_desc& d) {
-    const int want = d.tile_cfg & 0xff;          // bit 8: XCD-contiguous tile order (gemm_x3_kernel)
+    const int want = d.tile_cfg & 0xff;
     if (want >= 1 && want <= NXCFG) return want - 1;
     static const int forced = [] {
         const char* e = getenv("UD_GEMM_X3_CFG");

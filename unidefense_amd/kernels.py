@@ -25,29 +25,10 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-# Two streams (tape.side_branch: the reconstruction decoder beside the trunk): every scratch buffer / zero pool below is
-# shared by the launches of ONE stream in order — a reduction's finalize launch has consumed the scratch before the next
-# reduction on that stream starts — so the pools are keyed by (device, branch) and the branch's launches take their own.
-_BR = 0
-
-
-class branch:
-    def __init__(self, b):
-        self.b = b
-
-    def __enter__(self):
-        global _BR
-        self.prev, _BR = _BR, self.b
-        return self
-
-    def __exit__(self, *exc):
-        global _BR
-        _BR = self.prev
-        return False
-
-
+# Every scratch buffer / zero pool below is keyed by the device and shared by the launches of its ONE stream in order: a
+# reduction's finalize launch has consumed the scratch before the next reduction starts.
 def _key(ref):
-    return (ref.device.index, _BR)
+    return ref.device.index
 
 
 def _p(t):
@@ -89,7 +70,6 @@ def empty(shape, like, dtype=torch.float32):
 # its own.  They are carved instead from a few large zero blocks (one fill per 32 MB); a block is never reused, so
 # every carve is still zero.  reset_zero_pool() at the start of a forward / backward makes a step captured into a
 # hipGraph contain the fills of every block it carves from.
-_ZERO_POOL_ON = True
 _ZERO_BLOCK = 8 << 20            # floats per block (32 MB)
 _ZERO_OWN = 2 << 20              # tensors of at least this many floats get their own torch.zeros
 _ZERO_POOL = {}
@@ -124,7 +104,7 @@ def zeros(shape, like):
     n = 1
     for d in shape:
         n *= int(d)
-    if not _ZERO_POOL_ON or n >= _ZERO_OWN or n == 0:
+    if n >= _ZERO_OWN or n == 0:
         return torch.zeros(shape, dtype=torch.float32, device=like.device)
     key = _key(like)
     st = _ZERO_POOL.get(key)
@@ -178,7 +158,7 @@ def _gemm(A, B, Cout, M, N, K, lda, ldb, ldc, a_mode, b_mode, out_mode=0, split_
     d.lda, d.ldb, d.ldc = lda, ldb, ldc
     d.a_mode, d.b_mode, d.out_mode, d.split_k = a_mode, b_mode, out_mode, split_k
     d.batch, d.strideA, d.strideB, d.strideC = batch, strideA, strideB, strideC
-    d.tile_cfg = cfg | (0x100 if _XCD_CONTIGUOUS else 0)
+    d.tile_cfg = cfg
     slices = None
     if CFG.deterministic and out_mode == 2:
         # Cout holds a term to add to (or is a fresh buffer of split_out): result = [Cout +] the splits' partials in
@@ -200,7 +180,7 @@ def _gemm(A, B, Cout, M, N, K, lda, ldb, ldc, a_mode, b_mode, out_mode=0, split_
         d.g = geom
     fold = None
     if stats is not None:
-        slots = _call("ud_gemm_stats_slots", C.byref(d)) if _GEMM_EPILOGUE_STATS else 0
+        slots = _call("ud_gemm_stats_slots", C.byref(d))
         if slots == 0:
             stats_done = False
         else:
@@ -448,7 +428,6 @@ class _WeightLayoutBatch:
 
 
 _WEIGHT_LAYOUTS = _WeightLayoutBatch()
-_WEIGHT_LAYOUT_BATCH = True          # A/B: tools/run_with.py kernels._WEIGHT_LAYOUT_BATCH=False
 
 
 def weight_layout(w, mode):
@@ -456,10 +435,9 @@ def weight_layout(w, mode):
     flipped = flip(2,3).permute(1,2,3,0); mode 2: [B, KH*KW*A] = permute(1,2,3,0) — from the step's one-launch batch when it
     covers this weight as it is now, else made here (and the weight joins the batch from the next forward on)."""
     A, B, KH, KW = w.shape
-    if _WEIGHT_LAYOUT_BATCH:
-        buf = _WEIGHT_LAYOUTS.get(w, mode)
-        if buf is not None:
-            return buf
+    buf = _WEIGHT_LAYOUTS.get(w, mode)
+    if buf is not None:
+        return buf
     if mode == 0:
         return w.permute(0, 2, 3, 1).reshape(A, KH * KW * B).contiguous()
     if mode == 1:
@@ -482,8 +460,7 @@ def begin_forward(owner=None):
             lay = owner.__dict__["_ud_weight_layouts"] = _WeightLayoutBatch()
         _WEIGHT_LAYOUTS = lay
     _WEIGHT_PLANES.begin()
-    if _WEIGHT_LAYOUT_BATCH:
-        _WEIGHT_LAYOUTS.begin()
+    _WEIGHT_LAYOUTS.begin()
 
 
 def end_forward():
@@ -547,7 +524,7 @@ def _p3_desc(A, B, Cout, M, N, K, a_mode, b_mode, out_mode=0, split_k=1, a_row0=
     d.a_panel, d.a_plane, d.b_panel, d.b_plane = A.panel, A.plane, B.panel, B.plane
     d.ldc = N
     d.a_mode, d.b_mode, d.out_mode, d.split_k = a_mode, b_mode, out_mode, split_k
-    d.tile_cfg = cfg | (0x100 if _XCD_CONTIGUOUS else 0) | (_P3_RASTER if not cfg & 0x800 else 0)
+    d.tile_cfg = cfg | (_P3_RASTER if not cfg & 0x800 else 0)
     assert A.prec == B.prec or max(A.prec, B.prec) <= 2
     d.prec = min(A.prec, B.prec)          # (a prec-1 operand with prec-2 weight planes: the weights' first plane is read)
     d.c_half = 1 if Cout.dtype == torch.float16 else 0
@@ -560,10 +537,6 @@ def _p3_desc(A, B, Cout, M, N, K, a_mode, b_mode, out_mode=0, split_k=1, a_row0=
 
 
 _P3_PAIR = True          # A/B: tools/run_with.py kernels._P3_PAIR=False
-_P3_PAIR_SK = True       # ... also the shapes whose data gradient alone runs stream-K (as plain tiles in the pair: 25.67 -> 25.39 ms)
-
-
-_P3_PAIR_ORDER = 2          # 0: the data gradient's workgroups first, 1: the weight gradient's, 2: by rule (A/B below)
 
 
 def _p3_pair_tn_first(M, N, Kd, pn, pt):
@@ -571,8 +544,6 @@ def _p3_pair_tn_first(M, N, Kd, pn, pt):
     split-K slice well above the data gradient's reduction N, at most one round of workgroups) is the pair's critical path: started
     first, the data gradient's many short tiles fill in around it.  Bench step: data gradient first 25.49 ms, weight gradient
     first everywhere 25.51, this rule 25.34 (thresholds x 0.5 ... x 2 within noise; profiles/r05/p3_pair_ab.txt)."""
-    if _P3_PAIR_ORDER != 2:
-        return _P3_PAIR_ORDER == 1
     sp = int(pt[1]) if pt[0] == "split" else 1
     t1 = -(-N // 128) * -(-Kd // 128) * sp
     return M / sp > 2.0 * N and t1 <= 256
@@ -581,12 +552,12 @@ def _p3_pair_tn_first(M, N, Kd, pn, pt):
 def _p3_pair_ok(pn, pt):
     """can the data gradient and the weight gradient of a 1x1 conv go out as ONE launch of the planes kernel (ud_gemm_p3_pair)?
     Both plans plain or split-K, or a stream-K data gradient (run as plain tiles: the weight gradient's workgroups even out its
-    last round instead); no tail form.  Measured on the bench: pairing only where the two grids together fill
+    last round instead, 25.67 -> 25.39 ms); no tail form.  Measured on the bench: pairing only where the two grids together fill
     fewer rounds of 256 workgroups than apart (540 + 225 tiles: 3 instead of 3 + 1) 25.85 -> 25.69 ms, pairing always 25.61 — the
     second problem's workgroups start wherever the first's last round leaves a CU free, and a launch is saved.  The weight
     gradient keeps the split-K factor tuned for its own launch: x 0.5 / 0.25 and x 1.5 / 2 / 3 all measured slower (25.4 ->
     25.9 / 26.5 and 25.9 / 26.1 / 26.4 ms, profiles/r05/p3_pair_ab.txt)"""
-    return pn[0] in (("plain", "split", "sk") if _P3_PAIR_SK else ("plain", "split")) and pt[0] in ("plain", "split")
+    return pn[0] in ("plain", "split", "sk") and pt[0] in ("plain", "split")
 
 
 def spectral_bwd(ctx, dy2, out=None, dy_absmax=None):
@@ -636,7 +607,7 @@ def _gemm_p3(A, B, Cout, M, N, K, a_mode, b_mode, out_mode=0, split_k=1, stats=N
             Cout._ud_fresh = False
     fold = None
     stats_done = False
-    if stats is not None and _GEMM_EPILOGUE_STATS and out_mode == 0 and split_k == 1:
+    if stats is not None and out_mode == 0 and split_k == 1:
         stats_done = True
         slots = 64 if -(-M // 128) > _P3_STAT_SLOT_TILES else 1          # (gemm_p3.hip's epilogue applies the same rule)
         tgt = stats if slots == 1 else zeros64(2 * slots * N, Cout)
@@ -662,8 +633,6 @@ def _gemm_p3(A, B, Cout, M, N, K, a_mode, b_mode, out_mode=0, split_k=1, stats=N
 
 
 _TAIL_SPLIT = True
-_XCD_CONTIGUOUS = False          # ud_gemm_desc.tile_cfg bit 8: each XCD takes a contiguous range of the tile order
-_GEMM_EPILOGUE_STATS = True
 
 
 def _pd64(t, off_doubles=0):
@@ -971,13 +940,10 @@ def _p2_plans(kind, M, N, K):
     return out or [("plain",)]
 
 
-_TAILP = True          # A/B: tools/run_with.py kernels._TAILP=False
-
-
 def _tailp_plans(M, N, K):
     """the tail PAIR of a forward product (ud_gemm_p3_pair, round 6): (rows of the plain part, split-K of the remaining row tiles)
     candidates — the row tiles beyond whole rounds of the 256 CUs go out in the SAME grid as short split-K workgroups"""
-    if not _TAILP or M < 256 or N < 128 or K < 256:
+    if M < 256 or N < 128 or K < 256:
         return []
     mt, nt = -(-M // 128), -(-N // 128)
     full, tail = divmod(mt * nt, 256)
@@ -1078,7 +1044,7 @@ def spectral_takes_plane_half(M, N, Kd):
 
 def rfft2_plane_half_ok(x):
     """can ud_rfft2_ex_plane_half lay this half-stored transform's result into the spectral GEMM's plane?"""
-    if not (_P1_PLANES and _P1_DIRECT and _RFFT_PLANES and x.dtype == torch.float16 and CFG.spectral_p2 != "off"):
+    if not (x.dtype == torch.float16 and CFG.spectral_p2 != "off"):
         return False
     N, S, _, Cc = x.shape
     return S in (8, 16, 32, 12, 24, 48) and (2 * Cc) % 32 == 0 and not _fft_two_pass("rfft_ex", S, 1)
@@ -1115,16 +1081,15 @@ def planes_from_half(x2):
 # The mixed-precision mode (ud_gemm path 3, BASELINE configs[4]) on the planes kernel: one fp16 plane per operand, one product per
 # tile — 530-770 TFLOP/s on the spectral convs' shapes against 290-530 of gemm_x3_kernel's fp16 form (tools/bench_p3_prec1.py).
 # The half-stored activation becomes a plane by a layout pass (ud_planes_from_half), the weights' planes come from the step's
-# batch (their first plane), half results are stored by the epilogue: plain launches only (no atomics onto half).
-_P1_PLANES = True          # A/B: tools/run_with.py kernels._P1_PLANES=False
-_P1_DIRECT = True          # ... the producers lay half results into the plane themselves (no ud_planes_from_half pass)
-_P1_DW = True              # ... and the transform also computes the stride-1 depthwise conv (as in the fp32 mode)
+# batch (their first plane), half results are stored by the epilogue: plain launches only (no atomics onto half).  Where a
+# producer can, it lays its half result into the plane itself (no ud_planes_from_half pass), and the transform also computes the
+# stride-1 depthwise conv (as in the fp32 mode).
 _P1_MIN = (1024, 128)      # M, min(N, K) from which the layout pass pays (f16 bs 64: (1024, 512) 32.5 ms, (1024, 256) 32.0,
 #                            (1024, 128) 31.9, (4096, 64) 33.2; without the path 35.4 — profiles/r05/f16_p1_planes_ab.txt)
 
 
 def _p1_plans_for(M, N, Kd):
-    if not (_P1_PLANES and CFG.spectral_p2 != "off" and _call("ud_gemm_get_path") == 3 and _p2_shape_ok(M, N, Kd) and
+    if not (CFG.spectral_p2 != "off" and _call("ud_gemm_get_path") == 3 and _p2_shape_ok(M, N, Kd) and
             Kd % 8 == 0 and N % 8 == 0 and M >= _P1_MIN[0] and min(N, Kd) >= _P1_MIN[1]):
         return None
     return {"nt": ("plain",), "nn": ("plain",), "tn": _p2_default_plan("tn", N, Kd, M)}
@@ -1272,7 +1237,6 @@ def _pick_split(tiles, K):
 
 
 _TILE_CFGS = ((128, 128, 1.00), (128, 64, 0.93), (256, 32, 1.10), (32, 256, 1.10), (64, 128, 0.93))
-_X3_TILE_MODEL = False      # A/B: the fp32-kernel tile model (more split-K) is 0.4 % faster
 
 
 _FWD_SPLIT_T = 224      # A/B on the bench: 128/1024 -> 224/512 = -0.6 % step time
@@ -1284,22 +1248,20 @@ _FWD_SPLIT_WGS = 320       # workgroups the split aims at
 def _fwd_split(M, N, K):
     """split-K for a forward / data-gradient GEMM too small to fill the chip (e.g. the 8x8-resolution
     expand/project convs: M = 2048, 80 tiles for 256 CUs)."""
-    t = _tiles(M, N, K)
+    t = _tiles(M, N)
     if t >= _FWD_SPLIT_T or K < _FWD_SPLIT_K:
         return 1
     return max(1, min(K // _FWD_SPLIT_MINK, -(-_FWD_SPLIT_WGS // t)))
 
 
-_X3_CFGS = ((128, 128, 1.00), (128, 64, 1.20), (64, 128, 1.20))          # gemm_x3.hip kX
 _X3_MINDIM = 16                 # gemm.hip's auto rule
 
 
-def _tiles(M, N, K=None):
-    """Tile count of the configuration the library picks for an unsplit launch: gemm_x3.hip's for plain GEMMs whose
-    dimensions all reach the auto rule's minimum (K given), gemm.hip:choose_cfg's otherwise."""
-    x3 = _X3_TILE_MODEL and K is not None and min(M, N, K) >= _X3_MINDIM
+def _tiles(M, N):
+    """Tile count of the configuration gemm.hip:choose_cfg's cost model picks for an unsplit launch (it leads to more split-K than
+    gemm_x3.hip's own tile model and measured 0.4 % faster)."""
     best, best_tiles = None, 1
-    for bm, bn, pen in (_X3_CFGS if x3 else _TILE_CFGS):
+    for bm, bn, pen in _TILE_CFGS:
         t = -(-M // bm) * -(-N // bn)
         cost = -(-t // 256) * bm * bn * pen
         if best is None or cost < best:
@@ -1313,7 +1275,7 @@ def gemm_tn(a, b):
     K, M = a.shape
     N = b.shape[1]
     assert b.shape[0] == K
-    split = _pick_split(_tiles(M, N, K), K)
+    split = _pick_split(_tiles(M, N), K)
     r = _tuned_launch("tn", a, b, None, M, N, K, M, N, 1, 1, False, None,          # fp32 or half operands, fp32 result
                       lambda scr: _gemm(a, b, scr, M, N, K, M, N, N, 1, 1, 2 if split > 1 else 0, split))
     if r is not None:
@@ -1641,58 +1603,6 @@ def norm_bwd(x2, dy, G, R, mean, invstd, gamma, beta, act):
     return dx, dg, db
 
 
-# One-launch normalisation (csrc/norm.hip: norm_fwd_fused / norm_bwd_fused): statistics + apply in ONE kernel whose workgroups
-# exchange their partial sums through agent-scope atomics (no fence).  Built to cut the launch-bound InstanceNorms of the decoder
-# and the ResNet variants' BatchNorms from 3 / 4-5 launches to 1 / 1-2 — correct (tests/test_a_kernels_gpu.py), and measured
-# SLOWER on this part: the exchange is four dependent round trips to the memory side (publish, count, poll, read: ~17 us per
-# kernel) against two ~4.5 us launches — UDEB4 bs 32 25.07 -> 25.51 ms, UDR50 320^2 22.6 -> 25.2 (its 50 MB tensors also want
-# 2000 workgroups, the one-launch form runs <= 768 resident ones), UDR18 4.66 -> 5.00 (profiles/r06/norm_one_launch_ab.txt).
-# OFF; kept as the measured answer to "exchange inside the kernel instead of a launch".  A/B: tools/run_with.py kernels._NORM_FUSED=True
-_NORM_FUSED = False
-_NORM_FUSED_MAX_BYTES = 64 << 20
-
-
-def norm_fused_ok(x2, G, R):
-    Cc = x2.shape[-1]
-    return (_NORM_FUSED and norm_fused_takes(x2, G, R))
-
-
-def norm_fused_takes(x2, G, R):
-    Cc = x2.shape[-1]
-    return (x2.is_cuda and x2.dtype == torch.float32 and Cc % 4 == 0 and Cc >= 4
-            and x2.numel() * 4 <= _NORM_FUSED_MAX_BYTES and G * R == x2.shape[0])
-
-
-def _norm_fused_ws(x2, G, R):
-    Cc = x2.shape[-1]
-    slots = _ws64_t(x2, _call("ud_norm_fused_ws_doubles", G, R, Cc))
-    counters = zeros((_call("ud_norm_fused_counters", G, R, Cc),), x2)          # (zero words: 32-bit counters)
-    return slots, counters
-
-
-def norm_fwd_fused(x2, G, R, gamma, beta, act, eps, momentum=0.0, running_mean=None, running_var=None):
-    """(y, mean[G,C], invstd[G,C]) = ud_norm_stats + ud_norm_apply_fwd in one launch; running statistics moved when given (G = 1)"""
-    _chk(x2, gamma, beta)
-    Cc = x2.shape[-1]
-    mean, invstd, y = empty((G, Cc), x2), empty((G, Cc), x2), torch.empty_like(x2)
-    slots, counters = _norm_fused_ws(x2, G, R)
-    _call("ud_norm_fwd_fused", _p(x2), G, R, Cc, _p(gamma), _p(beta), int(act), eps, _p(slots), _p(counters), _p(mean), _p(invstd),
-          momentum, _p(running_mean), _p(running_var), _p(y), _stream())
-    return y, mean, invstd
-
-
-def norm_bwd_fused(x2, dy, G, R, mean, invstd, gamma, beta, act):
-    """(dx, dgamma[C], dbeta[C]) = ud_norm_bwd in one launch (G > 1: + the group sum of dgamma / dbeta)"""
-    _chk(x2, dy)
-    Cc = x2.shape[-1]
-    s = empty((2, G, Cc), x2)
-    dg, db, dx = empty((Cc,), x2), empty((Cc,), x2), torch.empty_like(x2)
-    slots, counters = _norm_fused_ws(x2, G, R)
-    _call("ud_norm_bwd_fused", _p(x2), _p(dy), G, R, Cc, _p(mean), _p(invstd), _p(gamma), _p(beta), int(act), _p(slots),
-          _p(counters), _p(s[0]), _p(s[1]), _p(dg), _p(db), _p(dx), _stream())
-    return dx, dg, db
-
-
 def group_colsum(x2, G, R, scale):
     _chk(x2)
     Cc = x2.shape[-1]
@@ -1892,14 +1802,11 @@ def _dft_pixel_mats(S, scale, w_interior, inverse, device):
     return m
 
 
-_FFT_GENERIC_PIXEL = True          # A/B: tools/run_with.py kernels._FFT_GENERIC_PIXEL=False (the plane-copy form)
-
-
 def _rfft2_generic(x, scale, w_interior):
     """rfft2 of ud_rfft2's contract for any side (95 = 5 * 19 of the 380 x 380 trunk): two batched GEMMs against DFT matrices on
     the pixel-major tensor itself (_dft_pixel_mats) — no plane copies, no torch kernel"""
     N, S, _, Cc = x.shape
-    if not (_FFT_GENERIC_PIXEL and Cc % 4 == 0):
+    if Cc % 4:
         return _rfft2_generic_planes(x, scale, w_interior)
     Wh = S // 2 + 1
     xs = x if x.dtype == torch.float32 else x.float()
@@ -1917,7 +1824,7 @@ def _irfft2_generic(Y, scale, w_interior):
     """irfft2 of ud_irfft2's contract for any side: x = scale * C2R(f Y), as two batched GEMMs on the pixel-major tensors"""
     N, S, Wh, C2 = Y.shape
     Cc = C2 // 2
-    if not (_FFT_GENERIC_PIXEL and Cc % 4 == 0):
+    if Cc % 4:
         return _irfft2_generic_planes(Y, scale, w_interior)
     Ys = Y if Y.dtype == torch.float32 else Y.float()
     a3, a4 = _dft_pixel_mats(S, scale, w_interior, True, Y.device)
@@ -2648,15 +2555,6 @@ def _fused_ws(ref, G, R, C_, per_group, min_rows=8):
     return _ws64(ref, need)
 
 
-def _ws64_t(ref, need):
-    """the (device, branch) fp64 scratch as a tensor of at least `need` doubles"""
-    ws = _REDUCE_WS.get(_key(ref))
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, _REDUCE_WS_MIN), dtype=torch.float64, device=ref.device)
-        _REDUCE_WS[_key(ref)] = ws
-    return ws
-
-
 def _ws64(ref, need):
     if need <= 0:
         return None
@@ -2743,9 +2641,6 @@ def se_scale_bn(x, bn, s, G, R, want_absmax=False):
     return y
 
 
-_RESIDUAL_PLANES = True          # A/B: tools/run_with.py kernels._RESIDUAL_PLANES=False
-
-
 def residual_bn(x, bn, keep, inv_keep, skip, G, R, update=False, want_absmax=False, planes_for=None):
     """out = bn(x) [* keep / keep_prob] [+ skip].  planes_for = (M, N, w2) of the 1x1 conv that reads `out` next (the following
     block's expand conv): where that conv runs on the planes GEMM, `out` is ALSO written as its fp16 x 2 planes
@@ -2756,7 +2651,7 @@ def residual_bn(x, bn, keep, inv_keep, skip, G, R, update=False, want_absmax=Fal
     amax = amax_slots(x, want_absmax)
     Cc = x.shape[-1]
     skip_amax = getattr(skip, "_ud_absmax", None) if skip is not None else None
-    if (planes_for is not None and _RESIDUAL_PLANES and _RFFT_PLANES and h == 0 and Cc % 4 == 0 and CFG.spectral_p2 != "off"
+    if (planes_for is not None and h == 0 and Cc % 4 == 0 and CFG.spectral_p2 != "off"
             and (skip is None or skip_amax is not None)
             and spectral_takes_planes(planes_for[0], planes_for[1], Cc, planes_for[2], want_stats=True)):
         pl = Planes(G * R, Cc, x, 2, False)
@@ -2781,16 +2676,13 @@ def normbwd_sums(x, dy, keep, inv_keep, bn, dy_is_dz, G, R, sacc):
           _stream())
 
 
-_NORMBWD_PLANES = True          # A/B: tools/run_with.py kernels._NORMBWD_PLANES=False
-
-
 def normbwd_planes_ok(x, ctx):
     """does the BatchNorm backward in front of a 1x1 conv write its result as that conv's GEMM planes itself?  (the conv's
     backward runs on the planes GEMM — ctx.plans — and the tensor has whole channel quads.)  1: fp32 — prec-2 planes, scaled by the
     energy bound (a 3C sum accumulator); 2: half storage — the half result laid into the prec-1 plane as it is; 0: no."""
-    if not (_NORMBWD_PLANES and _RFFT_PLANES and ctx.plans is not None and x.shape[-1] % 4 == 0 and CFG.spectral_p2 != "off"):
+    if not (ctx.plans is not None and x.shape[-1] % 4 == 0 and CFG.spectral_p2 != "off"):
         return 0
-    return 1 if x.dtype == torch.float32 else 2 if (_P1_DIRECT and x.dtype == torch.float16 and x.shape[-1] % 8 == 0) else 0
+    return 1 if x.dtype == torch.float32 else 2 if (x.dtype == torch.float16 and x.shape[-1] % 8 == 0) else 0
 
 
 def normbwd_apply_planes(x, dy, keep, inv_keep, bn, dy_is_dz, G, R, sacc, sacc_local=None):
@@ -3016,25 +2908,19 @@ def rfft2_ex(x, scale, w_interior=1.0, bn=None, want_act=False, gate_alpha=None,
     return (Y, act, ggrad) if gate_acc is not None else (Y, act)
 
 
-_RFFT_PLANES = True          # A/B: tools/run_with.py kernels._RFFT_PLANES=False
-
-
 def rfft2_planes_ok(x, bn, stride_ok=True):
     """can ud_rfft2_ex_planes write this transform's result as the spectral GEMM's planes?  (fp32 storage, the one-kernel
     transform sizes, whole 32-column panels, and a conv shape the planes GEMM takes at all: spectral_takes_planes)"""
-    if not (_RFFT_PLANES and x.dtype == torch.float32 and CFG.spectral_p2 != "off"):
+    if not (x.dtype == torch.float32 and CFG.spectral_p2 != "off"):
         return False
     N, S, _, Cc = x.shape
     return S in (8, 16, 32, 12, 24, 48) and (2 * Cc) % 32 == 0 and not _fft_two_pass("rfft_ex", S, 0)
 
 
-_RFFT_DW = True          # A/B: tools/run_with.py kernels._RFFT_DW=False
-
-
 def rfft2_dw_ok(S, k, stride, pad):
     """can rfft2_ex_planes compute the depthwise conv of the same plane too?  (the 256 x 256 trunk's power-of-two maps, stride 1,
     'same' pads)"""
-    return _RFFT_DW and stride == 1 and S in (8, 16, 32) and k in (3, 5) and tuple(pad) == ((k - 1) // 2,) * 4
+    return stride == 1 and S in (8, 16, 32) and k in (3, 5) and tuple(pad) == ((k - 1) // 2,) * 4
 
 
 def rfft2_ex_planes(x, scale, w_interior=1.0, bn=None, want_act=False, gate_alpha=None, gate_mode=0, update=False,
@@ -3128,14 +3014,13 @@ _DWTILE_PART = {}
 # them all at the end (ud_dwtile_wgrad_finalize_multi).  A gradient that is read before the end — a second use of the parameter,
 # a data-parallel reducer taking it as soon as it is complete — flushes first (Tape.add_param_grad).
 _WGRAD_FOLDS = None
-_WGRAD_FOLD_DEFER = True          # A/B: tools/run_with.py kernels._WGRAD_FOLD_DEFER=False
 
 
 def begin_wgrad_folds():
     global _WGRAD_FOLDS
     if _WGRAD_FOLDS:
         flush_wgrad_folds()          # a backward started inside another one's: the outer tape's pending folds are done first, not dropped
-    _WGRAD_FOLDS = [] if _WGRAD_FOLD_DEFER else None
+    _WGRAD_FOLDS = []
 
 
 def flush_wgrad_folds(end=False):
@@ -3206,20 +3091,13 @@ def dwtile_bwd(dy, x, wt, K, pad_t, pad_l, bn=None, gate_alpha=None, gate_mode=0
     return dz, dwt
 
 
-_IRFFT_DWBWD = True          # A/B: tools/run_with.py kernels._IRFFT_DWBWD=False
 _IRFFT_DWBWD_SIZES = (8, 16)
-_IRFFT_DWBWD_HALF = True          # ... also with half-stored tensors (the mixed-precision mode); A/B: =False
-# weight gradient of ud_irfft2_dwbwd by fp32 atomics onto the parameter-layout gradient instead of partial rows + the fold launch:
-# OFF — 1600 device-scope atomics per workgroup make the 8 x 8 kernel 81-92 us instead of 29 (16 x 16, k 5: 63 vs 52); the step
-# with the 18 fold launches is 25.93 ms against 26.28 (profiles/r05/dwbwd_wgrad_atomics_ab.txt; A/B: tools/run_with.py
-# kernels._IRFFT_DWBWD_ATOMIC=True)
-_IRFFT_DWBWD_ATOMIC = False
 
 
 def irfft2_dwbwd_ok(S, k, stride, pad, dtype):
     """the SF block's spatial-branch backward inside the adjoint transform (csrc/fft.hip: irfft2_dwbwd_kernel): the 8 x 8 maps"""
-    return (_IRFFT_DWBWD and S in _IRFFT_DWBWD_SIZES and k in (3, 5) and stride == 1 and tuple(pad) == ((k - 1) // 2,) * 4
-            and (dtype == torch.float32 or (_IRFFT_DWBWD_HALF and dtype == torch.float16)))
+    return (S in _IRFFT_DWBWD_SIZES and k in (3, 5) and stride == 1 and tuple(pad) == ((k - 1) // 2,) * 4
+            and dtype in (torch.float32, torch.float16))
 
 
 def irfft2_dwbwd(Y, scale, w_interior, dd, x, bn, wt, k, gate_alpha, gate_mode, sacc):
@@ -3233,16 +3111,10 @@ def irfft2_dwbwd(Y, scale, w_interior, dd, x, bn, wt, k, gate_alpha, gate_mode, 
     assert dd.shape == (N, S, S, Cc) and x.shape == dd.shape
     dz = torch.empty_like(dd)
     en = _pd(sacc, 2 * Cc) if sacc.numel() >= 3 * Cc else None          # a 3C accumulator: + sum dz^2 (normbwd_apply_planes' bound)
-    if _IRFFT_DWBWD_ATOMIC and not CFG.deterministic:
-        # the weight gradient by fp32 atomics onto a zeroed [C, k*k] (N adds per address): no partial rows, no fold launch
-        dwt = zeros((Cc, k * k), x)
-        _call("ud_irfft2_dwbwd", _p(Y), N, S, Cc, float(scale), float(w_interior), _p(dd), _p(x), C.byref(bn.ref()), _p(wt), int(k),
-              _p(gate_alpha), int(gate_mode), _p(dz), _pd(sacc), _pd(sacc, Cc), en, None, _p(dwt), h, _stream())
-        return dz, dwt
     part, defer = _wgrad_part(x, N * k * k * Cc)
     dwt = empty((Cc, k * k), x)
     _call("ud_irfft2_dwbwd", _p(Y), N, S, Cc, float(scale), float(w_interior), _p(dd), _p(x), C.byref(bn.ref()), _p(wt), int(k),
-          _p(gate_alpha), int(gate_mode), _p(dz), _pd(sacc), _pd(sacc, Cc), en, _p(part), None, h, _stream())
+          _p(gate_alpha), int(gate_mode), _p(dz), _pd(sacc), _pd(sacc, Cc), en, _p(part), h, _stream())
     if defer:
         _defer_wgrad_fold(part, N, int(k), Cc, gate_alpha, gate_mode, dwt)
     else:

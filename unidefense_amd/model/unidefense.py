@@ -315,11 +315,6 @@ class UniDefenseModelEb4(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("unidefense_amd runs on the GPU only (no CPU path); move the model and input to cuda")
         x = x.contiguous().to(torch.float32)
-        if cfg.side_branch and noise_x is None and x.requires_grad and torch.is_grad_enabled() and \
-                isinstance(self, UniDefenseModelEb4):
-            # refused before anything runs (no BatchNorm statistics moved): the branch's second stream does not form x.grad
-            raise RuntimeError("cfg.side_branch = 1 does not compute gradients with respect to the input image (UDEB4): set "
-                               "cfg.side_branch = 0, or run the forward with an input that does not require grad")
         # a tape is built whenever autograd would record: training, or an eval-mode forward outside no_grad() whose
         # parameters or input require gradients (fine-tuning on frozen BatchNorm statistics; x.grad of a frozen model for an
         # attack or a saliency map; the reference is plain autograd)
@@ -602,21 +597,17 @@ class UniDefenseModelEb4(nn.Module):
         # only draw that drop_rate = 0 / drop_connect_rate = 0 leave, to compare two executions bit for bit)
         if self.training and getattr(self, "_dec_dropout", True):
             d_in = T.dropout_mask(tape, x_b4, self._keep_mask(rng, "dec_keep", x_b4, 0.8), 0.2)
-        # The reconstruction branch (decoder -> rec -> spatial / frequency loss terms, unidefense.py:214-216, 244-253) shares only
-        # its input with the trunk's stage 5: with cfg.side_branch it runs — forward and backward — on a second stream beside
-        # stage 5 (both are latency-bound chains of small kernels); the attention, which reads the reconstruction, joins them.
-        with T.side_branch(tape, x_b4, (d_in, x)) as side:
-            dec1 = self._decoder(tape, d_in, self.dec_block1, False)
-            dec2 = self._decoder(tape, dec1, self.dec_block2, False)
-            dec3_pix = self._decoder(tape, dec2, self.dec_block3, True)
-            dec3 = T.tanh_to_planes(tape, dec3_pix)                          # [N,3,128,128]
-            t1 = T.mean_hw(tape, dec1)
-            t2 = T.mean_hw(tape, dec2)
-            rec = T.bilinear(tape, dec3, H, W)
-            spatial, freq = T.rec_losses(tape, rec, x, self.freq_norm)
+        # the reconstruction branch (decoder -> rec -> spatial / frequency loss terms, unidefense.py:214-216, 244-253)
+        dec1 = self._decoder(tape, d_in, self.dec_block1, False)
+        dec2 = self._decoder(tape, dec1, self.dec_block2, False)
+        dec3_pix = self._decoder(tape, dec2, self.dec_block3, True)
+        dec3 = T.tanh_to_planes(tape, dec3_pix)                          # [N,3,128,128]
+        t1 = T.mean_hw(tape, dec1)
+        t2 = T.mean_hw(tape, dec2)
+        rec = T.bilinear(tape, dec3, H, W)
+        spatial, freq = T.rec_losses(tape, rec, x, self.freq_norm)
 
         x_b5 = T.cast(tape, self._blocks(tape, x_b4h, 5, rng), f32)
-        side.join((dec1, dec2, dec3, t1, t2, rec, spatial, freq))
         att, freq_mask, spat_mask = self._attention(tape, dec3, x, x_b5, rng)
         x_b6 = T.cast(tape, self._blocks(tape, T.cast(tape, att, torch.float16) if st16 else att, 6, rng), f32)
 

@@ -36,12 +36,6 @@ class Tape:
         self.param_seen = {}
         self._deferred = set()   # id(param) whose stored gradient still waits for the one-launch fold (kernels.flush_wgrad_folds)
         self.weight_snapshot = None      # kernels.weight_batch_snapshot() of the forward (checked before the replay)
-        # side branch (cfg.side_branch): nodes recorded inside `side_branch(tape, ...)` — the reconstruction decoder and its loss
-        # tail, independent of the trunk's stage 5 / attention / stage 6 / head — replay on a second stream
-        self.side = None         # torch.cuda.Stream of the branch, or None
-        self.side_nodes = set()  # id(fn) of the closures recorded on it
-        self._in_side = False
-        self._side_param_grads = []
         # gradient with respect to the input image: `input` is the tracked x planes [N,3,H,W] (model(x) with x.requires_grad
         # and no perturbation), its gradient is left in `input_grad` by backward().  wgrad_on = False: no parameter takes a
         # gradient (a frozen eval-mode model), so the operators launch no weight-gradient work
@@ -56,8 +50,6 @@ class Tape:
     # -- recording -------------------------------------------------------------------------
     def record(self, fn):
         self.nodes.append(fn)
-        if self._in_side:
-            self.side_nodes.add(id(fn))
 
     def add_grad(self, t: torch.Tensor, g: torch.Tensor):
         """Accumulate g into the gradient slot of activation t (functional: never mutates g)."""
@@ -89,8 +81,6 @@ class Tape:
         g = g.reshape(p.shape)
         g = g if cur is None else K.axpby(cur, 1.0, g, 1.0)
         self.param_grads[p] = g
-        if self._in_side:
-            self._side_param_grads.append(g)
         if deferred:
             self._deferred.add(id(p))      # stored unfolded: a later contribution to p must flush before it reads `cur`
         n = self.param_seen[id(p)] = self.param_seen.get(id(p), 0) + 1
@@ -102,7 +92,8 @@ class Tape:
         """Run `fn()` (the weight-gradient kernels of parameter p) and record the result.  One queue: a second stream for
         these launches was measured slower in rounds 1, 2 and 4 (46.3 vs 43.6, 36.15 vs 34.70, 29.1 vs 27.2 ms per step: the
         GEMMs own the CU's registers and LDS, nothing co-schedules) and is gone — with it the ordering hazard of operand
-        planes made lazily on whichever stream touched them first."""
+        planes made lazily on whichever stream touched them first.  A second stream for the reconstruction decoder (round 6)
+        was measured slower as well (24.07 vs 24.44 ms, profiles/r06/side_branch_ab.txt) and is gone too."""
         self.add_param_grad(p, fn())
 
     # -- replay ----------------------------------------------------------------------------
@@ -111,11 +102,8 @@ class Tape:
             K.weight_batch_check(self.weight_snapshot)
         K.begin_wgrad_folds()          # the depthwise weight gradients' folds: one launch at the end instead of one per conv
         try:
-            if self.side is None or not self.side_nodes:
-                for fn in reversed(self.nodes):
-                    fn()
-            else:
-                self._backward_two_streams()
+            for fn in reversed(self.nodes):
+                fn()
         finally:
             K.flush_wgrad_folds(end=True)
         if self.input is not None:
@@ -123,47 +111,6 @@ class Tape:
         self.nodes = []
         self.grads = {}
         self._keep = []
-        self.side_nodes = set()
-
-    def _backward_two_streams(self):
-        """The replay with the side branch's closures on its stream.  The recorded order is a valid serial order, so each stream
-        runs its closures in that order; the branch starts (waits for the main stream) at its first closure — everything it
-        reads from outside are the output gradients, set before the replay — and the main stream waits for it before the first
-        closure recorded BEFORE the branch began (the consumer of the branch input's gradient).  Closures of the main stream in
-        between (stage 5 ... head) exchange nothing with the branch: the attention reads the reconstruction detached."""
-        main, side = torch.cuda.current_stream(), self.side
-        side_ids = self.side_nodes
-        first = min(i for i, fn in enumerate(self.nodes) if id(fn) in side_ids)
-        started = joined = False
-        for i in range(len(self.nodes) - 1, -1, -1):
-            fn = self.nodes[i]
-            if id(fn) in side_ids:
-                if not started:
-                    for g in self.grads.values():          # output gradients made on the main stream, read on the branch
-                        g.record_stream(side)
-                    side.wait_stream(main)
-                    started = True
-                with torch.cuda.stream(side), K.branch(1):
-                    self._in_side = True
-                    try:
-                        fn()
-                    finally:
-                        self._in_side = False
-            else:
-                if started and not joined and i < first:
-                    self._join(main, side)
-                    joined = True
-                fn()
-        if started and not joined:
-            self._join(main, side)
-
-    def _join(self, main, side):
-        for g in self.grads.values():                      # the branch input's gradient: made on the branch, read on main
-            g.record_stream(main)
-        for g in self._side_param_grads:
-            g.record_stream(main)
-        self._side_param_grads = []
-        main.wait_stream(side)
 
 
 def _needs(tape):
@@ -176,61 +123,6 @@ def _tracks(tape, t):
 
 def _wgrad(tape):
     return tape.wgrad_on
-
-
-_SIDE_STREAMS = {}
-
-
-class side_branch:
-    """`with side_branch(tape, like, inputs): ...` — the enclosed operators run on a second stream, concurrently with whatever
-    the caller launches on the main stream until `.join(outputs)`; their backward closures replay on that stream too
-    (Tape.backward).  Used for the reconstruction decoder (model/unidefense.py:214-216 of the reference), which shares only its
-    input with the trunk's stage 5: the two are latency-bound chains of small kernels on different tensors.  `inputs`: tensors
-    made on the main stream that the branch reads (their memory must not be recycled under it).  Off (plain serial execution)
-    without a tape, with cfg.side_branch = False, or on a tape that already carries a branch."""
-
-    def __init__(self, tape, like, inputs=()):
-        self.tape = tape
-        self.on = bool(tape is not None and cfg.side_branch and like.is_cuda and tape.side is None)
-        # (UniDefenseModelEb4.forward refuses a tracked input with the branch on before the forward starts)
-        assert not (self.on and tape.input is not None), "side branch with a tracked input image"
-        self.like, self.inputs = like, inputs
-        self.ctx = None
-
-    def __enter__(self):
-        if not self.on:
-            return self
-        dev = self.like.device.index
-        side = _SIDE_STREAMS.get(dev)
-        if side is None:
-            side = _SIDE_STREAMS[dev] = torch.cuda.Stream(device=self.like.device)
-        self.main = torch.cuda.current_stream()
-        for t in self.inputs:
-            t.record_stream(side)
-        side.wait_stream(self.main)
-        self.tape.side = side
-        self.tape._in_side = True
-        self.ctx = (torch.cuda.stream(side), K.branch(1))
-        self.ctx[0].__enter__()
-        self.ctx[1].__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx[1].__exit__(*exc)
-            self.ctx[0].__exit__(*exc)
-            self.tape._in_side = False
-        return False
-
-    def join(self, outputs=()):
-        """the main stream waits for the branch; `outputs`: tensors the branch made that the main stream goes on to read"""
-        if self.ctx is None:
-            return
-        for t in outputs:
-            if t is not None:
-                t.record_stream(self.main)
-        self.main.wait_stream(self.tape.side)
-        self.ctx = None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -417,7 +309,6 @@ def linear(tape, x, w, b):
 # ---------------------------------------------------------------------------------------------
 # depthwise conv, FFT, SFConv
 # ---------------------------------------------------------------------------------------------
-_DW_FUSED_ADD = True
 # Stride-1 depthwise convs of the fused MBConv node on the LDS-tiled kernels of csrc/dwtile.hip (the deferred BatchNorm is
 # applied while the halo tile is staged: swish(bn0(e)) is never materialised) WHERE THEY WIN — measured per shape against
 # the strip kernels with tools/bench_dwtile.py on an MI355X (profiles/r03/dwtile_f32_bs32.txt, dwtile_f16_bs64.txt):
@@ -467,9 +358,6 @@ def _dw_tile_rule(sf, k, stride, H, half):
 
 # Round 5: the stride-1 blocks' depthwise data gradient and weight gradient as ONE kernel (kernels.dwtile_bwd: both halo tiles
 # staged once; the separate kernels read dy and the conv's input twice each).  Where it is used: _dw_bwd_fused_policy.
-_DW_BWD_FUSED = True
-
-
 def _dw_bwd_fused_policy(sf, k, stride, H, half):
     """data + weight gradient of this depthwise conv in one launch (csrc/dwtile.hip: dw_tile_bwd_kernel)?  Measured per shape
     against the pair of kernels _dw_tile_policy picks (tools/bench_dwbwd.py on an MI355X, profiles/r05/dwbwd_*.txt; us, pair ->
@@ -477,7 +365,7 @@ def _dw_bwd_fused_policy(sf, k, stride, H, half):
     NOT the 64^2 k3 blocks (132 vs 134: two halo tiles of a 16 x 8 tile are 1.4x its pixels, twice) and NOT the 8^2 k5 blocks
     (48 vs 60: one workgroup per CU next to the strip kernels' eight).  Half storage bs 64: 328 -> 260, 90 -> 80, 224 -> 211,
     163 -> 156, 73 -> 71; a tie at 16^2 k5 and 8^2 k3, 72 vs 96 at 8^2 k5."""
-    if not _DW_BWD_FUSED or stride != 1:
+    if stride != 1:
         return False
     ov = _DW_BWD_FUSED_OVERRIDE.get((bool(sf), k, stride, H, bool(half)))
     if ov is not None:
@@ -513,7 +401,7 @@ def dwconv(tape, x, w, stride, pad):
                 return
             # x usually has a second consumer whose gradient is already there (SFConv's frequency branch, exp.py:55;
             # the SE pool): the data-gradient kernel adds it in its store instead of a separate axpby pass
-            cur = tape.grads.pop(id(x), None) if _DW_FUSED_ADD else None
+            cur = tape.grads.pop(id(x), None)
             if cur is not None and not (cur.is_contiguous() and cur.shape == x.shape and cur.dtype == torch.float32):
                 tape.grads[id(x)], cur = cur, None
             tape.add_grad(x, K.dwconv_bwd_data(dy, wt, k, stride, pt, pl, H, W, add=cur))
@@ -652,7 +540,7 @@ def batchnorm_act(tape, x, weight, bias, running_mean, running_var, eps, momentu
     affine = weight is not None
     if not affine:
         weight, bias = _const_affine(Cc, x)
-    synced = one = False
+    synced = False
     if training and sync_group is not None:
         import torch.distributed as dist
         synced = dist.get_world_size(sync_group) > 1 or cfg.force_collectives
@@ -668,18 +556,12 @@ def batchnorm_act(tape, x, weight, bias, running_mean, running_var, eps, momentu
         mean, invstd = K.syncbn_combine(gathered, world, Cc, R, eps, momentum, running_mean, running_var)
     elif training:
         world = 1
-        one = K.norm_fused_ok(x2, 1, R)          # statistics + apply in one launch (csrc/norm.hip, norm_fwd_fused)
-        if one:
-            y, mean, invstd = K.norm_fwd_fused(x2, 1, R, weight, bias, act, eps, momentum, running_mean, running_var)
-        else:
-            mean, invstd = K.norm_stats(x2, 1, R, eps, momentum, running_mean, running_var)
+        mean, invstd = K.norm_stats(x2, 1, R, eps, momentum, running_mean, running_var)
     else:
         world = 1
         mean = running_mean.view(1, Cc)
         invstd = torch.rsqrt(running_var + eps).view(1, Cc)
-    if not one:
-        y = K.norm_apply(x2, 1, R, mean, invstd, weight, bias, act)
-    y = y.view(x.shape)
+    y = K.norm_apply(x2, 1, R, mean, invstd, weight, bias, act).view(x.shape)
     if act == 2 and tape is not None and tape.kinks is not None:
         tape.kinks[id(weight)] = y
     if _needs(tape):
@@ -704,7 +586,7 @@ def batchnorm_act(tape, x, weight, bias, running_mean, running_var, eps, momentu
                 dx = K.norm_bwd_apply(x2, dy.view(-1, Cc), 1, R, mean, invstd, weight, bias, s,
                                       1.0 / float(R * world), act)
             else:
-                dx, dg, db = (K.norm_bwd_fused if one else K.norm_bwd)(x2, dy.view(-1, Cc), 1, R, mean, invstd, weight, bias, act)
+                dx, dg, db = K.norm_bwd(x2, dy.view(-1, Cc), 1, R, mean, invstd, weight, bias, act)
             tape.add_grad(x, dx.view(x.shape))
             if affine and dg is not None:
                 tape.add_param_grad(weight, dg)
@@ -756,13 +638,8 @@ def instancenorm_act(tape, x, weight, bias, eps, act):
     affine = weight is not None
     if not affine:
         weight, bias = _const_affine(Cc, x)
-    one = K.norm_fused_ok(x2, N, H * W)          # statistics + apply in one launch (csrc/norm.hip, norm_fwd_fused)
-    if one:
-        y, mean, invstd = K.norm_fwd_fused(x2, N, H * W, weight, bias, act, eps)
-        y = y.view(x.shape)
-    else:
-        mean, invstd = K.norm_stats(x2, N, H * W, eps)
-        y = K.norm_apply(x2, N, H * W, mean, invstd, weight, bias, act).view(x.shape)
+    mean, invstd = K.norm_stats(x2, N, H * W, eps)
+    y = K.norm_apply(x2, N, H * W, mean, invstd, weight, bias, act).view(x.shape)
     if act == 2 and tape is not None and tape.kinks is not None:
         tape.kinks[id(weight)] = y
     if _needs(tape):
@@ -770,7 +647,7 @@ def instancenorm_act(tape, x, weight, bias, eps, act):
             dy = tape.pop_grad(y)
             if dy is None:
                 return
-            dx, dg, db = (K.norm_bwd_fused if one else K.norm_bwd)(x2, dy.view(-1, Cc), N, H * W, mean, invstd, weight, bias, act)
+            dx, dg, db = K.norm_bwd(x2, dy.view(-1, Cc), N, H * W, mean, invstd, weight, bias, act)
             tape.add_grad(x, dx.view(x.shape))
             if affine:
                 tape.add_param_grad(weight, dg)
@@ -1304,7 +1181,7 @@ def mbconv_fused(tape, x, blk, keep, keep_prob, wt, dp, lazy_in=None, next_blk=N
                     xf, a = K.rfft2_ex_planes(src, s_f, 1.0, bn=src_bn, want_act=want_a, update=True)
             elif K.rfft2_plane_half_ok(src) and K.spectral_takes_plane_half(N * S * (S // 2 + 1), 2 * Ce, 2 * Ce):
                 # the mixed-precision mode: the half result laid into the prec-1 plane by the transform (no layout pass)
-                if K._P1_DW and K.rfft2_dw_ok(S, k, stride, sp.pad):
+                if K.rfft2_dw_ok(S, k, stride, sp.pad):
                     xf, a, spat = K.rfft2_ex_plane_half(src, s_f, 1.0, bn=src_bn, want_act=not (t_wg or t_fused or bwd_in_fft),
                                                         update=True, dw_wt=wt, dw_k=k)
                 else:
@@ -1357,7 +1234,7 @@ def mbconv_fused(tape, x, blk, keep, keep_prob, wt, dp, lazy_in=None, next_blk=N
     Wp = blk._project_conv.weight.view(Co, Ce)
     # project conv on the planes GEMM: the gated tensor c is written as its planes by se_scale_bn itself, scaled by
     # max |swish(bn1(d))| — which the SE squeeze pass leaves behind (kernels.colsum_bn_amax)
-    c_pl = (K._RFFT_PLANES and d.dtype == torch.float32 and Ce % 32 == 0 and cfg.spectral_p2 != "off"
+    c_pl = (d.dtype == torch.float32 and Ce % 32 == 0 and cfg.spectral_p2 != "off"
             and K.spectral_takes_planes(Mo, Co, Ce, Wp, want_stats=True))
     if c_pl:
         c_amax = K.colsum_bn_amax(d, bn1, N, HWo, pool, update=True)
@@ -1376,7 +1253,7 @@ def mbconv_fused(tape, x, blk, keep, keep_prob, wt, dp, lazy_in=None, next_blk=N
     elif c_pl:
         c = K.se_scale_bn_planes(d, bn1, s2, N, HWo, c_amax)
         (p, done), pctx = K.spectral_fwd(c, Wp, stats=acc2)
-    elif (K._P1_DIRECT and d.dtype == torch.float16 and Ce % 8 == 0 and K.spectral_takes_plane_half(Mo, Co, Ce)):
+    elif (d.dtype == torch.float16 and Ce % 8 == 0 and K.spectral_takes_plane_half(Mo, Co, Ce)):
         c = K.se_scale_bn_plane_half(d, bn1, s2, N, HWo)          # the mixed-precision mode: no row-major c, no layout pass
         (p, done), pctx = K.spectral_fwd(c, Wp, stats=acc2)
     else:
