@@ -307,6 +307,10 @@ int ud_sfmix_fwd(const void* spat, const void* freq, const float* alpha, void* y
     int pool, int f16, ud_stream_t stream);
 int ud_sfmix_bwd(const void* spat, const void* freq, const float* alpha, const void* dy, void* dspat, void*
     dfreq, double* part, float* dalpha, int N, int Ho, int Wo, int C, int pool, int f16, ud_stream_t stream);
+/* dfreq [N][2 Ho][2 Wo][C] = U(dy) / 4 for dy [N][Ho][Wo][C]: the data gradient of the 2 x 2 mean of the pooled frequency branch
+ * alone — ud_sfmix_bwd's dfreq (pool = 1) without the gate factor, dspat and dalpha, for a frozen backward that keeps neither
+ * branch (the gate factor is applied by the ud_rfft2_ex that follows; the spatial branch by the dgrad kernel's gate mode 2) */
+int ud_sfmix_pool_bwd(const void* dy, void* dfreq, int N, int Ho, int Wo, int C, int f16, ud_stream_t stream);
 /* same for two equal-shape tensors (fuse_coef, model/unidefense.py:153-154) */
 int ud_gate_mix_blocks(long total);
 int ud_gate_mix_fwd(const float* p, const float* q, const float* alpha, float* y, long total,
@@ -498,9 +502,13 @@ int ud_affine3(const float* x, const float* M, float* out, int N, int HW, ud_str
  * 2 1 - sigmoid(alpha[0])  (the sf_coef mix of exp.py:61-65 carried into the backward kernels).
  * EVAL FORM: sum == NULL with running_mean and running_var both set is an eval-mode BatchNorm: mean = running_mean and
  * var = running_var (the fixed affine map of nn.BatchNorm2d.eval()); the running buffers are only read, never written,
- * and sumsq / inv_count / unbias / momentum are ignored.  Every forward consumer takes it; every BACKWARD entry point
- * (ud_coldot_bn, ud_normbwd_*, ud_se_scale_bwd_bn, ud_dwconv_bwd_data_bn, ud_dwtile_wgrad, ud_dwtile_bwd, ud_irfft2_dwbwd,
- * ud_pw_bwd_fused, ud_pj_bwd_fused_a / _b) returns UD_EINVAL for it.
+ * and sumsq / inv_count / unbias / momentum are ignored.  Every forward consumer takes it; every TRAINING-FORM BACKWARD entry
+ * point (ud_coldot_bn, ud_normbwd_*, ud_se_scale_bwd_bn, ud_dwconv_bwd_data_bn, ud_dwtile_wgrad, ud_dwtile_bwd, ud_irfft2_dwbwd,
+ * ud_pw_bwd_fused, ud_pj_bwd_fused_a / _b) returns UD_EINVAL for it: their statistics terms do not exist for a fixed affine map.
+ * FROZEN BACKWARD: the backward THROUGH an eval-form BatchNorm is dx = gamma invstd dz per channel — no sums, no apply pass, no
+ * statistics exchange.  The entry points that take it (ud_coldot_bn_eval, ud_se_scale_bwd_bn_eval, ud_bn_eval_bwd,
+ * ud_dwtile_dgrad_eval: the data-gradient-only backward of a frozen MBConv block, tape.mbconv_frozen_half) REQUIRE the eval form
+ * and return UD_EINVAL for a training-form ud_bn_ref; they write no parameter gradient.
  * STATISTICS OFF IN EVAL: a forward whose BatchNorms are all in the eval form needs no batch statistics, so producers
  * whose statistics epilogue is optional skip it when handed no accumulator, and ud_colstats is not launched at all.
  * ud_dwtile (stats 0), ud_gemm (stat_sum NULL) and ud_pj_fwd_fused (sum == sumsq == NULL) always took this; ud_irfft2_mix and
@@ -662,6 +670,8 @@ int ud_normbwd_apply_plane_half(const void* x, const void* dy, const float* keep
  *   a: dpre = dgate[n][c] * sigmoid'(s2);  ds1[n][i] = swish'(s1) sum_c dpre W_e[c][i];
  *      dW_e[c][i] = sum_n dpre swish(s1[n][i]);  db_e[c] = sum_n dpre
  *   b: dpool[n][c] = sum_i ds1 W_r[i][c];  dW_r[i][c] = sum_n ds1[n][i] pool[n][c] * pool_scale;  db_r[i] = sum_n ds1 */
+/* dWe == dbe == NULL (a: both or neither) / dWr == dbr == NULL (b; pool may then be NULL too): the workgroups that form the
+ * weight and bias gradients are not launched — the data-gradient-only backward of a frozen model */
 int ud_se_bwd_a(const double* dgate, const float* s2, const float* s1, const float* We, double* ds1_acc, float* dWe,
                 float* dbe, int N, int C, int Cs, ud_stream_t stream);
 int ud_se_bwd_b(const double* ds1_acc, const float* s1, const float* Wr, const double* pool, float pool_scale,
@@ -671,6 +681,20 @@ int ud_se_bwd_b(const double* ds1_acc, const float* s1, const float* Wr, const d
 int ud_se_scale_bwd_bn(const void* dc, const void* x, const ud_bn_ref* bn, const float* s, const float* dpool,
     float inv_hw, void* dz, double* s1, double* s2, double* ws, int G, int R, int C, int f16, ud_stream_t
     stream);
+/* ---- frozen backward: the same steps through EVAL-FORM BatchNorms (required; UD_EINVAL for the training form) ----
+ * ud_coldot_bn_eval      : out[g][c] += sum_r dy * act(bn(x)) (the SE gate's gradient; out zeroed by the caller).  Deterministic:
+ *                          no atomic add is shared by two workgroups — one row-chunk per sample adds once into the zeroed slot,
+ *                          more go through ws (ud_coldot_bn_eval_ws_doubles(G, R, C) doubles; 0: not needed) and a fold.
+ * ud_se_scale_bwd_bn_eval: dd = (dc * sigmoid(s[g][c]) + dpool[g][c] * inv_hw) * act'(bn(x)) * gamma invstd: the gradient through
+ *                          the SE gate, the swish and BN1 itself in ONE pass over (dc, x); no s1 / s2 / ws.
+ * ud_bn_eval_bwd         : dx = dy * gamma invstd [* act'(bn(x)) when bn->act != 0; x may be NULL otherwise] */
+long ud_coldot_bn_eval_ws_doubles(int G, int R, int C);
+int ud_coldot_bn_eval(const void* dy, const void* x, const ud_bn_ref* bn, int G, int R, int C, double* out, double* ws,
+                      int f16, ud_stream_t stream);
+int ud_se_scale_bwd_bn_eval(const void* dc, const void* x, const ud_bn_ref* bn, const float* s, const float* dpool,
+                            float inv_hw, void* dd, int G, int R, int C, int f16, ud_stream_t stream);
+int ud_bn_eval_bwd(const void* dy, const void* x, const ud_bn_ref* bn, void* dx, int G, int R, int C, int f16,
+                   ud_stream_t stream);
 /* ud_normbwd_apply (dy_is_dz) fused with the gradient of the SF mix y = (1-a) spat + a freq (exp.py:61-65):
  * writes dd = dL/dy and accumulates sum dd * diff, diff = freq - spat as stored by ud_irfft2_mix, into the 64 slots
  * dalpha_acc[0..64) (zeroed by the caller); energy (optional, C doubles zeroed by the caller): += sum_rows dd_c^2, rounded up —
@@ -789,6 +813,14 @@ int ud_dwtile_wgrad(const void* src, const ud_bn_ref* bn_in, const void* dy, con
 int ud_dwtile_bwd(const void* dy, const void* x, const ud_bn_ref* bn, const float* wt, const float* gate_alpha, int gate_mode,
                   const void* add, void* dz, float* dwt, float* wpart, long part_rows, double* s1, double* s2, double* ws,
                   int N, int H, int W, int C, int K, int P_t, int P_l, int f16, ud_stream_t stream);
+/* Frozen backward: ud_dwtile's data gradient (flipped taps, stride 2 through the zero-stuffed grid of dy, gate modes 0 / 1 / 2,
+ * optional add) pushed through the EVAL-FORM BatchNorm + activation of the conv's input xbn in the epilogue:
+ *   dx = (gate * dwconv^T(dy) + add) * act'(bn(xbn)) * gamma invstd
+ * dy [N][Ho][Wo][C]; add (may be NULL) / xbn / dx [N][H][W][C]; pad_t / pad_l: the FORWARD conv's pads; K 3 / 5, stride 1 / 2.
+ * Requires the eval form (UD_EINVAL for a training-form bn); writes no sums and needs no scratch. */
+int ud_dwtile_dgrad_eval(const void* dy, const float* wt, const float* gate_alpha, int gate_mode, const void* add,
+                         const void* xbn, const ud_bn_ref* bn, void* dx, int N, int H, int W, int C, int Ho, int Wo, int K,
+                         int pad_t, int pad_l, int stride, int f16, ud_stream_t stream);
 /* dwt[C][K*K] = gate * sum_p part[p][K*K][C] (fp64 accumulation): the fold of per-workgroup weight-gradient partials, for kernels
  * outside csrc/dwtile.hip that produce them (ud_irfft2_dwbwd) */
 int ud_dwtile_wgrad_finalize(const float* part, int nparts, int K, int C, const float* gate_alpha, int gate_mode, float* dwt,

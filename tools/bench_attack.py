@@ -10,7 +10,13 @@ L-infinity PGD iteration (summed cross-entropy, eps 2/255, step 1/255) on the sa
 alternating window by window; a window is --iters iterations ending in a device synchronise, timed on the host clock (the
 eager loop's cost includes its host gaps).  Reported: the median window of each, their ratio and the windows' spread.
   runner : AttackRunner(steps=iters)(x, y) — the copy-in and `iters` replays of the captured iteration
-  eager  : autograd.grad of the objective on the frozen model, then torch sign / add / max / min / clamp / copy_"""
+  eager  : autograd.grad of the objective on the frozen model, then torch sign / add / max / min / clamp / copy_
+
+    python tools/bench_attack.py --precision both [--size 380 --batch 32]   # UDEB4: the fp16 runner against the fp32 runner
+    python tools/bench_attack.py --precision fp16 --trace-iters 30          # replays only, for a rocprofv3 kernel trace
+
+--precision fp16 / both (UDEB4 only): the captured iteration of AttackRunner(precision=...) — with `both` the two runners' windows
+alternate in one process and the row reports the median of the --windows windows of each, their ratio and every window's spread."""
 import argparse
 import json
 import os
@@ -86,6 +92,38 @@ def _row(name, size, bs, a, dev):
             "max_abs_diff_x_adv": d}
 
 
+def _row_precision(size, bs, a, dev):
+    """UDEB4: per-iteration time of the fp16 and / or the fp32 AttackRunner, windows alternating"""
+    from unidefense_amd.attack import AttackRunner
+    m = _model("UDEB4", dev)
+    x = param_fill.make_input(bs, size, 3).to(dev)
+    y = param_fill.make_labels(bs).to(dev)
+    precs = ("fp32", "fp16") if a.precision == "both" else (a.precision,)
+    runners = {p: AttackRunner(m, bs, size, norm="linf", eps=EPS, steps=a.iters, step=STEP, precision=p) for p in precs}
+    for _ in range(2):                       # the eager warm-up, then the capture
+        for r in runners.values():
+            r(x, y)
+    if a.trace_iters:
+        for r in runners.values():
+            r.steps = a.trace_iters          # replays of the captured iteration only
+            r(x, y)
+        torch.cuda.synchronize(dev)
+        return {"model": "UDEB4", "size": size, "batch": bs, "trace_iters": a.trace_iters, "precision": list(precs),
+                "warmup_iters": 2 * a.iters}
+    t = {p: [] for p in precs}
+    for _ in range(a.windows):
+        for p, r in runners.items():
+            t[p].append(_window(lambda: r(x, y), dev) / a.iters)
+    row = {"model": "UDEB4", "size": size, "batch": bs, "iters_per_window": a.iters, "windows": a.windows}
+    for p in precs:
+        row[f"{p}_ms_per_iter"] = round(statistics.median(t[p]), 3)
+        row[f"{p}_min_max_ms"] = [round(min(t[p]), 3), round(max(t[p]), 3)]
+    if len(precs) == 2:
+        row["fp32_over_fp16"] = round(statistics.median(t["fp32"]) / statistics.median(t["fp16"]), 4)
+        row["linf_x_adv_fp16_vs_fp32"] = float((runners["fp16"](x, y) - runners["fp32"](x, y)).abs().max())
+    return row
+
+
 def _kernels(name, size, bs, a, dev):
     """the four kernels at the row's shape: bytes moved, bytes / 5.5 TB/s, and the time per launch from HIP events over
     --reps back-to-back launches (kernel times proper come from a rocprofv3 run of this mode)"""
@@ -127,8 +165,17 @@ def main():
     ap.add_argument("--windows", type=int, default=5, help="windows per loop (>= 5), alternating")
     ap.add_argument("--kernels", action="store_true", help="launch the four kernels of csrc/attack.hip only")
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--precision", choices=("fp32", "fp16", "both"), default=None,
+                    help="UDEB4: time AttackRunner(precision=...); both: the two runners' windows alternate in one process")
+    ap.add_argument("--size", type=int, default=256, help="with --precision: the input side")
+    ap.add_argument("--batch", type=int, default=32, help="with --precision: the batch size")
+    ap.add_argument("--trace-iters", type=int, default=0,
+                    help="with --precision: after warm-up and capture, replay this many iterations and stop (kernel traces)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.precision is not None:
+        print(json.dumps(_row_precision(a.size, a.batch, a, dev)), flush=True)
+        return
     for name, size, bs in ROWS:
         if name not in a.rows.split(","):
             continue

@@ -4,13 +4,19 @@ same with the parameters requiring grad, and the training step (forward + backwa
     python tools/bench_input_grad.py                    # the three rows, one JSON line each
     python tools/bench_input_grad.py --trace frozen     # eager frozen forward + d/dx passes only (for rocprofv3 runs)
 
+    python tools/bench_input_grad.py --precision both [--size 380 --batch 32]   # UDEB4: InputGradRunner fp16 against fp32
+
 Rows: UDEB4 256^2 bs 32, UDR50 320^2 bs 16, UDR18 256^2 bs 32.  Each column: one eager warm-up, then a hipGraph capture and
---replays timed replays (HIP events; median per replay)."""
+--replays timed replays (HIP events; median per replay).
+--precision fp32 / fp16 / both (UDEB4 only): InputGradRunner(precision=...)(x, y) calls (copy-in + one replay) of the summed
+cross-entropy, in windows of --replays calls timed on the host clock around a device synchronise; with `both` the two runners'
+windows alternate in one process; reported: the median of --windows windows each, their ratio and the windows' spread."""
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 import torch
 
@@ -89,6 +95,36 @@ def _time_captured(fn, replays):
     return statistics.median(ts)
 
 
+def _row_precision(a, dev):
+    from unidefense_amd.attack import InputGradRunner
+    m = _model("UDEB4", dev).eval()
+    x = param_fill.make_input(a.batch, a.size, 3).to(dev)
+    y = param_fill.make_labels(a.batch).to(dev)
+    precs = ("fp32", "fp16") if a.precision == "both" else (a.precision,)
+    runners = {p: InputGradRunner(m, a.batch, a.size, precision=p) for p in precs}
+    for _ in range(3):                       # the eager warm-up, the capture, one replay
+        for r in runners.values():
+            r(x, y)
+    t = {p: [] for p in precs}
+    for _ in range(a.windows):
+        for p, r in runners.items():
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for _ in range(a.replays):
+                r(x, y)
+            torch.cuda.synchronize(dev)
+            t[p].append((time.perf_counter() - t0) * 1e3 / a.replays)
+    row = {"model": "UDEB4", "size": a.size, "batch": a.batch, "calls_per_window": a.replays, "windows": a.windows}
+    for p in precs:
+        row[f"{p}_ms_per_call"] = round(statistics.median(t[p]), 3)
+        row[f"{p}_min_max_ms"] = [round(min(t[p]), 3), round(max(t[p]), 3)]
+    if len(precs) == 2:
+        row["fp32_over_fp16"] = round(statistics.median(t["fp32"]) / statistics.median(t["fp16"]), 4)
+        g32, g16 = runners["fp32"](x, y), runners["fp16"](x, y)
+        row["rel_l2_fp16_vs_fp32"] = float((g16 - g32).norm() / g32.norm())
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--replays", type=int, default=20)
@@ -96,8 +132,16 @@ def main():
     ap.add_argument("--trace", choices=("frozen", "params"), default=None,
                     help="eager forward + d/dx passes only (no capture): the launches a rocprofv3 kernel trace counts")
     ap.add_argument("--passes", type=int, default=3)
+    ap.add_argument("--precision", choices=("fp32", "fp16", "both"), default=None,
+                    help="UDEB4: time InputGradRunner(precision=...); both: the two runners' windows alternate in one process")
+    ap.add_argument("--size", type=int, default=256, help="with --precision: the input side")
+    ap.add_argument("--batch", type=int, default=32, help="with --precision: the batch size")
+    ap.add_argument("--windows", type=int, default=5, help="with --precision: windows per runner")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.precision is not None:
+        print(json.dumps(_row_precision(a, dev)), flush=True)
+        return
     for name, size, bs in ROWS:
         if name not in a.rows.split(","):
             continue

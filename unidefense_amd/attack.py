@@ -11,15 +11,24 @@ or a change of running statistics differentiates the updated model.
 AttackRunner's graph holds ONE iteration — forward on the static leaf x_adv, objective, d/dx, and the step written into x_adv in
 place by csrc/attack.hip (L-infinity: one launch; L2: norm, step, norm, projection) — and a call replays it `steps` times.
 
-fp32 only: the half-storage eval forward (InferenceRunner's precision="fp16") has no backward — every backward entry point
-refuses the eval form of ud_bn_ref — so these runners take no precision argument.
+precision="fp16" (UDEB4 only; runner-scoped like InferenceRunner's): the MBConv trunk's forward AND backward in half storage —
+every block is one tape node (tape.mbconv_frozen_half) whose forward is the fp16 InferenceRunner's (runner.out is bitwise that
+runner's output) and whose backward goes through the eval-form BatchNorms as per-channel constants (csrc: ud_bn_eval_bwd,
+ud_coldot_bn_eval, ud_se_scale_bwd_bn_eval, ud_dwtile_dgrad_eval; the training-form backward entry points keep refusing the eval
+form).  The stem's data gradient, decoder, attention, head and objective stay fp32.  The objective is multiplied by grad_scale (a
+power of two, default 1024: 99.95 % of the unscaled x-gradient's entries lie below fp16's smallest normal) before the backward and
+the fp32 result divided by it inside the graph: runner.g is unscaled; a non-finite gradient stays non-finite.  The eager
+model(x), the fp32 runners and the training step do not change.
 """
 import contextlib
+import math
 
 import torch
 import torch.nn.functional as F
 
-from .infer import _MAX_RUNNERS
+from .infer import _MAX_RUNNERS, _check_precision, _eval_nodes
+
+DEFAULT_GRAD_SCALE = 1024.0          # fp16 runners: the loss scale of the half-storage training tests
 
 NORMS = ("linf", "l2")
 OBJECTIVES = ("cross_entropy",)
@@ -56,6 +65,20 @@ def frozen(model):
             p.requires_grad_(f)
 
 
+def resolve_grad_scale(precision, grad_scale):
+    """The factor on the objective: fp32 takes none (None or 1); fp16: a power of two > 0, DEFAULT_GRAD_SCALE when None."""
+    if precision != "fp16":
+        if grad_scale is not None and float(grad_scale) != 1.0:
+            raise ValueError(f"grad_scale is the fp16 runners' loss scale: precision 'fp32' takes None or 1, got {grad_scale!r}")
+        return 1.0
+    if grad_scale is None:
+        return DEFAULT_GRAD_SCALE
+    g = float(grad_scale)
+    if not (g > 0.0 and g != float("inf") and math.frexp(g)[0] == 0.5):
+        raise ValueError(f"grad_scale must be a power of two > 0, got {grad_scale!r}")
+    return g
+
+
 def _detached(o):
     if isinstance(o, torch.Tensor):
         return o.detach()
@@ -76,10 +99,13 @@ def resolve_step(eps, steps, step=None):
 class _GradRunnerBase:
     _what = "runner"
 
-    def _init_model(self, model, batch, size, objective):
+    def _init_model(self, model, batch, size, objective, precision="fp32", grad_scale=None):
         from .model import MODEL
         if not isinstance(model, tuple(MODEL.values())):
             raise ValueError(f"{self._what} takes a UDEB4 / UDR18 / UDR50 model, got {type(model).__name__}")
+        _check_precision(model, precision)
+        self.precision, self.half = precision, precision == "fp16"
+        self.grad_scale = resolve_grad_scale(precision, grad_scale)
         self.objective = _objective(objective)
         if model.training:
             raise ValueError(f"{self._what} needs model.eval(): the captured forward reads the running statistics")
@@ -104,9 +130,18 @@ class _GradRunnerBase:
 
     def _grad(self, x, y):
         """forward + objective + d/dx on the leaf x: (gradient, detached output dict)"""
-        out = self.model(x)
-        g, = torch.autograd.grad(self.objective(out, y), x)
-        return g, _detached(out)
+        if not self.half:
+            out = self.model(x)
+            g, = torch.autograd.grad(self.objective(out, y), x)
+            return g, _detached(out)
+        # fp16: the trunk's frozen half nodes (runner-scoped flag); the scaled objective keeps the half gradients off fp16's
+        # subnormals, the fp32 result is unscaled in place (inside the graph when capturing)
+        from . import kernels as K
+        with _eval_nodes(self.model, half=True):
+            out = self.model(x)
+            g, = torch.autograd.grad(self.objective(out, y) * self.grad_scale, x)
+        g = g.contiguous()
+        return K.axpby(g, 1.0 / self.grad_scale, out=g), _detached(out)
 
 
 class InputGradRunner(_GradRunnerBase):
@@ -114,11 +149,12 @@ class InputGradRunner(_GradRunnerBase):
     [batch] int64 on the model's GPU: the gradient of objective(model(x), y) with respect to x for the frozen eval-mode model.
     g and runner.out (the forward's output dict, detached) live in static buffers that the next call overwrites.
     objective: "cross_entropy" (cross_entropy_sum) or a callable (out, y) -> scalar that the caller guarantees capturable.
-    fp32 only (no precision argument: the half-storage eval forward has no backward)."""
+    precision: "fp32" or "fp16" (UDEB4: the trunk's forward and frozen backward in half storage); grad_scale: fp16's loss scale,
+    a power of two (None: 1024); g is unscaled either way."""
     _what = "InputGradRunner"
 
-    def __init__(self, model, batch, size, objective="cross_entropy"):
-        self._init_model(model, batch, size, objective)
+    def __init__(self, model, batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
+        self._init_model(model, batch, size, objective, precision, grad_scale)
         self.x = self.y = None
 
     def __call__(self, x, y):
@@ -156,11 +192,11 @@ class AttackRunner(_GradRunnerBase):
     clamp(x + U(-eps, eps), clip), drawn outside the graph with torch's generator (`generator=` makes it reproducible).
     eps, step, clip and the norm are kernel arguments inside the graph: fixed per runner.  eps is in model-input units.
     x_adv and runner.g (the last iteration's gradient, taken at the x_adv BEFORE that iteration's step) are static buffers
-    that the next call overwrites; runner.args holds the resolved arguments."""
+    that the next call overwrites; runner.args holds the resolved arguments.  precision / grad_scale: as InputGradRunner."""
     _what = "AttackRunner"
 
     def __init__(self, model, batch, size, norm="linf", eps=None, steps=10, step=None, random_start=False, targeted=False,
-                 clip=(-1.0, 1.0), objective="cross_entropy"):
+                 clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
         if norm not in NORMS:
             raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
         if eps is None or not float(eps) >= 0.0:
@@ -171,14 +207,15 @@ class AttackRunner(_GradRunnerBase):
             raise ValueError(f"clip must be (lo, hi) with lo < hi, got {clip!r}")
         if norm == "l2" and random_start:
             raise ValueError("random_start is built for norm 'linf' only")
-        self._init_model(model, batch, size, objective)
+        self._init_model(model, batch, size, objective, precision, grad_scale)
         self.norm, self.eps, self.steps = norm, float(eps), int(steps)
         self.step = resolve_step(eps, self.steps, step)
         self.random_start, self.targeted = bool(random_start), bool(targeted)
         self.lo, self.hi = float(clip[0]), float(clip[1])
         self.args = {"norm": norm, "eps": self.eps, "steps": self.steps, "step": self.step, "random_start": self.random_start,
                      "targeted": self.targeted, "clip": (self.lo, self.hi),
-                     "objective": objective if isinstance(objective, str) else getattr(objective, "__name__", repr(objective))}
+                     "objective": objective if isinstance(objective, str) else getattr(objective, "__name__", repr(objective)),
+                     "precision": self.precision, "grad_scale": self.grad_scale}
         self.x0 = self.x_adv = self.y = self._ss = self._ws = None
 
     def _buffers(self, x, y):
@@ -250,16 +287,35 @@ def _cached(model, slot, key, make):
     return r
 
 
-def input_grad_runner(model, batch, size, objective="cross_entropy"):
+def _precision_key(key, precision, grad_scale):
+    """an fp32 runner's key is what it was before the runners took a precision; an fp16 runner's carries (precision, scale)"""
+    return key if precision == "fp32" else key + (precision, resolve_grad_scale(precision, grad_scale))
+
+
+def input_grad_key(batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
+    return _precision_key((int(batch), int(size), objective), precision, grad_scale)
+
+
+def attack_key(batch, size, norm="linf", eps=None, steps=10, step=None, random_start=False, targeted=False,
+               clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
+    return _precision_key((int(batch), int(size), norm, eps, steps, step, bool(random_start), bool(targeted), tuple(clip),
+                           objective), precision, grad_scale)
+
+
+def input_grad_runner(model, batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
     """The model's InputGradRunner for the full argument tuple, made on first use; a model keeps at most _MAX_RUNNERS of them
     (a dictionary of their own: InferenceRunner's cache and keys are untouched)."""
-    key = (int(batch), int(size), objective)
-    return _cached(model, "_ud_grad_runners", key, lambda: InputGradRunner(model, batch, size, objective))
+    _check_precision(model, precision)
+    key = input_grad_key(batch, size, objective, precision, grad_scale)
+    return _cached(model, "_ud_grad_runners", key,
+                   lambda: InputGradRunner(model, batch, size, objective, precision, grad_scale))
 
 
 def attack_runner(model, batch, size, norm="linf", eps=None, steps=10, step=None, random_start=False, targeted=False,
-                  clip=(-1.0, 1.0), objective="cross_entropy"):
+                  clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
     """The model's AttackRunner for the full argument tuple, made on first use; at most _MAX_RUNNERS are kept."""
-    key = (int(batch), int(size), norm, eps, steps, step, bool(random_start), bool(targeted), tuple(clip), objective)
+    _check_precision(model, precision)
+    key = attack_key(batch, size, norm, eps, steps, step, random_start, targeted, clip, objective, precision, grad_scale)
     return _cached(model, "_ud_attack_runners", key,
-                   lambda: AttackRunner(model, batch, size, norm, eps, steps, step, random_start, targeted, clip, objective))
+                   lambda: AttackRunner(model, batch, size, norm, eps, steps, step, random_start, targeted, clip, objective,
+                                        precision, grad_scale))

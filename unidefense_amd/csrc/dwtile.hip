@@ -109,13 +109,19 @@ __device__ __forceinline__ void stage_taps(const float* __restrict__ wt, int C4,
 // EPI 0: plain store.  EPI 1: + sum / sum of squares of the stored result (forward statistics).
 // EPI 2: data gradient: da = gate * acc [+ add]; with a BatchNorm behind it (has_bn_out): dz = da * act'(bn(x)), sums of dz
 //        and dz * xhat.
+// EPI 3: data gradient through an EVAL-FORM BatchNorm (the frozen backward): dx = da * act'(bn(x)) * gamma invstd — the
+//        BatchNorm's whole backward is that per-channel constant, so no sums and no later apply pass.
 // waves per SIMD the register allocation has to leave room for: what the LDS tile allows (57 KB at K = 5 / 16 x 16: two
 // workgroups per CU; 33 - 44 KB otherwise: three or four) — without the bound hipcc hoists every LDS read of the unrolled
 // window loop and takes all 256 VGPRs
 template <int K, int SW> constexpr int kMinWaves = (K == 5 && SW == 8) ? 2 : (SW == 4 ? 4 : 3);
 
+// (the eval-form epilogue's 5 x 5 whole-map instance: its 46 KB of LDS admit three workgroups per CU whatever the registers do, and
+// bounded to four waves the fp32 form spilled 20 bytes)
+template <int K, int CQ, int SW, int EPI> constexpr int kTileWaves = (EPI == 3 && K == 5 && CQ == 16) ? 3 : kMinWaves<K, SW>;
+
 template <typename T, int K, int CQ, int SW, int EPI, int ST = 1>
-__global__ __launch_bounds__(NT, (kMinWaves<K, SW>)) void dw_tile_kernel(TileGeom g, const T* __restrict__ src, ud_bn_ref bn_in, int has_bn_in,
+__global__ __launch_bounds__(NT, (kTileWaves<K, CQ, SW, EPI>)) void dw_tile_kernel(TileGeom g, const T* __restrict__ src, ud_bn_ref bn_in, int has_bn_in,
                                                      const float* __restrict__ wt, T* __restrict__ out,
                                                      const float* __restrict__ gate_alpha, int gate_mode,
                                                      const T* __restrict__ add, const T* __restrict__ xbn,
@@ -124,7 +130,7 @@ __global__ __launch_bounds__(NT, (kMinWaves<K, SW>)) void dw_tile_kernel(TileGeo
     using L = Lds<K, CQ, SW, ST>;
     using S = TileShape<CQ, SW>;
     constexpr int PTH = S::PTH;
-    static_assert(ST == 1 || EPI != 2, "the strided data gradient runs the stride-1 kernel over a zero-stuffed tile");
+    static_assert(ST == 1 || EPI < 2, "the strided data gradient runs the stride-1 kernel over a zero-stuffed tile");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* tile = reinterpret_cast<f32x4*>(smem);
     f32x4* taps = tile + L::TILE_Q;
@@ -143,8 +149,8 @@ __global__ __launch_bounds__(NT, (kMinWaves<K, SW>)) void dw_tile_kernel(TileGeo
     const long obase = (((long)n * g.Ho + (oh < g.Ho ? oh : 0)) * g.Wo) * g.C4 + (cok ? c4 : 0);
     // epilogue operands first: their latency hides behind the staging and the window loop
     const In4<T> add4{add}, x4{xbn};
-    f32x4 pre_add[EPI == 2 ? SW : 1], pre_x[EPI == 2 ? SW : 1];
-    if (EPI == 2) {
+    f32x4 pre_add[EPI >= 2 ? SW : 1], pre_x[EPI >= 2 ? SW : 1];
+    if (EPI >= 2) {
 #pragma unroll
         for (int o = 0; o < SW; ++o) {
             int ow = ow0 + col0 + o;
@@ -186,7 +192,7 @@ __global__ __launch_bounds__(NT, (kMinWaves<K, SW>)) void dw_tile_kernel(TileGeo
     if (cok && oh < g.Ho) {
         Bn4 cbo;
         float gs = 1.f;
-        if (EPI == 2) {
+        if (EPI >= 2) {
             gs = gate_factor(gate_alpha, gate_mode);
             if (has_bn_out) cbo = bn_load(bn_out, 0, g.C4, c4, false);
         }
@@ -210,6 +216,18 @@ __global__ __launch_bounds__(NT, (kMinWaves<K, SW>)) void dw_tile_kernel(TileGeo
                         r[e] = d;
                         v[e] += (double)d;
                         v[4 + e] += (double)d * (double)xh;
+                    }
+                }
+            } else if (EPI == 3) {
+                r = r * gs;
+                if (add) r += pre_add[o];
+                if (has_bn_out) {
+                    const f32x4 a = pre_x[o];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float d = r[e] * (cbo.ga[e] * cbo.is[e]);
+                        if (bn_out.act) d *= ud_act_grad_fast(cbo.ga[e] * ((a[e] - cbo.mu[e]) * cbo.is[e]) + cbo.be[e], bn_out.act);
+                        r[e] = d;
                     }
                 }
             } else if (EPI == 1) {
@@ -622,8 +640,11 @@ int launch_tile(TileGeom g, const T* src, const ud_bn_ref* bn_in, const float* w
                        out, gate_alpha, gate_mode, add, xbn, bo, bn_out ? 1 : 0, use_part ? ws : nullptr, s1, s2)
     if (epi == 0) UD_TILE(0);
     else if (epi == 1) UD_TILE(1);
-    else if constexpr (ST == 1) UD_TILE(2);
-    else return UD_EINVAL;
+    else if constexpr (ST == 1) {
+        if (epi == 2) UD_TILE(2);
+        else if constexpr (SW == 4) UD_TILE(3);          // the eval-form epilogue exists for the strips of 4 its entry point takes
+        else return UD_EINVAL;
+    } else return UD_EINVAL;
 #undef UD_TILE
     UD_LAUNCH_CHECK();
     if (use_part) {
@@ -753,6 +774,34 @@ int ud_dwtile(const void* src, const ud_bn_ref* bn_in, const float* wt, void* ou
     if (epi == 2) UD_GO(5, 8, 4);
     UD_GO(5, 8, 8);
 #undef UD_GO
+}
+
+// The data gradient of ud_dwtile (epi 2: flipped taps, stride 2 through the zero-stuffed grid, gate, add) pushed through an
+// EVAL-FORM BatchNorm + activation of the conv's input: dx = (gate * dwconv^T(dy) + add) * act'(bn(xbn)) * gamma invstd.
+// dy [N][Ho][Wo][C], xbn / add / dx [N][H][W][C]; pad_t / pad_l: the FORWARD conv's pads.  No sums, no scratch.
+// Bytes per element of dx: reads xbn [+ add], writes dx, + dy once per output tile (x (1 + halo) / stride^2).
+int ud_dwtile_dgrad_eval(const void* dy, const float* wt, const float* gate_alpha, int gate_mode, const void* add,
+                         const void* xbn, const ud_bn_ref* bn, void* dx, int N, int H, int W, int C, int Ho, int Wo, int K,
+                         int pad_t, int pad_l, int stride, int f16, ud_stream_t stream) {
+    if (!ud_bn_eval_form(bn) || bn->G != 1) return UD_EINVAL;
+    if (!tile_args_ok(N, Ho, Wo, C, H, W, K) || !dy || !wt || !xbn || !dx) return UD_EINVAL;
+    if (stride != 1 && stride != 2) return UD_EINVAL;
+    if (pad_t < 0 || pad_t > K - 1 || pad_l < 0 || pad_l > K - 1) return UD_EINVAL;
+    if (gate_mode < 0 || gate_mode > 2 || (gate_mode != 0 && !gate_alpha)) return UD_EINVAL;
+    // the forward's extents: every input pixel a tap can reach lies inside dy's (zero-stuffed) grid + halo
+    if (Ho > (H + K - 1) / stride + 1 || Wo > (W + K - 1) / stride + 1 || (long)Ho * stride + K < H || (long)Wo * stride + K < W)
+        return UD_EINVAL;
+    TileGeom g{N, Ho, Wo, C / 4, H, W, K - 1 - pad_t, K - 1 - pad_l, 1, 0, 0, stride == 2 ? 1 : 0};
+    hipStream_t s = (hipStream_t)stream;
+    const bool sm = small_map(H, W, C);
+#define UD_GE(KK, QQ)                                                                                                 \
+    UD_STORAGE_DISPATCH(f16, return (launch_tile<T, KK, QQ, 4>(g, (const T*)dy, nullptr, wt, (T*)dx, gate_alpha, gate_mode, \
+                                                               (const T*)add, (const T*)xbn, bn, 3, nullptr, nullptr,   \
+                                                               nullptr, s)))
+    if (K == 3) { if (sm) UD_GE(3, 16); UD_GE(3, 8); }
+    if (sm) UD_GE(5, 16);
+    UD_GE(5, 8);
+#undef UD_GE
 }
 
 int ud_dwtile_wgrad(const void* src, const ud_bn_ref* bn_in, const void* dy, const float* gate_alpha, int gate_mode,

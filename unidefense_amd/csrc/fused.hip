@@ -567,6 +567,68 @@ __global__ __launch_bounds__(NT) void se_scale_bwd_bn_kernel(RedGeom q, const T*
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Backward through an EVAL-FORM BatchNorm (the frozen half backward of tape.mbconv_frozen_half): mean and variance are
+// constants, so dx = gamma invstd dz per channel — no sums, no second pass, the constant folded into the pass that makes dz.
+// Streaming, element-wise: whole rows per workgroup (geom_ew), a channel quad per access, kRowUnroll<T> rows in flight.
+// ---------------------------------------------------------------------------------------------------------
+// dd = (dc * sigmoid(s) + dpool * inv_hw) * act'(bn(x)) * gamma invstd.   Bytes per element: reads dc, x, writes dd: 3 sizeof(T)
+template <typename T>
+__global__ __launch_bounds__(NT) void se_scale_bwd_bn_eval_kernel(RedGeom q, const T* __restrict__ dc, const T* __restrict__ x,
+                                                                  ud_bn_ref bn, const float* __restrict__ s,
+                                                                  const float* __restrict__ dpool, float inv_hw,
+                                                                  T* __restrict__ ddo) {
+    int ri, c4;
+    if (!thread_coords(q, ri, c4)) return;
+    const In4<T> x4{x}, d4{dc};
+    const Out4<T> o4{ddo};
+    const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, false);
+    f32x4 gate = reinterpret_cast<const f32x4*>(s)[(long)blockIdx.z * q.C4 + c4];
+    const f32x4 dp = reinterpret_cast<const f32x4*>(dpool)[(long)blockIdx.z * q.C4 + c4] * inv_hw;
+    const f32x4 k = cb.ga * cb.is;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]);
+    Rows w = rows_of(q, ri, c4);
+#pragma unroll kRowUnroll<T>
+    for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) {
+        const f32x4 a = x4[w.idx], d = d4[w.idx];
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float g = d[e] * gate[e] + dp[e];
+            if (bn.act) g *= ud_act_grad_fast(cb.ga[e] * ((a[e] - cb.mu[e]) * cb.is[e]) + cb.be[e], bn.act);
+            o[e] = g * k[e];
+        }
+        o4.st(w.idx, o);
+    }
+}
+
+// dx = dy * gamma invstd [* act'(bn(x)) when bn.act; x is not read otherwise].   Bytes per element: 2 sizeof(T) (3 with an activation)
+template <typename T>
+__global__ __launch_bounds__(NT) void bn_eval_bwd_kernel(RedGeom q, const T* __restrict__ dy, const T* __restrict__ x, ud_bn_ref bn,
+                                                         T* __restrict__ dx) {
+    int ri, c4;
+    if (!thread_coords(q, ri, c4)) return;
+    const In4<T> x4{x}, d4{dy};
+    const Out4<T> o4{dx};
+    const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, false);
+    const f32x4 k = cb.ga * cb.is;
+    Rows w = rows_of(q, ri, c4);
+    if (bn.act) {
+#pragma unroll kRowUnroll<T>
+        for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) {
+            const f32x4 a = x4[w.idx];
+            f32x4 o = d4[w.idx] * k;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] *= ud_act_grad_fast(cb.ga[e] * ((a[e] - cb.mu[e]) * cb.is[e]) + cb.be[e], bn.act);
+            o4.st(w.idx, o);
+        }
+    } else {
+#pragma unroll kRowUnroll<T>
+        for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) o4.st(w.idx, d4[w.idx] * k);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // SE backward FCs
 // ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float dpre_of(const double* dgate, const float* s2, long i) {
@@ -1172,14 +1234,15 @@ int ud_gate_grad_from_acc(const double* acc, const float* alpha, float* out, ud_
 
 int ud_se_bwd_a(const double* dgate, const float* s2, const float* s1, const float* We, double* ds1_acc, float* dWe,
                 float* dbe, int N, int C, int Cs, ud_stream_t stream) {
-    if (N < 1 || C < 1 || Cs < 1 || Cs > 128 || !dgate || !s2 || !s1 || !We || !ds1_acc || !dWe || !dbe) return UD_EINVAL;
+    if (N < 1 || C < 1 || Cs < 1 || Cs > 128 || !dgate || !s2 || !s1 || !We || !ds1_acc || (!dWe != !dbe)) return UD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int role1 = N * ud_cdiv(C, Cs <= 64 ? 32 * (NT / 64) : 32 * (NT / 128));
+    const bool wg = dWe != nullptr;          // dWe == dbe == NULL (a frozen backward): the weight-gradient workgroups are not launched
     if (Cs <= 64) {
-        dim3 grid((unsigned)(role1 + ud_cdiv(C, NT / 64)));
+        dim3 grid((unsigned)(role1 + (wg ? ud_cdiv(C, NT / 64) : 0)));
         hipLaunchKernelGGL(se_bwd_a_kernel<64>, grid, dim3(NT), 0, s, dgate, s2, s1, We, ds1_acc, dWe, dbe, N, C, Cs);
     } else {
-        dim3 grid((unsigned)(role1 + ud_cdiv(C, NT / 128)));
+        dim3 grid((unsigned)(role1 + (wg ? ud_cdiv(C, NT / 128) : 0)));
         hipLaunchKernelGGL(se_bwd_a_kernel<128>, grid, dim3(NT), 0, s, dgate, s2, s1, We, ds1_acc, dWe, dbe, N, C, Cs);
     }
     UD_LAUNCH_CHECK();
@@ -1188,9 +1251,10 @@ int ud_se_bwd_a(const double* dgate, const float* s2, const float* s1, const flo
 
 int ud_se_bwd_b(const double* ds1_acc, const float* s1, const float* Wr, const double* pool, float pool_scale,
                 float* dpool, float* dWr, float* dbr, int N, int C, int Cs, ud_stream_t stream) {
-    if (N < 1 || N > NT || C < 1 || Cs < 1 || Cs > NT || !ds1_acc || !s1 || !Wr || !pool || !dpool || !dWr || !dbr)
+    const bool wg = dWr != nullptr;          // dWr == dbr == NULL (a frozen backward): only the dpool rows are launched; pool is not read
+    if (N < 1 || N > NT || C < 1 || Cs < 1 || Cs > NT || !ds1_acc || !s1 || !Wr || !dpool || (!dWr != !dbr) || (wg && !pool))
         return UD_EINVAL;
-    dim3 grid((unsigned)ud_cdiv(C, NT), (unsigned)(N + Cs));
+    dim3 grid((unsigned)ud_cdiv(C, NT), (unsigned)(N + (wg ? Cs : 0)));
     hipLaunchKernelGGL(se_bwd_b_kernel, grid, dim3(NT), 0, (hipStream_t)stream, ds1_acc, s1, Wr, pool, pool_scale, dpool,
                        dWr, dbr, N, C, Cs);
     UD_LAUNCH_CHECK();
@@ -1209,6 +1273,58 @@ int ud_se_scale_bwd_bn(const void* dc, const void* x, const ud_bn_ref* bn, const
                                                 pl.use_part ? ws : nullptr));
     UD_LAUNCH_CHECK();
     return finish_reduce(pl, 2, false, C, ws, s1, s2, st);
+}
+
+// ---- the frozen backward's entry points: they REQUIRE the eval form of ud_bn_ref (the ones above refuse it) ----------------
+// The SE-gate dot shares its kernel with ud_coldot_bn (bn_load reads either form) but never adds across workgroups with atomics:
+// one row-chunk per sample stores straight into the zeroed accumulator's slot (a single add per address), more of them go through
+// fp64 partials and the fold — the result does not depend on the order in which workgroups finish.
+static RedGeom coldot_eval_geom(int G, int R, int C) { return make_geom_ex(G, R, C, 1024, 64, 8); }
+
+long ud_coldot_bn_eval_ws_doubles(int G, int R, int C) {
+    if (!shape_ok(G, R, C)) return UD_EINVAL;
+    const RedGeom q = coldot_eval_geom(G, R, C);
+    return q.P > 1 ? (long)q.G * q.P * C : 0;
+}
+
+int ud_coldot_bn_eval(const void* dy, const void* x, const ud_bn_ref* bn, int G, int R, int C, double* out, double* ws,
+                      int f16, ud_stream_t stream) {
+    if (!ud_bn_eval_form(bn) || bn->G != 1) return UD_EINVAL;
+    if (!shape_ok(G, R, C) || !x || !dy || !out) return UD_EINVAL;
+    const RedGeom q = coldot_eval_geom(G, R, C);
+    const bool use_part = q.P > 1;
+    if (use_part && !ws) return UD_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    UD_STORAGE_DISPATCH(f16, hipLaunchKernelGGL((colsum_bn_kernel<T, true>), red_grid(q), dim3(NT), 0, s, q, (const T*)x,
+                                                (const T*)dy, *bn, out, use_part ? ws : nullptr, (uint32_t*)nullptr));
+    UD_LAUNCH_CHECK();
+    if (use_part) {
+        hipLaunchKernelGGL(partials_to_acc, dim3(ud_cdiv((long)G * C, 8)), dim3(NT), 0, s, 1, G, C, q.P, ws, out, nullptr);
+        UD_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int ud_se_scale_bwd_bn_eval(const void* dc, const void* x, const ud_bn_ref* bn, const float* s, const float* dpool,
+                            float inv_hw, void* dd, int G, int R, int C, int f16, ud_stream_t stream) {
+    if (!ud_bn_eval_form(bn) || bn->G != 1) return UD_EINVAL;
+    if (!shape_ok(G, R, C) || !dc || !x || !s || !dpool || !dd) return UD_EINVAL;
+    RedGeom q = geom_ew(G, R, C);
+    UD_STORAGE_DISPATCH(f16, hipLaunchKernelGGL(se_scale_bwd_bn_eval_kernel<T>, red_grid(q), dim3(NT), 0, (hipStream_t)stream, q,
+                                                (const T*)dc, (const T*)x, *bn, s, dpool, inv_hw, (T*)dd));
+    UD_LAUNCH_CHECK();
+    return 0;
+}
+
+int ud_bn_eval_bwd(const void* dy, const void* x, const ud_bn_ref* bn, void* dx, int G, int R, int C, int f16,
+                   ud_stream_t stream) {
+    if (!ud_bn_eval_form(bn) || bn->G != 1) return UD_EINVAL;
+    if (!shape_ok(G, R, C) || !dy || !dx || (bn->act && !x) || bn->act < 0 || bn->act > 2) return UD_EINVAL;
+    RedGeom q = geom_ew(G, R, C);
+    UD_STORAGE_DISPATCH(f16, hipLaunchKernelGGL(bn_eval_bwd_kernel<T>, red_grid(q), dim3(NT), 0, (hipStream_t)stream, q,
+                                                (const T*)dy, (const T*)x, *bn, (T*)dx));
+    UD_LAUNCH_CHECK();
+    return 0;
 }
 
 // items of the depthwise data-gradient kernels (rows of their column-owning decomposition) and its scratch need

@@ -234,6 +234,26 @@ __global__ __launch_bounds__(NT) void sfmix_bwd(long total4, int Ho, int Wo, int
     }
 }
 
+// dfreq[n][h][w] = dy[n][h / 2][w / 2] / 4: the data gradient of the 2 x 2 mean (pooled_freq) alone — what sfmix_bwd writes
+// as dfreq without its gate factor, for a frozen backward that keeps neither branch and wants no gate gradient (the gate is
+// applied by the transform that follows).  One thread per quad of dfreq: contiguous stores, dy read 4 times through L2.
+template <typename T>
+__global__ __launch_bounds__(NT) void sfmix_pool_bwd(long total4, int H, int W, int C4, const T* __restrict__ dy,
+                                                     T* __restrict__ dfreq) {
+    const In4<T> d4{dy};
+    const Out4<T> o4{dfreq};
+    const int Ho = H / 2, Wo = W / 2;
+    for (long e = (long)blockIdx.x * NT + threadIdx.x; e < total4; e += (long)gridDim.x * NT) {
+        const int c4 = (int)(e % C4);
+        const long pix = e / C4;
+        const int w = (int)(pix % W);
+        const long t = pix / W;
+        const int h = (int)(t % H);
+        const long n = t / H;
+        o4.st(e, d4[((n * Ho + h / 2) * Wo + w / 2) * C4 + c4] * 0.25f);
+    }
+}
+
 // out[0] (+)= sigmoid'(alpha) * sum(part[0..n))        (gradient of a sigmoid-gated scalar coefficient)
 __global__ __launch_bounds__(NT) void gate_grad_finalize(int n, const double* __restrict__ part,
                                                          const float* __restrict__ alpha, float* __restrict__ out) {
@@ -709,6 +729,16 @@ int ud_sfmix_bwd(const void* spat, const void* freq, const float* alpha, const v
                                                 (T*)dfreq, part));
     UD_LAUNCH_CHECK();
     hipLaunchKernelGGL(gate_grad_finalize, dim3(1), dim3(NT), 0, s, nb, part, alpha, dalpha);
+    UD_LAUNCH_CHECK();
+    return 0;
+}
+
+// dfreq [N][2 Ho][2 Wo][C] = U(dy) / 4 for dy [N][Ho][Wo][C]: ud_sfmix_bwd's pooled dfreq without the gate, dspat and dalpha
+int ud_sfmix_pool_bwd(const void* dy, void* dfreq, int N, int Ho, int Wo, int C, int f16, ud_stream_t stream) {
+    if (N < 1 || Ho < 1 || Wo < 1 || C < 4 || C % 4 || !dy || !dfreq) return UD_EINVAL;
+    const long total4 = (long)N * Ho * Wo * 4 * (C / 4);
+    UD_STORAGE_DISPATCH(f16, hipLaunchKernelGGL(sfmix_pool_bwd<T>, dim3(ew_blocks(total4)), dim3(NT), 0, (hipStream_t)stream,
+                                                total4, 2 * Ho, 2 * Wo, C / 4, (const T*)dy, (T*)dfreq));
     UD_LAUNCH_CHECK();
     return 0;
 }

@@ -256,8 +256,9 @@ class TrainEngine(AbstractEngine):
         the model's AttackRunner (unidefense_amd/attack.py) and scored again the same way.  attack (default
         config['config']['attack']): the runner's keyword arguments, e.g. {"norm": "linf", "eps": 4/255, "steps": 10} — eps in
         model-input units (after Normalize(0.5, 0.5) one 8-bit grey level is 2/255).  Returns {"clean": what test() returns,
-        "adv": the same keys on x_adv, "attack": the resolved arguments}.  inference_graph / inference_precision keep their
-        meaning for the two scoring forwards.  Data parallel: each rank attacks its own batches on the un-wrapped model (a
+        "adv": the same keys on x_adv, "attack": the resolved arguments, precision and grad_scale included}.  The attack dict's
+        "precision": "fp16" (UDEB4; optional "grad_scale") runs the attack's frozen pass in half storage; inference_graph /
+        inference_precision keep their meaning for the two scoring forwards.  Data parallel: each rank attacks its own batches on the un-wrapped model (a
         frozen pass has no collective of its own) and the scores are gathered over the ranks as in _score."""
         from .metrics import gather_scores
         attack = attack if attack is not None else self.config["config"].get("attack")

@@ -2823,13 +2823,19 @@ def gate_grad_from_acc(acc, alpha):
     return out
 
 
-def se_bwd(dgate, s2, s1, We, Wr, pool, pool_scale):
+def se_bwd(dgate, s2, s1, We, Wr, pool, pool_scale, need_w=True):
     """Backward of the two SE FCs (model.py:119-121) in two launches.  dgate: fp64 [N, C] (gradient of the gate
-    sigmoid(s2)); pool: fp64 pooled SUMS.  Returns (dpool, dWe, dbe, dWr, dbr)."""
+    sigmoid(s2)); pool: fp64 pooled SUMS.  Returns (dpool, dWe, dbe, dWr, dbr).
+    need_w=False (a frozen backward): only dpool — the weight / bias gradient workgroups are not launched, pool is not read."""
     _chk(s2, s1, We, Wr)
     N, Cc = s2.shape
     Cs = s1.shape[1]
     ds1_acc = zeros64(N * Cs, s2)
+    if not need_w:
+        _call("ud_se_bwd_a", _pd(dgate), _p(s2), _p(s1), _p(We), _pd(ds1_acc), None, None, N, Cc, Cs, _stream())
+        dpool = empty((N, Cc), s2)
+        _call("ud_se_bwd_b", _pd(ds1_acc), _p(s1), _p(Wr), None, 0.0, _p(dpool), None, None, N, Cc, Cs, _stream())
+        return dpool, None, None, None, None
     dWe = empty((Cc, Cs), s2)
     dbe = empty((Cc,), s2)
     _call("ud_se_bwd_a", _pd(dgate), _p(s2), _p(s1), _p(We), _pd(ds1_acc), _p(dWe), _p(dbe), N, Cc, Cs, _stream())
@@ -2849,6 +2855,44 @@ def se_scale_bwd_bn(dc, x, bn, s, dpool, inv_hw, G, R, sacc):
     _call("ud_se_scale_bwd_bn", _p(dc), _p(x), C.byref(bn.ref()), _p(s), _p(dpool), float(inv_hw), _p(dz), _pd(sacc),
           _pd(sacc, Cc), _fused_ws(x, G, R, Cc, False), G, R, Cc, h, _stream())
     return dz
+
+
+# ---- the frozen backward (tape.mbconv_frozen_half): through EVAL-FORM BatchNorms (EvalBN), data gradients only ----
+def coldot_bn_eval(dy, x, bn, G, R, out):
+    """out[g][c] += sum_r dy * act(bn(x)) for an EvalBN (the SE gate's gradient); deterministic (no atomics across workgroups)"""
+    h = _act(dy, x)
+    Cc = x.shape[-1]
+    ws = _ws64(x, _call("ud_coldot_bn_eval_ws_doubles", G, R, Cc))
+    _call("ud_coldot_bn_eval", _p(dy), _p(x), C.byref(bn.ref()), G, R, Cc, _pd(out), ws, h, _stream())
+
+
+def se_scale_bwd_bn_eval(dc, x, bn, s, dpool, inv_hw, G, R):
+    """dd = (dc * sigmoid(s) + dpool * inv_hw) * act'(bn(x)) * gamma invstd for an EvalBN: gate + swish + BN1 backward, one pass"""
+    h = _act(dc, x)
+    _chk(s, dpool)
+    Cc = x.shape[-1]
+    dd = torch.empty_like(x)
+    _call("ud_se_scale_bwd_bn_eval", _p(dc), _p(x), C.byref(bn.ref()), _p(s), _p(dpool), float(inv_hw), _p(dd), G, R, Cc, h,
+          _stream())
+    return dd
+
+
+def bn_eval_bwd(dy, x, bn, G, R):
+    """dx = dy * gamma invstd [* act'(bn(x)) when bn.act; x may be None otherwise] for an EvalBN"""
+    h = _act(dy, x)
+    Cc = dy.shape[-1]
+    dx = torch.empty_like(dy)
+    _call("ud_bn_eval_bwd", _p(dy), _p(x), C.byref(bn.ref()), _p(dx), G, R, Cc, h, _stream())
+    return dx
+
+
+def sfmix_pool_bwd(dy):
+    """U(dy) / 4 [N, 2 Ho, 2 Wo, C]: the pooled frequency branch's data gradient without the gate (sfmix_bwd's dfreq / sigmoid(a))"""
+    h = _act(dy)
+    N, Ho, Wo, Cc = dy.shape
+    df = empty((N, 2 * Ho, 2 * Wo, Cc), dy, dy.dtype)
+    _call("ud_sfmix_pool_bwd", _p(dy), _p(df), N, Ho, Wo, Cc, h, _stream())
+    return df
 
 
 def dwconv_bwd_data_bn(dy, gate_alpha, gate_mode, wt, add, x, bn, K, stride, pad_t, pad_l, sacc):
@@ -3003,6 +3047,19 @@ def dwtile_bwd_data(dy, wt, K, pad_t, pad_l, H, W, gate_alpha=None, gate_mode=0,
           _p(gate_alpha), int(gate_mode), _p(add), _p(x) if bn is not None else None, _bnp(bn), 2,
           _pd(sacc) if bn is not None else None, _pd(sacc, Cc) if bn is not None else None, ws, int(stride), h, _stream())
     return out
+
+
+def dwtile_dgrad_eval(dy, wt, K, pad_t, pad_l, x, bn, gate_alpha=None, gate_mode=0, add=None, stride=1):
+    """dx = (gate * dwconv_bwd_data(dy) + add) * act'(bn(x)) * gamma invstd for an EvalBN on the conv's input x [N,H,W,C] (the
+    frozen backward's depthwise step: no sums, no scratch); pad_t / pad_l: the forward conv's pads."""
+    h = _act(dy, add, x)
+    _chk(wt)
+    N, H, W, Cc = x.shape
+    _, Ho, Wo, _ = dy.shape
+    dx = torch.empty_like(x)
+    _call("ud_dwtile_dgrad_eval", _p(dy), _p(wt), _p(gate_alpha), int(gate_mode), _p(add), _p(x), C.byref(bn.ref()), _p(dx),
+          N, H, W, Cc, Ho, Wo, K, pad_t, pad_l, int(stride), h, _stream())
+    return dx
 
 
 _DWTILE_PART = {}

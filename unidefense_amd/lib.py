@@ -125,6 +125,7 @@ _SIGNATURES = {
     "ud_sfmix_blocks": [_I, _I, _I, _I],
     "ud_sfmix_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "ud_sfmix_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ud_sfmix_pool_bwd": [_P, _P, _I, _I, _I, _I, _I, _P],
     "ud_gate_mix_blocks": [_L],
     "ud_gate_mix_fwd": [_P, _P, _P, _P, _L, _P],
     "ud_gate_mix_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _P],
@@ -212,6 +213,10 @@ _SIGNATURES = {
     "ud_se_bwd_a": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "ud_se_bwd_b": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
     "ud_se_scale_bwd_bn": [_P, _P, _BN, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "ud_coldot_bn_eval_ws_doubles": [_I, _I, _I],
+    "ud_coldot_bn_eval": [_P, _P, _BN, _I, _I, _I, _P, _P, _I, _P],
+    "ud_se_scale_bwd_bn_eval": [_P, _P, _BN, _P, _P, _F, _P, _I, _I, _I, _I, _P],
+    "ud_bn_eval_bwd": [_P, _P, _BN, _P, _I, _I, _I, _I, _P],
     "ud_bn_apply": [_P, _BN, _P, _I, _I, _I, _I, _P],
     "ud_dwconv_bwd_data_bn": [_P, _P, _I, _P, _P, _P, _BN, _P, _P, _P, _P] + [_I] * 10 + [_I, _P],
     "ud_dwconv_bwd_data_bn_ws_doubles": [_I, _I, _I, _I, _I],
@@ -231,6 +236,7 @@ _SIGNATURES = {
     "ud_dwtile_wgrad_finalize_multi": [C.POINTER(WgradFold), _I, _P],
     "ud_rfft2_ex_plane_half": [_P, _P, _L, _P, _I, _I, _I, _F, _F, _BN, _P, _P, _I, _P, _P, _P, _P, _I, _P],
     "ud_irfft2_dwbwd": [_P, _I, _I, _I, _F, _F, _P, _P, _BN, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P],
+    "ud_dwtile_dgrad_eval": [_P, _P, _P, _I, _P, _P, _BN, _P] + [_I] * 11 + [_P],
     "ud_dwtile_bwd": [_P, _P, _BN, _P, _P, _I, _P, _P, _P, _P, _L, _P, _P, _P] + [_I] * 8 + [_P],
     "ud_rfft2_planes_ws_floats": [_L, _I],
     "ud_rfft2_planes": [_P, _P, _P, _L, _I, _F, _P],
@@ -251,9 +257,10 @@ _SIGNATURES = {
 # helpers that return a count rather than a status code
 _COUNT_FUNCS = {"ud_mb_eval_dw_ok", "ud_mb_eval_dw_tiles", "ud_mb_eval_dw_h_ok", "ud_mb_eval_dw_h_tiles", "ud_pj_fwd_fused_ok", "ud_pj_bwd_fused_ok", "ud_pj_bwd_fused_grid", "ud_pw_bwd_fused_ok", "ud_pw_bwd_fused_grid", "ud_loss_tail_ws_floats", "ud_dwtile_wgrad", "ud_dwtile_bwd", "ud_fft32_set_wave", "ud_fft2_two_pass_ws_floats", "ud_dwtile_ws_doubles", "ud_dwtile_wgrad_part_rows", "ud_reduce_ws_doubles", "ud_gemm_query_path", "ud_gemm_get_path", "ud_gemm_stats_slots", "ud_adamw_chunk_elems", "ud_rfft2_planes_ws_floats", "ud_fused_reduce_ws_doubles", "ud_dwconv_bwd_data_bn_ws_doubles", "ud_dwconv_bwd_weight_parts", "ud_sfmix_blocks", "ud_gate_mix_blocks",
                 "ud_l1_chunks", "ud_efdm_ws_bytes", "ud_conv_small_supported", "ud_conv_small_wgrad_supported",
-                "ud_conv_small_wgrad_ws_floats", "ud_xchg_bytes", "ud_stem_dgrad_supported", "ud_sample_sumsq_ws_bytes"}
+                "ud_conv_small_wgrad_ws_floats", "ud_xchg_bytes", "ud_stem_dgrad_supported", "ud_sample_sumsq_ws_bytes",
+                "ud_coldot_bn_eval_ws_doubles"}
 _LONG_FUNCS = {"ud_mb_eval_dw_tiles", "ud_mb_eval_dw_h_tiles", "ud_pj_bwd_fused_grid", "ud_pw_bwd_fused_grid", "ud_fft2_two_pass_ws_floats", "ud_dwtile_ws_doubles", "ud_dwtile_wgrad_part_rows", "ud_xchg_bytes", "ud_efdm_ws_bytes", "ud_rfft2_planes_ws_floats", "ud_conv_small_wgrad_ws_floats", "ud_fused_reduce_ws_doubles",
-               "ud_dwconv_bwd_data_bn_ws_doubles", "ud_sample_sumsq_ws_bytes"}        # return a C long
+               "ud_dwconv_bwd_data_bn_ws_doubles", "ud_sample_sumsq_ws_bytes", "ud_coldot_bn_eval_ws_doubles"}        # return a C long
 
 EXPORTED = tuple(_SIGNATURES)
 

@@ -273,15 +273,16 @@ class UniDefenseModelEb4(nn.Module):
         from ..infer import inference_runner
         return inference_runner(self, batch, size, precision)
 
-    def input_grad_runner(self, batch, size, objective="cross_entropy"):
+    def input_grad_runner(self, batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
         """The graph-replayed gradient of objective(model(x), y) with respect to x for [batch, 3, size, size] inputs
-        (unidefense_amd/attack.py: InputGradRunner), cached per argument tuple."""
+        (unidefense_amd/attack.py: InputGradRunner), cached per argument tuple.  precision "fp16": the MBConv trunk's forward and
+        backward in half storage (tape.mbconv_frozen_half), the objective scaled by grad_scale (default 1024) and the result unscaled."""
         from ..attack import input_grad_runner
-        return input_grad_runner(self, batch, size, objective)
+        return input_grad_runner(self, batch, size, objective, precision, grad_scale)
 
     def attack_runner(self, batch, size, **kwargs):
         """The graph-replayed FGSM / PGD attack for [batch, 3, size, size] inputs (unidefense_amd/attack.py: AttackRunner;
-        kwargs: norm, eps, steps, step, random_start, targeted, clip, objective), cached per argument tuple."""
+        kwargs: norm, eps, steps, step, random_start, targeted, clip, objective, precision, grad_scale), cached per argument tuple."""
         from ..attack import attack_runner
         return attack_runner(self, batch, size, **kwargs)
 
@@ -443,10 +444,14 @@ class UniDefenseModelEb4(nn.Module):
                 x = T.mbconv_fused(tape, x, blk, keep, 1.0 - rate, fused["wt"][id(blk._depthwise_conv.weight)],
                                    fused["dp"], lazy_in if idx == 0 else None, next_blk=nxt)
             elif rng.get("_eval16") is not None and (blk.spec.sf_norm is None or K.fft_kernel_size(x.shape[1])):
-                # the fp16 InferenceRunner's forward: half storage, eval-form BatchNorms, no statistics (an SF block on a map side
+                # the fp16 runners' forward: half storage, eval-form BatchNorms, no statistics (an SF block on a map side
                 # with no in-register transform — 95 at 380 x 380 — takes the operator path below, in fp32 between two casts)
-                x = T.mbconv_eval_half(x, blk, rng["_eval16"][id(blk._depthwise_conv.weight)], lazy_in if idx == start else None,
-                                       self.EVAL_NODE_H_MAX_CIN)
+                wt = rng["_eval16"][id(blk._depthwise_conv.weight)]
+                if tape is not None:
+                    # an fp16 gradient runner (unidefense_amd/attack.py): the same forward as ONE tape node with the frozen half backward
+                    x = T.mbconv_frozen_half(tape, x, blk, wt, lazy_in if idx == start else None)
+                else:
+                    x = T.mbconv_eval_half(x, blk, wt, lazy_in if idx == start else None, self.EVAL_NODE_H_MAX_CIN)
             elif tape is None and not self.training and self.__dict__.get("_eval_fused") and self._eval_block_ok(blk):
                 # eval-mode node of an InferenceRunner's forward (unidefense_amd/infer.py): expand conv inside the depthwise pass
                 x = self._mbconv_eval(x, blk)
@@ -565,8 +570,9 @@ class UniDefenseModelEb4(nn.Module):
         # registers, fp64 BatchNorm sums, fp32 weights / weight gradients, fp16 MFMA); stem conv, decoder, attention,
         # head and losses stay fp32 — T.cast at the boundaries.  Fused training path only.
         fused = self.training and _fused_mbconv()
-        # the fp16 InferenceRunner (unidefense_amd/infer.py): the eval forward with the same storage boundaries
-        ev16 = tape is None and not self.training and bool(self.__dict__.get("_eval_half"))
+        # the fp16 InferenceRunner (unidefense_amd/infer.py): the eval forward with the same storage boundaries; with a tape: the fp16
+        # InputGradRunner / AttackRunner (unidefense_amd/attack.py), whose frozen backward stays in half storage too
+        ev16 = not self.training and bool(self.__dict__.get("_eval_half"))
         st16 = (fused and _half_storage(self)) or ev16
         f32 = torch.float32
         if fused:
@@ -580,8 +586,16 @@ class UniDefenseModelEb4(nn.Module):
         elif ev16:
             # the stem conv's output rounded once to half; its eval BatchNorm + swish applied on load by block 0's depthwise conv
             rng["_eval16"] = wts
-            h = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False).to(torch.float16)
-            x_b0 = self._blocks(tape, h, 0, rng, K.EvalBN(bb._bn0, 1))
+            stem_bn = K.EvalBN(bb._bn0, 1)
+            if tape is None:
+                h = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False).to(torch.float16)
+                x_b0 = self._blocks(tape, h, 0, rng, stem_bn)
+            else:
+                # recorded first, replayed last: block 0's depthwise pass hands back the gradient of the raw half stem output (already
+                # through the stem's eval BatchNorm + swish), the cast makes it fp32 and ud_stem_dgrad completes x.grad
+                h32 = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False, x_planes=x_in)
+                h = T.cast(tape, h32, torch.float16)
+                x_b0 = self._blocks(tape, h, 0, rng, T.LazyInput(stem_bn, lambda dh, h=h: tape.add_grad(h, dh)))
         else:
             h = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False, x_planes=x_in)
             h = self._bn(tape, h, bb._bn0, 1)

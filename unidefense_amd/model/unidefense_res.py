@@ -154,15 +154,17 @@ class UniDefenseModelRes18(nn.Module):
         from ..infer import inference_runner
         return inference_runner(self, batch, size, precision)
 
-    def input_grad_runner(self, batch, size, objective="cross_entropy"):
+    def input_grad_runner(self, batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
         """The graph-replayed gradient of objective(model(x), y) with respect to x for [batch, 3, size, size] inputs
-        (unidefense_amd/attack.py: InputGradRunner), cached per argument tuple."""
+        (unidefense_amd/attack.py: InputGradRunner), cached per argument tuple.  fp32 only (precision "fp16" raises ValueError:
+        the ResNet variants have no half-storage path)."""
         from ..attack import input_grad_runner
-        return input_grad_runner(self, batch, size, objective)
+        return input_grad_runner(self, batch, size, objective, precision, grad_scale)
 
     def attack_runner(self, batch, size, **kwargs):
         """The graph-replayed FGSM / PGD attack for [batch, 3, size, size] inputs (unidefense_amd/attack.py: AttackRunner;
-        kwargs: norm, eps, steps, step, random_start, targeted, clip, objective), cached per argument tuple."""
+        kwargs: norm, eps, steps, step, random_start, targeted, clip, objective, precision — "fp32" only here), cached per
+        argument tuple."""
         from ..attack import attack_runner
         return attack_runner(self, batch, size, **kwargs)
 

@@ -1522,3 +1522,137 @@ def _eval_half_tail(x, blk, d, bn1, s1, N, HWo, Mo):
     c = K.se_scale_bn(d, bn1, s2, N, HWo)
     p = K.gemm_nt(c.view(Mo, Ce), blk._project_conv.weight.view(Co, Ce))
     return K.residual_bn(p.view(N, Ho, Wo, Co), K.EvalBN(blk._bn2, 0), None, 1.0, x if sp.skip else None, N, HWo)
+
+
+# measurement hook of the frozen half backward: a callable (block's parameter container, name, half tensor) called for every half
+# gradient tensor the node stores (tests and DESIGN 3l record the largest scaled magnitude against fp16's 65504 with it); None: off
+HALF_GRAD_PROBE = None
+
+
+def mbconv_frozen_half(tape, x, blk, wt, lazy_in=None):
+    """MBConvBlock.forward in eval mode, half storage, as ONE tape node whose backward is the FROZEN one (the fp16 InputGradRunner /
+    AttackRunner, unidefense_amd/attack.py): data gradients only, through eval-form BatchNorms.
+
+    Forward: mbconv_eval_half's composed kernels in the same order (the outputs are bitwise the fp16 InferenceRunner's).  Kept for
+    the backward: e (raw expand output), d (raw depthwise / SF output), s1, s2 — not the gated tensor, the spectra, the two SF
+    branches or any activated tensor.
+    Backward (half storage, fp32 registers; an eval BatchNorm's backward is the per-channel constant gamma invstd, folded into the
+    kernel that makes the gradient — no sums, no apply pass, no fp64 accumulators but the SE gate's):
+      dp = gamma2 invstd2 dout (ud_bn_eval_bwd, the thin tensor) -> dc = dp @ Wp (half GEMM) -> dgate = sum_hw dc swish(bn1(d))
+      (ud_coldot_bn_eval) -> the SE FCs' data gradient (ud_se_bwd_a / _b without their weight-gradient workgroups) ->
+      dd = (dc sigmoid(s2) + dpool / HW) swish'(bn1(d)) gamma1 invstd1 (ud_se_scale_bwd_bn_eval) -> SF: the adjoint transforms
+      around the spectral data-gradient GEMM, the gate applied by ud_rfft2_ex (frequency) and the dgrad kernel (spatial) ->
+      de = (gate dwconv^T(dd) + da_f) swish'(bn0(e)) gamma0 invstd0 (ud_dwtile_dgrad_eval) -> dx = de @ We (+ the skip gradient).
+    x [N,H,W,Cin] fp16; for block 0: the raw half stem output, lazy_in = LazyInput(the stem's EvalBN, backward(dh))."""
+    if tape.wgrad_on:
+        raise RuntimeError("mbconv_frozen_half is the backward of a FROZEN model (no parameter requires a gradient): it forms no "
+                           "weight gradient; a half-storage backward with trainable parameters is the training step's")
+    sp = blk.spec
+    N, H, W, Cin = x.shape
+    M = N * H * W
+    k, stride = sp.k, sp.stride
+    pl, pr, pt, pb = sp.pad
+    Ho = (H + pt + pb - k) // stride + 1
+    Wo = (W + pl + pr - k) // stride + 1
+    HWo, Mo = Ho * Wo, N * Ho * Wo
+    Ce, Co, Cs = sp.cexp, sp.cout, sp.cse
+    assert x.dtype == torch.float16 and not (sp.skip and lazy_in is not None)
+    dwm = blk._depthwise_conv
+    sf = sp.sf_norm is not None
+    bn1 = K.EvalBN(blk._bn1, 1)
+    bn2 = K.EvalBN(blk._bn2, 0)
+    if sp.expand != 1:
+        We = blk._expand_conv.weight.view(Ce, Cin)
+        e = K.gemm_nt(x.view(M, Cin), We).view(N, H, W, Ce)
+        src, src_bn = e, K.EvalBN(blk._bn0, 1)
+    else:
+        We = None
+        src, src_bn = x, (lazy_in.bn if lazy_in is not None else None)
+    spat = K.dwtile_fwd(src, wt, k, pt, pl, Ho, Wo, bn=src_bn, stride=stride)
+    if sf:
+        S = H
+        s_f, s_i = _fft_scales(S, sp.sf_norm)
+        alpha = dwm.sf_coef
+        Wf = dwm.freq_conv.weight.view(2 * Ce, 2 * Ce)
+        xf, _ = K.rfft2_ex(src, s_f, 1.0, bn=src_bn)
+        xf_shape = xf.shape
+        yf = K.gemm_nt(xf.view(-1, 2 * Ce), Wf).view(xf_shape)
+        if stride == 1:
+            d, _ = K.irfft2_mix(yf, s_i, spat, alpha, None)
+        else:
+            d = K.sfmix_fwd(spat, K.irfft2(yf, s_i, 1.0), alpha, True)
+        del xf, yf, spat
+    else:
+        d = spat
+    pool = K.zeros64(N * Ce, x)
+    K.colsum_bn(d, bn1, N, HWo, pool)
+    wr2, we2 = blk._se_reduce.weight.view(Cs, Ce), blk._se_expand.weight.view(Ce, Cs)
+    s1 = K.fc_fwd_d(pool, 1.0 / HWo, wr2, blk._se_reduce.bias, N)
+    s2 = K.fc_fwd(s1, we2, blk._se_expand.bias, 1)
+    Wp = blk._project_conv.weight.view(Co, Ce)
+    p = K.gemm_nt(K.se_scale_bn(d, bn1, s2, N, HWo).view(Mo, Ce), Wp)
+    out = K.residual_bn(p.view(N, Ho, Wo, Co), bn2, None, 1.0, x if sp.skip else None, N, HWo)
+    del pool, p
+
+    def bwd():
+        dout = tape.pop_grad(out)
+        if dout is None:
+            return
+        if not (dout.is_contiguous() and dout.shape == out.shape):
+            dout = dout.reshape(out.shape).contiguous()
+        assert dout.dtype == torch.float16
+        # ---- BN2: the constant applied in a pass over the thin tensor; project conv's data gradient on the half GEMM
+        probe = HALF_GRAD_PROBE
+        dp = K.bn_eval_bwd(dout, None, bn2, 1, Mo)
+        dc = K.gemm_nn(dp.view(Mo, Co), Wp).view(N, Ho, Wo, Ce)
+        if probe is not None:
+            for nm, t in (("dout", dout), ("dp", dp), ("dc", dc)):
+                probe(blk, nm, t)
+        # ---- SE gate, the two FCs (data gradient only), then gate + swish + BN1 in one pass over (dc, d)
+        dgate = K.zeros64(N * Ce, x)
+        K.coldot_bn_eval(dc, d, bn1, N, HWo, dgate)
+        dpool = K.se_bwd(dgate, s2, s1, we2, wr2, None, 1.0 / HWo, need_w=False)[0]
+        dd = K.se_scale_bwd_bn_eval(dc, d, bn1, s2, dpool, 1.0 / HWo, N, HWo)
+        del dc
+        if probe is not None:
+            probe(blk, "dd", dd)
+        # ---- SF: frequency branch sigmoid(a) dd through the adjoint transforms and the spectral data-gradient GEMM (stride 2:
+        # through the 2 x 2 mean first); spatial branch (1 - sigmoid(a)) dd by the dgrad kernel's gate mode 2; the gate is frozen
+        g_alpha, g_mode, da_f = None, 0, None
+        if sf:
+            dfr = dd if stride == 1 else K.sfmix_pool_bwd(dd)
+            dyf, _ = K.rfft2_ex(dfr, s_i, 2.0, gate_alpha=alpha, gate_mode=1)
+            dxf = K.gemm_nn(dyf.view(-1, 2 * Ce), Wf).view(xf_shape)
+            da_f = K.irfft2(dxf, s_f, 0.5)
+            if probe is not None:
+                for nm, t in (("dyf", dyf), ("dxf", dxf), ("da_f", da_f)):
+                    probe(blk, nm, t)
+            del dfr, dyf, dxf
+            g_alpha, g_mode = alpha, 2
+        # ---- depthwise data gradient through BN0 (block 0: the stem's BatchNorm) + swish in one tiled pass, then the expand conv
+        if src_bn is not None:
+            de = K.dwtile_dgrad_eval(dd, wt, k, pt, pl, src, src_bn, g_alpha, g_mode, da_f, stride)
+            if probe is not None:
+                probe(blk, "de", de)
+            if lazy_in is not None:
+                lazy_in.backward(de)
+                return
+            if sp.skip and tape.watch is None and getattr(dout, "_ud_owned", False):
+                dx = K.gemm_nn(de.view(M, Ce), We, out=dout.view(M, Cin), accumulate=True).view(x.shape)      # + the skip gradient
+            else:
+                dx = K.gemm_nn(de.view(M, Ce), We).view(x.shape)
+                if sp.skip:
+                    dx = K.axpby(dx, 1.0, dout, 1.0, out=dx)
+        else:
+            add, skip_done = da_f, not sp.skip
+            if sp.skip and add is None:
+                add, skip_done = dout, True
+            dx = K.dwtile_bwd_data(dd, wt, k, pt, pl, H, W, g_alpha, g_mode, add, stride=stride)
+            if not skip_done:
+                dx = K.axpby(dx, 1.0, dout, 1.0, out=dx)
+        if probe is not None:
+            probe(blk, "dx", dx)
+        dx._ud_owned = True
+        tape.add_grad(x, dx)
+    tape.record(bwd)
+    return out
