@@ -462,6 +462,58 @@ int ud_attack_step_l2(float* x_adv, const float* g, const double* gss, int N, lo
 int ud_attack_project_l2(float* x_adv, const float* x0, const double* dss, int N, long per, float eps, float lo, float hi,
                          ud_stream_t stream);
 
+/* ---- Auto-PGD (csrc/apgd.hip; unidefense_amd/attack.py: APGDRunner) -------------------------------------------------
+ * Per-sample control state on the device, so that one iteration is a static launch sequence inside a captured graph:
+ *   ist [5][N] int32 : rows UD_APGD_I_K (iteration index), _CNT (rises of f since the last checkpoint), _HALVED (eta was
+ *                      halved at the previous checkpoint), _IMPROVED, _RESET (what the update of this iteration obeys)
+ *   fst [5][N] fp32  : rows UD_APGD_F_PREV (f of the previous iteration), _BEST, _CKPT (f_best at the last checkpoint), _ETA, _A
+ *   history [steps + 1][N] fp32 : row k = f_k, row steps = f of the closing evaluation
+ * ud_apgd_control: f [N] fp32 = the per-sample objective at the current point.  One thread per sample; with k = ist[K][n]:
+ *   k == 0: f_best = f_ckpt = f, eta = eta0, improved = 1, cnt = 0, halved = 0, a = 1
+ *   k  > 0: cnt += (f > f_prev); improved = f > f_best (f_best updated); a = alpha
+ *   k == ck_w[j]: c1 = cnt < ck_thr[j]; c2 = !halved && f_ckpt == f_best; c1 || c2: eta /= 2, reset = 1, a = 1, halved = 1,
+ *                 else halved = 0; then f_ckpt = f_best, cnt = 0          (reset = 0 where no checkpoint fired)
+ *   then f_prev = f, history[k][n] = f, ist[K][n] = k + 1.  k outside [0, steps) writes nothing.  The caller zeroes row
+ *   UD_APGD_I_K to start a run.  A NaN f compares false everywhere.  ck_w (strictly rising, in [1, steps - 1]) and ck_thr
+ *   (ceil(rho * window), so that c1 is an integer comparison) are HOST arrays of n_ck <= UD_APGD_MAX_CHECKPOINTS entries,
+ *   passed by value to the kernel.  closing != 0: only improved = f > f_best (f_best updated) and history[steps][n] = f.
+ * ud_apgd_update_linf: one pass over contiguous fp32 [N][per] tensors obeying (improved, reset, eta, a) of each sample:
+ *   improved: (x_best, g_best) <- (x, g);  (src, gs) = (x_best, g_best) if reset else (x, g);
+ *   z = P(src + eta sign(gs));  x <- z if a == 1 else P((src + a (z - src)) + (1 - a) (src - x_prev));  x_prev <- src
+ *   with P(v) = clamp(clamp(v, x0 - eps, x0 + eps), lo, hi), one fp32 rounding per operation in exactly this order (bitwise
+ *   the torch fp32 expression), sign(0) = 0, a NaN gradient element gives a NaN there.
+ * ud_apgd_keep: dst[n] <- src[n] for the samples with flag[n] != 0 (flag [N] int32).
+ * L2 (per-sample factors, sums and new values formed in double, one rounding to fp32, as ud_attack_step_l2):
+ *   ud_apgd_step_l2   : gss[n] = |g[n]|^2.  improved: (x_best, g_best, gss_best) <- (x, g, gss); source selection as above
+ *                       with x <- src; z <- src + eta gs / max(|gs|, 1e-12)   (z is projected by ud_sample_sumsq +
+ *                       ud_attack_project_l2 next)
+ *   ud_apgd_combine_l2: x holds src, z the projected step: x <- z if a == 1 else src + a (z - src) + (1 - a)(src - x_prev);
+ *                       x_prev <- src
+ *   ud_apgd_project_l2: ud_attack_project_l2 on the samples with a != 1 only; a sample with a == 1 is left as it is.
+ * UD_EINVAL before any HIP call: a NULL pointer, N < 1, per < 1, steps < 1, eps < 0 or NaN, lo > hi or NaN, eta0 < 0 or NaN,
+ * alpha outside (0, 1], a checkpoint table that is too long, not rising or outside [1, steps - 1]. */
+#define UD_APGD_MAX_CHECKPOINTS 16
+#define UD_APGD_I_K 0
+#define UD_APGD_I_CNT 1
+#define UD_APGD_I_HALVED 2
+#define UD_APGD_I_IMPROVED 3
+#define UD_APGD_I_RESET 4
+#define UD_APGD_F_PREV 0
+#define UD_APGD_F_BEST 1
+#define UD_APGD_F_CKPT 2
+#define UD_APGD_F_ETA 3
+#define UD_APGD_F_A 4
+int ud_apgd_control(const float* f, int* ist, float* fst, float* history, int N, int steps, const int* ck_w,
+                    const int* ck_thr, int n_ck, float eta0, float alpha, int closing, ud_stream_t stream);
+int ud_apgd_update_linf(float* x, float* x_prev, float* x_best, float* g_best, const float* x0, const float* g, const int* ist,
+                        const float* fst, int N, long per, float eps, float lo, float hi, ud_stream_t stream);
+int ud_apgd_keep(float* dst, const float* src, const int* flag, int N, long per, ud_stream_t stream);
+int ud_apgd_step_l2(float* x, float* z, float* x_best, float* g_best, double* gss_best, const float* g, const double* gss,
+                    const int* ist, const float* fst, int N, long per, ud_stream_t stream);
+int ud_apgd_combine_l2(float* x, float* x_prev, const float* z, const float* fst, int N, long per, ud_stream_t stream);
+int ud_apgd_project_l2(float* x, const float* x0, const double* dss, const float* fst, int N, long per, float eps, float lo,
+                       float hi, ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

@@ -1,4 +1,5 @@
-"""Graph-replayed input gradients and FGSM / PGD attacks on a frozen eval-mode detector: InputGradRunner, AttackRunner.
+"""Graph-replayed input gradients and FGSM / PGD / Auto-PGD attacks on a frozen eval-mode detector: InputGradRunner,
+AttackRunner, APGDRunner.
 
 Both follow InferenceRunner's life cycle (unidefense_amd/infer.py): call 1 runs eagerly (it settles the on-line GEMM tuner and
 every lazily made workspace of the forward AND the backward for the shape), call 2 captures one hipGraph on static buffers,
@@ -19,6 +20,11 @@ form).  The stem's data gradient, decoder, attention, head and objective stay fp
 power of two, default 1024: 99.95 % of the unscaled x-gradient's entries lie below fp16's smallest normal) before the backward and
 the fp32 result divided by it inside the graph: runner.g is unscaled; a non-finite gradient stays non-finite.  The eager
 model(x), the fp32 runners and the training step do not change.
+
+APGDRunner (Auto-PGD, APGD-CE) has the same life cycle next to AttackRunner, which it leaves as it is: its graph holds one
+iteration whose per-sample control — which samples improved, whose step size is halved, who restarts from their best point —
+is device state written by csrc/apgd.hip (ud_apgd_control: one thread per sample; ud_apgd_update_linf: one pass), plus a
+forward-only graph that scores the last point; the best point per sample over all iterations and restarts is returned.
 """
 import contextlib
 import math
@@ -319,3 +325,236 @@ def attack_runner(model, batch, size, norm="linf", eps=None, steps=10, step=None
     return _cached(model, "_ud_attack_runners", key,
                    lambda: AttackRunner(model, batch, size, norm, eps, steps, step, random_start, targeted, clip, objective,
                                         precision, grad_scale))
+
+
+# ---- Auto-PGD (APGD-CE, Croce & Hein 2020): per-sample step control, restarts from the best point, best-of ----------------------
+_APGD_P1 = 22                        # hundredths of `steps`: the first checkpoint; the gaps shrink by 3 down to 6
+
+
+def apgd_checkpoints(steps):
+    """The checkpoint iterations for `steps` iterations, in integer arithmetic: p_0 = 0, p_1 = 22, p_{j+1} = p_j +
+    max(p_j - p_{j-1} - 3, 6) hundredths; w_j = ceil(p_j steps / 100), deduplicated, those in [1, steps - 1]."""
+    steps = int(steps)
+    out, prev, p = [], 0, _APGD_P1
+    while True:
+        w = (p * steps + 99) // 100
+        if w > steps - 1:
+            return tuple(out)
+        if w >= 1 and (not out or w != out[-1]):
+            out.append(w)
+        prev, p = p, p + max(p - prev - 3, 6)
+
+
+def apgd_table(steps, rho):
+    """(checkpoints, thresholds): checkpoint w_j's window is L_j = w_j - w_{j-1} (w_0 = 0) and its first condition
+    cnt < rho L_j is, for an integer cnt, cnt < ceil(rho L_j): the integer the control kernel compares with."""
+    ws = apgd_checkpoints(steps)
+    thr = tuple(int(math.ceil(float(rho) * (w - (ws[j - 1] if j else 0)))) for j, w in enumerate(ws))
+    return ws, thr
+
+
+def cross_entropy_each(out, y):
+    """cross_entropy_sum's terms: each sample's classification loss, [batch]"""
+    cls = out["cls_out"]
+    if cls.shape[1] == 1:
+        return F.binary_cross_entropy_with_logits(cls.squeeze(1), y.to(cls.dtype), reduction="none")
+    return F.cross_entropy(cls, y, reduction="none")
+
+
+class APGDRunner(_GradRunnerBase):
+    """runner = APGDRunner(model, batch, size, norm="linf", eps=..., steps=100, restarts=1, ...); x_adv = runner(x, y[, generator]).
+
+    Auto-PGD on the per-sample objective f (objective="cross_entropy": each sample's loss; or a callable (out, y) -> [batch];
+    targeted=True ascends -f).  Per sample: step size eta = 2 eps, halved at the checkpoints apgd_checkpoints(steps) when f rose
+    in fewer than rho of the window's iterations, or when neither eta nor the best f changed since the previous checkpoint; a
+    halving restarts the sample from its best point; momentum alpha; direction and projection as AttackRunner's (linf: sign, box,
+    clip; l2: g / |g|, ball, clip).  One hipGraph holds ONE iteration — forward, f, d sum(f) / dx, the per-sample control
+    (ud_apgd_control: device state, no host round trip) and the update — and a restart replays it `steps` times, then replays
+    a forward-only graph that scores the last point.  Restart 0 starts at clamp(x, clip) (random_start: at random); every
+    later restart starts at random (linf: uniform in the box; l2: on the sphere of radius eps), drawn by torch outside the graph
+    from `generator`; the per-sample best over all iterations and restarts is kept.
+
+    Static buffers that the next call overwrites: x_adv (returned), best_loss [N] (f at x_adv), loss0 [N] (f at restart 0's
+    start), eta [N] and history [steps + 1, N] (step sizes and f_k of the LAST restart; history[steps] is the closing
+    evaluation), g (the last iteration's gradient), out (the last iteration's forward output); args: the resolved arguments.
+    precision / grad_scale: as InputGradRunner."""
+    _what = "APGDRunner"
+
+    def __init__(self, model, batch, size, norm="linf", eps=None, steps=100, restarts=1, random_start=False, rho=0.75, alpha=0.75,
+                 targeted=False, clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
+        if norm not in NORMS:
+            raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
+        if eps is None or not float(eps) >= 0.0:
+            raise ValueError(f"eps must be >= 0, got {eps!r}")
+        if int(steps) != steps or steps < 1:
+            raise ValueError(f"steps must be an integer >= 1, got {steps!r}")
+        if int(restarts) != restarts or restarts < 1:
+            raise ValueError(f"restarts must be an integer >= 1, got {restarts!r}")
+        if not 0.0 < float(rho) <= 1.0:
+            raise ValueError(f"rho must be in (0, 1], got {rho!r}")
+        if not 0.0 < float(alpha) <= 1.0:
+            raise ValueError(f"alpha must be in (0, 1], got {alpha!r}")
+        if len(clip) != 2 or not float(clip[0]) < float(clip[1]):
+            raise ValueError(f"clip must be (lo, hi) with lo < hi, got {clip!r}")
+        self._init_model(model, batch, size, objective, precision, grad_scale)
+        self.objective = objective if callable(objective) else cross_entropy_each
+        self.norm, self.eps, self.steps, self.restarts = norm, float(eps), int(steps), int(restarts)
+        self.random_start, self.targeted = bool(random_start), bool(targeted)
+        self.rho, self.alpha = float(rho), float(alpha)
+        self.lo, self.hi = float(clip[0]), float(clip[1])
+        self.checkpoints, self._thr = apgd_table(self.steps, self.rho)
+        self.args = {"method": "apgd", "norm": norm, "eps": self.eps, "steps": self.steps, "restarts": self.restarts,
+                     "random_start": self.random_start, "rho": self.rho, "alpha": self.alpha, "targeted": self.targeted,
+                     "clip": (self.lo, self.hi),
+                     "objective": objective if isinstance(objective, str) else getattr(objective, "__name__", repr(objective)),
+                     "precision": self.precision, "grad_scale": self.grad_scale}
+        self.closing_graph = None
+        self.x0 = self.x = self.x_adv = self.y = None
+
+    def _buffers(self, x, y):
+        from . import kernels as K
+        n, dev = self.batch, self.device
+        self.x0 = x.detach().clone().contiguous()
+        self.x = self.x0.clone().requires_grad_()                 # the static leaf: the current iterate
+        self.x_prev, self.x_best, self.g_best = (torch.zeros_like(self.x0) for _ in range(3))
+        self.x_adv = torch.zeros_like(self.x0)
+        self.y = y.detach().clone()
+        self.ist, self.fst = K.apgd_state(n, dev)
+        self.history = torch.zeros(self.steps + 1, n, dtype=torch.float32, device=dev)
+        self.best_loss = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.loss0 = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.eta = self.fst[K.APGD_F["eta"]]
+        self._f_best = self.fst[K.APGD_F["f_best"]]
+        self._improved = self.ist[K.APGD_I["improved"]]
+        if self.norm == "l2":
+            per = 3 * self.size * self.size
+            self._z = torch.zeros_like(self.x0)
+            self._gss, self._gss_best, self._dss = (torch.zeros(n, dtype=torch.float64, device=dev) for _ in range(3))
+            self._ws = torch.zeros(max(K.sample_sumsq_ws_bytes(n, per) // 8, 1), dtype=torch.float64, device=dev)
+
+    def _each(self, out):
+        f = self.objective(out, self.y)
+        if not isinstance(f, torch.Tensor) or tuple(f.shape) != (self.batch,):
+            raise ValueError(f"APGDRunner's objective must return a [{self.batch}] tensor, one value per sample, got "
+                             f"{tuple(f.shape) if isinstance(f, torch.Tensor) else type(f).__name__}")
+        return -f if self.targeted else f
+
+    def _nodes(self):
+        return _eval_nodes(self.model, half=True) if self.half else contextlib.nullcontext()
+
+    def _iteration(self):
+        """one APGD iteration on the static buffers: what the graph holds"""
+        from . import kernels as K
+        with self._nodes():
+            out = self.model(self.x)
+            f = self._each(out)
+            g, = torch.autograd.grad(f.sum() * self.grad_scale if self.half else f.sum(), self.x)
+        g = g.contiguous()
+        if self.half:                                          # unscaled in place, inside the graph when capturing
+            K.axpby(g, 1.0 / self.grad_scale, out=g)
+        self.g, self.out = g, _detached(out)
+        K.apgd_control(f.detach().float().contiguous(), self.ist, self.fst, self.history, self.steps, self.checkpoints, self._thr,
+                       2.0 * self.eps, self.alpha)
+        if self.norm == "linf":
+            K.apgd_update_linf(self.x, self.x_prev, self.x_best, self.g_best, self.x0, g, self.ist, self.fst, self.eps, self.lo,
+                               self.hi)
+        else:
+            K.sample_sumsq(g, None, out=self._gss, ws=self._ws)
+            K.apgd_step_l2(self.x, self._z, self.x_best, self.g_best, self._gss_best, g, self._gss, self.ist, self.fst)
+            K.sample_sumsq(self._z, self.x0, out=self._dss, ws=self._ws)
+            K.attack_project_l2(self._z, self.x0, self._dss, self.eps, self.lo, self.hi)
+            K.apgd_combine_l2(self.x, self.x_prev, self._z, self.fst)
+            K.sample_sumsq(self.x, self.x0, out=self._dss, ws=self._ws)
+            K.apgd_project_l2(self.x, self.x0, self._dss, self.fst, self.eps, self.lo, self.hi)
+
+    def _closing(self):
+        """the closing evaluation: forward only at the last point; if it beats the best, it becomes the best"""
+        from . import kernels as K
+        with torch.no_grad(), self._nodes():
+            f = self._each(self.model(self.x))
+        K.apgd_control(f.float().contiguous(), self.ist, self.fst, self.history, self.steps, self.checkpoints, self._thr,
+                       2.0 * self.eps, self.alpha, closing=True)
+        K.apgd_keep(self.x_best, self.x, self._improved)
+
+    def _start(self, restart, generator):
+        """the start point of a restart, drawn outside the graph; the iteration counters back to 0"""
+        from . import kernels as K
+        with torch.no_grad():
+            x0 = self.x0
+            if restart == 0 and not self.random_start:
+                s = x0.clamp(self.lo, self.hi)
+            else:
+                gdev = generator.device if generator is not None else self.device
+                if self.norm == "linf":
+                    u = torch.rand(self.shape, generator=generator, device=gdev, dtype=torch.float32).to(self.device)
+                    s = (x0 + (u * 2.0 - 1.0) * self.eps).clamp_(self.lo, self.hi)
+                else:
+                    n = torch.randn(self.shape, generator=generator, device=gdev, dtype=torch.float32).to(self.device)
+                    nrm = n.flatten(1).norm(dim=1).clamp_min(1e-12).view(-1, 1, 1, 1)
+                    s = (x0 + n * (self.eps / nrm)).clamp_(self.lo, self.hi)
+            self.x.copy_(s)
+            self.x_prev.copy_(s)
+            self.ist[K.APGD_I["k"]].zero_()
+
+    def _merge(self, restart):
+        """the per-sample maximum of f_best over the restarts so far, outside the graph"""
+        from . import kernels as K
+        with torch.no_grad():
+            if restart == 0:
+                self.loss0.copy_(self.history[0])
+                self.x_adv.copy_(self.x_best)
+                self.best_loss.copy_(self._f_best)
+            else:
+                better = (self._f_best > self.best_loss).to(torch.int32)
+                K.apgd_keep(self.x_adv, self.x_best, better)
+                self.best_loss.copy_(torch.where(better.bool(), self._f_best, self.best_loss))
+
+    def __call__(self, x, y, generator=None):
+        self._check(x, y)
+        self.calls += 1
+        with torch.enable_grad():
+            if self.calls == 1:                                   # eager warm-up: the same launches, a valid attack
+                self._buffers(x, y)
+            elif self.graph is None:
+                torch.cuda.synchronize(self.device)
+                g, c = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+                with frozen(self.model):
+                    with torch.cuda.graph(g):
+                        self._iteration()
+                    with torch.cuda.graph(c):
+                        self._closing()
+                self.graph, self.closing_graph = g, c
+            with torch.no_grad():
+                self.x0.copy_(x)
+                self.y.copy_(y)
+            for r in range(self.restarts):
+                self._start(r, generator)
+                if self.graph is None:
+                    with frozen(self.model):
+                        for _ in range(self.steps):
+                            self._iteration()
+                        self._closing()
+                else:
+                    for _ in range(self.steps):
+                        self.graph.replay()
+                    self.closing_graph.replay()
+                self._merge(r)
+        return self.x_adv
+
+
+def apgd_key(batch, size, norm="linf", eps=None, steps=100, restarts=1, random_start=False, rho=0.75, alpha=0.75, targeted=False,
+             clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
+    return _precision_key((int(batch), int(size), norm, eps, steps, restarts, bool(random_start), rho, alpha, bool(targeted),
+                           tuple(clip), objective), precision, grad_scale)
+
+
+def apgd_runner(model, batch, size, norm="linf", eps=None, steps=100, restarts=1, random_start=False, rho=0.75, alpha=0.75,
+                targeted=False, clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
+    """The model's APGDRunner for the full argument tuple, made on first use; at most _MAX_RUNNERS are kept, in a dictionary of
+    their own (the other runners' caches are untouched)."""
+    _check_precision(model, precision)
+    key = apgd_key(batch, size, norm, eps, steps, restarts, random_start, rho, alpha, targeted, clip, objective, precision,
+                   grad_scale)
+    return _cached(model, "_ud_apgd_runners", key,
+                   lambda: APGDRunner(model, batch, size, norm, eps, steps, restarts, random_start, rho, alpha, targeted, clip,
+                                      objective, precision, grad_scale))

@@ -259,7 +259,9 @@ class TrainEngine(AbstractEngine):
         "adv": the same keys on x_adv, "attack": the resolved arguments, precision and grad_scale included}.  The attack dict's
         "precision": "fp16" (UDEB4; optional "grad_scale") runs the attack's frozen pass in half storage; inference_graph /
         inference_precision keep their meaning for the two scoring forwards.  Data parallel: each rank attacks its own batches on the un-wrapped model (a
-        frozen pass has no collective of its own) and the scores are gathered over the ranks as in _score."""
+        frozen pass has no collective of its own) and the scores are gathered over the ranks as in _score.
+        "method": "apgd" in the attack dict selects Auto-PGD (the model's APGDRunner: norm, eps, steps, restarts, rho, alpha, ...;
+        an optional "seed" seeds the generator of its random restarts); "pgd", the default, is the fixed-step AttackRunner."""
         from .metrics import gather_scores
         attack = attack if attack is not None else self.config["config"].get("attack")
         if not attack:
@@ -277,13 +279,27 @@ class TrainEngine(AbstractEngine):
                 out = self.model(x)
             return torch.softmax(out["cls_out"], 1)[:, 0]
 
+        attack = dict(attack)
+        method = attack.pop("method", "pgd")
+        if method not in ("pgd", "apgd"):
+            raise ValueError(f"attack method must be 'pgd' or 'apgd', got {method!r}")
+        generator = None
+        if method == "apgd":                                 # Auto-PGD (APGDRunner): "seed" makes the random restarts reproducible
+            seed = attack.pop("seed", None)
+            if seed is not None:
+                generator = torch.Generator(device=self.device).manual_seed(int(seed))
+
         clean, adv, labels, runner = [], [], [], None
         for step in range(1, batches + 1):
             xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
             x, y = torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
             clean.append(score(x))
-            runner = self.model_without_ddp.attack_runner(x.shape[0], x.shape[-1], **attack)
-            adv.append(score(runner(x, y)))
+            if method == "apgd":
+                runner = self.model_without_ddp.apgd_runner(x.shape[0], x.shape[-1], **attack)
+                adv.append(score(runner(x, y, generator)))
+            else:
+                runner = self.model_without_ddp.attack_runner(x.shape[0], x.shape[-1], **attack)
+                adv.append(score(runner(x, y)))
             labels.append(y)
         labels = torch.cat(labels)
         return {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"),

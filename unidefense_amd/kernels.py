@@ -1472,6 +1472,98 @@ def attack_project_l2(x_adv, x0, dss, eps, lo, hi):
     return x_adv
 
 
+# ---- Auto-PGD (csrc/apgd.hip): per-sample control state ist [5, N] int32 / fst [5, N] fp32, rows as in the header -------------
+APGD_MAX_CHECKPOINTS = 16
+APGD_I = {"k": 0, "cnt": 1, "halved": 2, "improved": 3, "reset": 4}
+APGD_F = {"f_prev": 0, "f_best": 1, "f_ckpt": 2, "eta": 3, "a": 4}
+
+
+def _chk_apgd_state(ist, fst, N):
+    if not (ist.is_cuda and ist.dtype == torch.int32 and ist.is_contiguous() and tuple(ist.shape) == (5, N)):
+        raise ValueError(f"ist must be a contiguous int32 CUDA tensor [5, {N}], got {ist.dtype} {ist.device} {tuple(ist.shape)}")
+    _chk(fst)
+    if tuple(fst.shape) != (5, N):
+        raise ValueError(f"fst must be [5, {N}], got {tuple(fst.shape)}")
+
+
+def apgd_state(N, device):
+    """(ist, fst): zeroed control state for N samples"""
+    return (torch.zeros(5, N, dtype=torch.int32, device=device), torch.zeros(5, N, dtype=torch.float32, device=device))
+
+
+def apgd_control(f, ist, fst, history, steps, ck_w, ck_thr, eta0, alpha, closing=False):
+    """One step of the per-sample APGD state machine on f [N] fp32 (closing: the keep-best decision of the last point only);
+    ck_w / ck_thr: the checkpoint iterations and their integer thresholds ceil(rho window), passed by value."""
+    _chk(f, history)
+    N = f.numel()
+    _chk_apgd_state(ist, fst, N)
+    if tuple(history.shape) != (int(steps) + 1, N):
+        raise ValueError(f"history must be [{int(steps) + 1}, {N}], got {tuple(history.shape)}")
+    n = len(ck_w)
+    if len(ck_thr) != n or n > APGD_MAX_CHECKPOINTS:
+        raise ValueError(f"checkpoint table: {n} iterations, {len(ck_thr)} thresholds, at most {APGD_MAX_CHECKPOINTS}")
+    arr = C.c_int * max(n, 1)
+    _call("ud_apgd_control", _p(f), _p(ist), _p(fst), _p(history), N, int(steps), arr(*[int(w) for w in ck_w]),
+          arr(*[int(t) for t in ck_thr]), n, float(eta0), float(alpha), int(bool(closing)), _stream())
+
+
+def apgd_update_linf(x, x_prev, x_best, g_best, x0, g, ist, fst, eps, lo, hi):
+    """In place on x, x_prev, x_best, g_best: the L-infinity APGD update (include/unidefense_hip.h), bitwise the torch fp32
+    expression evaluated operation by operation."""
+    _chk_same(x, x_prev, x_best, g_best, x0, g)
+    N = x.shape[0]
+    _chk_apgd_state(ist, fst, N)
+    _call("ud_apgd_update_linf", _p(x), _p(x_prev), _p(x_best), _p(g_best), _p(x0), _p(g), _p(ist), _p(fst), N,
+          x.numel() // N, float(eps), float(lo), float(hi), _stream())
+    return x
+
+
+def apgd_keep(dst, src, flag):
+    """dst[n] <- src[n] for the samples with flag[n] != 0 (flag [N] int32)"""
+    _chk_same(dst, src)
+    N = dst.shape[0]
+    if not (flag.is_cuda and flag.dtype == torch.int32 and flag.is_contiguous() and flag.numel() == N):
+        raise ValueError(f"flag must be a contiguous int32 CUDA tensor of {N} values, got {flag.dtype} {tuple(flag.shape)}")
+    _call("ud_apgd_keep", _p(dst), _p(src), _p(flag), N, dst.numel() // N, _stream())
+    return dst
+
+
+def apgd_step_l2(x, z, x_best, g_best, gss_best, g, gss, ist, fst):
+    """The L2 APGD step: keep-best copy (with |g_best|^2 beside g_best), source selection (x <- src) and
+    z <- src + eta gs / max(|gs|, 1e-12); gss [N] float64 = sample_sumsq(g)."""
+    _chk_same(x, z, x_best, g_best, g)
+    N = x.shape[0]
+    _chk_f64(gss, N)
+    _chk_f64(gss_best, N)
+    _chk_apgd_state(ist, fst, N)
+    _call("ud_apgd_step_l2", _p(x), _p(z), _p(x_best), _p(g_best), _p(gss_best), _p(g), _p(gss), _p(ist), _p(fst), N,
+          x.numel() // N, _stream())
+    return z
+
+
+def apgd_combine_l2(x, x_prev, z, fst):
+    """x holds src, z the projected step: x <- z where a == 1, else src + a (z - src) + (1 - a)(src - x_prev); x_prev <- src"""
+    _chk_same(x, x_prev, z)
+    N = x.shape[0]
+    _chk(fst)
+    if tuple(fst.shape) != (5, N):
+        raise ValueError(f"fst must be [5, {N}], got {tuple(fst.shape)}")
+    _call("ud_apgd_combine_l2", _p(x), _p(x_prev), _p(z), _p(fst), N, x.numel() // N, _stream())
+    return x
+
+
+def apgd_project_l2(x, x0, dss, fst, eps, lo, hi):
+    """attack_project_l2 on the samples with a != 1; the others are left exactly as they are"""
+    _chk_same(x, x0)
+    N = x.shape[0]
+    _chk_f64(dss, N)
+    _chk(fst)
+    if tuple(fst.shape) != (5, N):
+        raise ValueError(f"fst must be [5, {N}], got {tuple(fst.shape)}")
+    _call("ud_apgd_project_l2", _p(x), _p(x0), _p(dss), _p(fst), N, x.numel() // N, float(eps), float(lo), float(hi), _stream())
+    return x
+
+
 def conv_gather_wgrad(a, x, g):
     """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)]."""
     _chk(a, x)

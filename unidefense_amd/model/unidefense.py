@@ -286,6 +286,13 @@ class UniDefenseModelEb4(nn.Module):
         from ..attack import attack_runner
         return attack_runner(self, batch, size, **kwargs)
 
+    def apgd_runner(self, batch, size, **kwargs):
+        """The graph-replayed Auto-PGD (APGD-CE) attack for [batch, 3, size, size] inputs (unidefense_amd/attack.py: APGDRunner;
+        kwargs: norm, eps, steps, restarts, random_start, rho, alpha, targeted, clip, objective, precision, grad_scale), cached per
+        argument tuple in a dictionary of its own."""
+        from ..attack import apgd_runner
+        return apgd_runner(self, batch, size, **kwargs)
+
     # -- pretrained backbone (model/efficientnet/utils.py:589-634): missing sf_coef / freq_conv keys tolerated
     def load_backbone_weights(self, path):
         sd = torch.load(path, map_location="cpu")
