@@ -514,6 +514,41 @@ int ud_apgd_combine_l2(float* x, float* x_prev, const float* z, const float* fst
 int ud_apgd_project_l2(float* x, const float* x0, const double* dss, const float* fst, int N, long per, float eps, float lo,
                        float hi, ud_stream_t stream);
 
+/* ---- Square attack, L-infinity (csrc/square.hip; unidefense_amd/attack.py: SquareRunner) ------------------------------
+ * Score-based black-box search: proposal j (j = 1..steps) overwrites one side[j-1] x side[j-1] window of the trial image
+ * with x0 +- eps per channel; the control keeps it where the objective f fell.  Device state, so that one iteration
+ * (propose, forward, f, control) is a static launch sequence inside a captured graph:
+ *   ist [4][N] int32 : rows UD_SQUARE_I_K (iteration index), _ACCEPTED (the last proposal was kept), _ACTIVE (the sample is
+ *                      still searched), _QUERIES (forwards that counted for the sample)
+ *   fst [1][N] fp32  : row UD_SQUARE_F_BEST (the lowest f so far)
+ *   history [steps + 1][N] fp32 : row k = f_k;  decisions [steps + 1][N] int32 : row k = accepted_k (row 0 is 0)
+ *   draw tables      : side [steps] int32 (1 <= side <= size), dh, dw [steps][N] int32 (0 <= dh, dw <= size - side),
+ *                      dsign [steps][N][3] fp32 (+-1); row j - 1 belongs to proposal j.  A row that breaks these bounds is
+ *                      skipped by the kernel, never followed out of the image.
+ * ud_square_propose: x_try, x_best, x0 fp32 [N][3][size][size]; with k = ist[K][n], ONE launch does
+ *   resolve (2 <= k <= steps + 1): on the window W' of proposal k - 1: accepted ? x_best[W'] = x_try[W'] : x_try[W'] = x_best[W']
+ *   write   (1 <= k <= steps, closing == 0): on the window W of proposal k: x_try[c][W] = min(max(x0[c][W] + dsign[c] eps, lo), hi)
+ *   (one fp32 add, NaN-transparent clamps: bitwise the torch fp32 expression).  Every element of W' u W is owned by exactly one
+ *   thread, which forms the settled value and then stores x_best and x_try: identical, overlapping and disjoint consecutive
+ *   windows need no ordering between threads.  Only the windows' bytes are touched.  closing != 0: resolve only.
+ * ud_square_control: f [N] fp32 = the objective at x_try.  One thread per sample; with k = ist[K][n]:
+ *   k == 0          : f_best = f, accepted = 0, queries = 1, active = early_stop ? f_best > 0 : 1
+ *   1 <= k <= steps : queries += active; accepted = active && f < f_best (f_best follows); active as above
+ *   then history[k][n] = f, decisions[k][n] = accepted, ist[K][n] = k + 1.  k outside [0, steps] writes nothing.  The caller
+ *   zeroes row UD_SQUARE_I_K to start a run.  A NaN f compares false everywhere and stays in history.
+ * UD_EINVAL before any HIP call: a NULL pointer, N < 1 or > 65535, size < 1 or > 32768, steps < 1, eps < 0 or NaN, lo > hi or
+ * NaN. */
+#define UD_SQUARE_I_K 0
+#define UD_SQUARE_I_ACCEPTED 1
+#define UD_SQUARE_I_ACTIVE 2
+#define UD_SQUARE_I_QUERIES 3
+#define UD_SQUARE_F_BEST 0
+int ud_square_propose(float* x_try, float* x_best, const float* x0, const int* ist, const int* side, const int* dh,
+                      const int* dw, const float* dsign, int N, int size, int steps, float eps, float lo, float hi, int closing,
+                      ud_stream_t stream);
+int ud_square_control(const float* f, int* ist, float* fst, float* history, int* decisions, int N, int steps, int early_stop,
+                      ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

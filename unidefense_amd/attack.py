@@ -1,5 +1,5 @@
-"""Graph-replayed input gradients and FGSM / PGD / Auto-PGD attacks on a frozen eval-mode detector: InputGradRunner,
-AttackRunner, APGDRunner.
+"""Graph-replayed input gradients and FGSM / PGD / Auto-PGD / Square attacks on a frozen eval-mode detector: InputGradRunner,
+AttackRunner, APGDRunner, SquareRunner.
 
 Both follow InferenceRunner's life cycle (unidefense_amd/infer.py): call 1 runs eagerly (it settles the on-line GEMM tuner and
 every lazily made workspace of the forward AND the backward for the shape), call 2 captures one hipGraph on static buffers,
@@ -25,6 +25,12 @@ APGDRunner (Auto-PGD, APGD-CE) has the same life cycle next to AttackRunner, whi
 iteration whose per-sample control — which samples improved, whose step size is halved, who restarts from their best point —
 is device state written by csrc/apgd.hip (ud_apgd_control: one thread per sample; ud_apgd_update_linf: one pass), plus a
 forward-only graph that scores the last point; the best point per sample over all iterations and restarts is returned.
+
+SquareRunner (Square Attack, L-infinity, as in AutoAttack) is the black-box member: it needs the forward only — InferenceRunner's,
+in either precision — and no gradient, so it cross-checks the gradient attacks above, which all differentiate the same frozen
+backward.  Its graph holds one query: csrc/square.hip's ud_square_propose (settle the last proposal's window, write the next),
+the forward, the per-sample objective and ud_square_control (keep or undo, who is still searched); every random choice is drawn by
+torch outside the graph (square_draws) into device tables that the kernels index with the sample's own counter.
 """
 import contextlib
 import math
@@ -558,3 +564,239 @@ def apgd_runner(model, batch, size, norm="linf", eps=None, steps=100, restarts=1
     return _cached(model, "_ud_apgd_runners", key,
                    lambda: APGDRunner(model, batch, size, norm, eps, steps, restarts, random_start, rho, alpha, targeted, clip,
                                       objective, precision, grad_scale))
+
+
+# ---- Square Attack, L-infinity (Andriushchenko et al. 2020, as AutoAttack runs it): score-based, forward only --------------------
+SQUARE_OBJECTIVES = ("margin", "cross_entropy")
+_SQUARE_THRESHOLDS = (10, 50, 200, 500, 1000, 2000, 4000, 6000, 8000)
+
+
+def square_sizes(steps, size, p_init):
+    """The window side s_j of proposal j = 0 .. steps - 1, evaluated by iteration k = j + 1: it = (k 10000) // steps,
+    p = p_init / 2^m with m the number of thresholds (10, 50, 200, 500, 1000, 2000, 4000, 6000, 8000) that `it` exceeds,
+    s = min(max(floor(sqrt(p size^2) + 0.5), 1), size).  Integers and float64 only: the same on any machine."""
+    steps, size = int(steps), int(size)
+    out = []
+    for j in range(steps):
+        it = ((j + 1) * 10000) // steps
+        m = sum(1 for t in _SQUARE_THRESHOLDS if it > t)
+        p = float(p_init) / 2.0 ** m
+        out.append(min(max(int(math.floor(math.sqrt(p * size * size) + 0.5)), 1), size))
+    return tuple(out)
+
+
+def square_draws(steps, batch, size, p_init, generator=None):
+    """Every random choice of one restart, drawn in this fixed order on the generator's device (None: torch's default CPU
+    generator): sign0 [batch, 3, size] (+-1, fp32: the vertical stripes of the start, one sign per channel and column) from
+    randint; u_h then u_w [steps, batch] float64 uniforms, h = floor(u_h (size - s_j + 1)) and w likewise (int64, inside
+    [0, size - s_j]); sign [steps, batch, 3] (+-1, fp32) from randint.  Returns (sign0, h, w, sign).  A CPU generator with the
+    same seed gives the same draws on any machine."""
+    steps, batch, size = int(steps), int(batch), int(size)
+    dev = generator.device if generator is not None else torch.device("cpu")
+    side = torch.tensor(square_sizes(steps, size, p_init), dtype=torch.float64, device=dev).reshape(-1, 1)
+    sign0 = torch.randint(0, 2, (batch, 3, size), generator=generator, device=dev).to(torch.float32) * 2.0 - 1.0
+    room = size - side + 1.0
+    u_h = torch.rand(steps, batch, generator=generator, device=dev, dtype=torch.float64)
+    u_w = torch.rand(steps, batch, generator=generator, device=dev, dtype=torch.float64)
+    h = torch.minimum(torch.floor(u_h * room), room - 1.0).to(torch.int64)
+    w = torch.minimum(torch.floor(u_w * room), room - 1.0).to(torch.int64)
+    sign = torch.randint(0, 2, (steps, batch, 3), generator=generator, device=dev).to(torch.float32) * 2.0 - 1.0
+    return sign0, h, w, sign
+
+
+def margin_each(out, y):
+    """The margin of the true class, [batch]: z_y - max_{j != y} z_j; with a single logit (2 y - 1) z.  Positive while the sample
+    is classified correctly."""
+    z = out["cls_out"]
+    if z.shape[1] == 1:
+        return (2.0 * y.to(z.dtype) - 1.0) * z.squeeze(1)
+    idx = y.reshape(-1, 1)
+    own = z.gather(1, idx).squeeze(1)
+    other = z.scatter(1, idx, float("-inf")).max(1).values
+    return own - other
+
+
+def _neg_cross_entropy_each(out, y):
+    return -cross_entropy_each(out, y)
+
+
+class SquareRunner(_GradRunnerBase):
+    """runner = SquareRunner(model, batch, size, eps=..., steps=5000, ...); x_adv = runner(x, y[, generator]).
+
+    Square Attack in L-infinity on the per-sample objective f, which is MINIMISED (objective="margin": margin_each, the sample is
+    fooled once f <= 0; "cross_entropy": minus each sample's loss; or a callable (out, y) -> [batch]).  The start is
+    clamp(x + eps sign0, clip) with vertical stripes sign0; proposal j overwrites one s_j x s_j window (square_sizes) at a random
+    place with x +- eps per channel, and is kept where f fell below the best so far.  With objective "margin" and early_stop a
+    sample is searched (and its queries counted) only while its best f is positive.  One hipGraph holds ONE query — propose,
+    forward (InferenceRunner's, under no_grad), f, control — and a restart replays it steps + 1 times, then settles the last
+    window; every random choice comes from square_draws(steps, batch, size, p_init, generator) outside the graph.  restarts: each
+    takes new draws, the per-sample lowest f is kept.  check_every (0: never): every that many replays the host reads the number
+    of samples still searched and stops the restart at zero.  No tape, no gradient, nothing frozen.
+
+    Static buffers that the next call overwrites: x_adv (returned), best_loss [N] (f at x_adv), loss0 [N] (f at restart 0's
+    start), queries [N] (forwards that counted, summed over the restarts), history [steps + 1, N] and decisions [steps + 1, N]
+    (f_k and kept-or-not of the LAST restart; rows past an early exit are zero), out (the last forward's output); args: the
+    resolved arguments."""
+    _what = "SquareRunner"
+
+    def __init__(self, model, batch, size, norm="linf", eps=None, steps=5000, p_init=0.8, restarts=1, early_stop=True,
+                 check_every=0, clip=(-1.0, 1.0), objective="margin", precision="fp32"):
+        from .model import MODEL
+        if not isinstance(model, tuple(MODEL.values())):
+            raise ValueError(f"{self._what} takes a UDEB4 / UDR18 / UDR50 model, got {type(model).__name__}")
+        _check_precision(model, precision)
+        if norm != "linf":
+            raise ValueError(f"norm must be 'linf': the L2 Square attack is not built, got {norm!r}")
+        if eps is None or not float(eps) >= 0.0:
+            raise ValueError(f"eps must be >= 0, got {eps!r}")
+        if int(steps) != steps or steps < 1:
+            raise ValueError(f"steps must be an integer >= 1, got {steps!r}")
+        if int(restarts) != restarts or restarts < 1:
+            raise ValueError(f"restarts must be an integer >= 1, got {restarts!r}")
+        if not check_every >= 0 or int(check_every) != check_every:
+            raise ValueError(f"check_every must be an integer >= 0, got {check_every!r}")
+        if not 0.0 < float(p_init) <= 1.0:
+            raise ValueError(f"p_init must be in (0, 1], got {p_init!r}")
+        if len(clip) != 2 or not float(clip[0]) < float(clip[1]):
+            raise ValueError(f"clip must be (lo, hi) with lo < hi, got {clip!r}")
+        if not callable(objective) and objective not in SQUARE_OBJECTIVES:
+            raise ValueError(f"objective must be one of {SQUARE_OBJECTIVES} or a callable (out, y) -> [batch], got {objective!r}")
+        if model.training:
+            raise ValueError(f"{self._what} needs model.eval(): the captured forward reads the running statistics")
+        p = next(model.parameters())
+        if not p.is_cuda:
+            raise ValueError(f"{self._what} needs a cuda model")
+        self.model, self.batch, self.size = model, int(batch), int(size)
+        self.shape = (self.batch, 3, self.size, self.size)
+        self.device = p.device
+        self.precision, self.half = precision, precision == "fp16"
+        self.objective = objective if callable(objective) else (margin_each if objective == "margin" else _neg_cross_entropy_each)
+        self.norm, self.eps, self.steps, self.restarts = norm, float(eps), int(steps), int(restarts)
+        self.p_init, self.check_every = float(p_init), int(check_every)
+        self.early_stop = bool(early_stop)
+        self._stop = self.early_stop and objective == "margin"        # only the margin has a threshold that means "fooled"
+        self.lo, self.hi = float(clip[0]), float(clip[1])
+        self.sizes = square_sizes(self.steps, self.size, self.p_init)
+        self.args = {"method": "square", "norm": norm, "eps": self.eps, "steps": self.steps, "p_init": self.p_init,
+                     "restarts": self.restarts, "early_stop": self.early_stop, "check_every": self.check_every,
+                     "clip": (self.lo, self.hi),
+                     "objective": objective if isinstance(objective, str) else getattr(objective, "__name__", repr(objective)),
+                     "precision": self.precision}
+        self.calls = 0
+        self.graph = self.out = None
+        self.x0 = self.x_try = self.x_best = self.x_adv = self.y = None
+
+    def _buffers(self, x, y):
+        from . import kernels as K
+        n, dev, steps = self.batch, self.device, self.steps
+        self.x0 = x.detach().clone().contiguous()
+        self.x_try, self.x_best, self.x_adv = (torch.zeros_like(self.x0) for _ in range(3))
+        self.y = y.detach().clone()
+        self.ist, self.fst = K.square_state(n, dev)
+        self.history = torch.zeros(steps + 1, n, dtype=torch.float32, device=dev)
+        self.decisions = torch.zeros(steps + 1, n, dtype=torch.int32, device=dev)
+        self.best_loss = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.loss0 = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.queries = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._side = torch.tensor(self.sizes, dtype=torch.int32, device=dev)
+        self._dh = torch.zeros(steps, n, dtype=torch.int32, device=dev)
+        self._dw = torch.zeros(steps, n, dtype=torch.int32, device=dev)
+        self._dsign = torch.ones(steps, n, 3, dtype=torch.float32, device=dev)
+        self._f_best = self.fst[K.SQUARE_F["f_best"]]
+        self._active = self.ist[K.SQUARE_I["active"]]
+
+    def _each(self, out):
+        f = self.objective(out, self.y)
+        if not isinstance(f, torch.Tensor) or tuple(f.shape) != (self.batch,):
+            raise ValueError(f"SquareRunner's objective must return a [{self.batch}] tensor, one value per sample, got "
+                             f"{tuple(f.shape) if isinstance(f, torch.Tensor) else type(f).__name__}")
+        return f
+
+    def _propose(self, closing=False):
+        from . import kernels as K
+        K.square_propose(self.x_try, self.x_best, self.x0, self.ist, self._side, self._dh, self._dw, self._dsign, self.eps,
+                         self.lo, self.hi, closing=closing)
+
+    def _iteration(self):
+        """one query on the static buffers: what the graph holds"""
+        from . import kernels as K
+        self._propose()
+        with torch.no_grad(), _eval_nodes(self.model, self.half):
+            out = self.model(self.x_try)
+            f = self._each(out)
+        self.out = _detached(out)
+        K.square_control(f.detach().float().contiguous(), self.ist, self.fst, self.history, self.decisions, self.steps, self._stop)
+
+    def _start(self, generator):
+        """a restart's draws into the device tables and its start point, outside the graph; the state back to zero"""
+        sign0, h, w, sign = square_draws(self.steps, self.batch, self.size, self.p_init, generator)
+        with torch.no_grad():
+            self._dh.copy_(h.to(self.device))
+            self._dw.copy_(w.to(self.device))
+            self._dsign.copy_(sign.to(self.device))
+            s = (self.x0 + sign0.to(self.device).unsqueeze(2) * self.eps).clamp_(self.lo, self.hi)
+            self.x_try.copy_(s)
+            self.x_best.copy_(s)
+            self.ist.zero_()
+            self.history.zero_()
+            self.decisions.zero_()
+
+    def _merge(self, restart):
+        """the per-sample minimum of f_best over the restarts so far, outside the graph"""
+        from . import kernels as K
+        with torch.no_grad():
+            if restart == 0:
+                self.loss0.copy_(self.history[0])
+                self.x_adv.copy_(self.x_best)
+                self.best_loss.copy_(self._f_best)
+            else:
+                better = (self._f_best < self.best_loss).to(torch.int32)
+                K.apgd_keep(self.x_adv, self.x_best, better)
+                self.best_loss.copy_(torch.where(better.bool(), self._f_best, self.best_loss))
+            self.queries.add_(self.ist[K.SQUARE_I["queries"]])
+
+    def __call__(self, x, y, generator=None):
+        self._check(x, y)
+        self.calls += 1
+        if self.calls == 1:                                       # eager warm-up: the same launches, a valid attack
+            self._buffers(x, y)
+        elif self.graph is None:
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._iteration()
+            self.graph = g
+        with torch.no_grad():
+            self.x0.copy_(x)
+            self.y.copy_(y)
+            self.queries.zero_()
+        for r in range(self.restarts):
+            self._start(generator)
+            for k in range(self.steps + 1):
+                if self.graph is None:
+                    self._iteration()
+                else:
+                    self.graph.replay()
+                if self.check_every and (k + 1) % self.check_every == 0 and int(self._active.sum()) == 0:
+                    break
+            self._propose(closing=True)
+            self._merge(r)
+        return self.x_adv
+
+
+def square_key(batch, size, norm="linf", eps=None, steps=5000, p_init=0.8, restarts=1, early_stop=True, check_every=0,
+               clip=(-1.0, 1.0), objective="margin", precision="fp32"):
+    """an fp32 runner's key; an fp16 runner's carries the precision behind it, as _precision_key's (Square has no loss scale)"""
+    key = (int(batch), int(size), norm, eps, steps, p_init, restarts, bool(early_stop), check_every, tuple(clip), objective)
+    return key if precision == "fp32" else key + (precision,)
+
+
+def square_runner(model, batch, size, norm="linf", eps=None, steps=5000, p_init=0.8, restarts=1, early_stop=True, check_every=0,
+                  clip=(-1.0, 1.0), objective="margin", precision="fp32"):
+    """The model's SquareRunner for the full argument tuple, made on first use; at most _MAX_RUNNERS are kept, in a dictionary of
+    their own (the other runners' caches are untouched)."""
+    _check_precision(model, precision)
+    key = square_key(batch, size, norm, eps, steps, p_init, restarts, early_stop, check_every, clip, objective, precision)
+    return _cached(model, "_ud_square_runners", key,
+                   lambda: SquareRunner(model, batch, size, norm, eps, steps, p_init, restarts, early_stop, check_every, clip,
+                                        objective, precision))

@@ -261,7 +261,11 @@ class TrainEngine(AbstractEngine):
         inference_precision keep their meaning for the two scoring forwards.  Data parallel: each rank attacks its own batches on the un-wrapped model (a
         frozen pass has no collective of its own) and the scores are gathered over the ranks as in _score.
         "method": "apgd" in the attack dict selects Auto-PGD (the model's APGDRunner: norm, eps, steps, restarts, rho, alpha, ...;
-        an optional "seed" seeds the generator of its random restarts); "pgd", the default, is the fixed-step AttackRunner."""
+        an optional "seed" seeds the generator of its random restarts); "pgd", the default, is the fixed-step AttackRunner.
+        "method": "square" selects the black-box Square attack (the model's SquareRunner: eps, steps, p_init, restarts, ...; an
+        optional "seed" seeds the CPU generator of its draws).  "method": "apgd+square" takes {"apgd": {...}, "square": {...},
+        "seed": ...}: both attacks start from the clean batch, both results are scored, and each sample keeps the score with the
+        lower probability of its true label (the worst case over the ensemble); "attack" then holds both resolved dicts."""
         from .metrics import gather_scores
         attack = attack if attack is not None else self.config["config"].get("attack")
         if not attack:
@@ -281,30 +285,51 @@ class TrainEngine(AbstractEngine):
 
         attack = dict(attack)
         method = attack.pop("method", "pgd")
-        if method not in ("pgd", "apgd"):
-            raise ValueError(f"attack method must be 'pgd' or 'apgd', got {method!r}")
-        generator = None
-        if method == "apgd":                                 # Auto-PGD (APGDRunner): "seed" makes the random restarts reproducible
+        if method not in ("pgd", "apgd", "square", "apgd+square"):
+            raise ValueError(f"attack method must be 'pgd', 'apgd', 'square' or 'apgd+square', got {method!r}")
+        generator = square_generator = None
+        square = None
+        if method != "pgd":                                  # "seed" makes the random restarts / the draws reproducible
             seed = attack.pop("seed", None)
-            if seed is not None:
+            if seed is not None and method != "square":      # Auto-PGD (APGDRunner) draws its restarts on the device
                 generator = torch.Generator(device=self.device).manual_seed(int(seed))
+            if seed is not None and method != "apgd":        # Square (SquareRunner) draws on the CPU: the same on any machine
+                square_generator = torch.Generator().manual_seed(int(seed))
+        if method == "apgd+square":
+            unknown = set(attack) - {"apgd", "square"}
+            if unknown or "apgd" not in attack or "square" not in attack:
+                raise ValueError(f"attack method 'apgd+square' takes {{'apgd': {{...}}, 'square': {{...}}, 'seed': ...}}, got the keys "
+                                 f"{sorted(attack)}")
+            attack, square = dict(attack["apgd"]), dict(attack["square"])
+        elif method == "square":
+            attack, square = None, attack
 
-        clean, adv, labels, runner = [], [], [], None
+        clean, adv, labels, runner, square_runner = [], [], [], None, None
         for step in range(1, batches + 1):
             xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
             x, y = torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
             clean.append(score(x))
-            if method == "apgd":
+            if method in ("apgd", "apgd+square"):
                 runner = self.model_without_ddp.apgd_runner(x.shape[0], x.shape[-1], **attack)
-                adv.append(score(runner(x, y, generator)))
-            else:
+                s = score(runner(x, y, generator))
+            elif method == "pgd":
                 runner = self.model_without_ddp.attack_runner(x.shape[0], x.shape[-1], **attack)
-                adv.append(score(runner(x, y)))
+                s = score(runner(x, y))
+            if square is not None:
+                square_runner = self.model_without_ddp.square_runner(x.shape[0], x.shape[-1], **square)
+                s2 = score(square_runner(x, y, square_generator))
+                # the score is P(class 0): the true label's probability is lower where it is lower for y == 0, higher otherwise
+                s = s2 if method == "square" else torch.where(y == 0, torch.minimum(s, s2), torch.maximum(s, s2))
+            adv.append(s)
             labels.append(y)
         labels = torch.cat(labels)
+        if method == "apgd+square":
+            args = {"method": method, "apgd": dict(runner.args), "square": dict(square_runner.args)}
+        else:
+            args = dict((square_runner if method == "square" else runner).args)
         return {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"),
                 "adv": self._metrics(*gather_scores(torch.cat(adv), labels), "Test(adv)"),
-                "attack": dict(runner.args)}
+                "attack": args}
 
     def validate(self, step, batches=4):
         """The reference's validate (forgery_engine.py:320-421) without the figure / wandb plumbing: metrics over all

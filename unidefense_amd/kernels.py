@@ -1564,6 +1564,61 @@ def apgd_project_l2(x, x0, dss, fst, eps, lo, hi):
     return x
 
 
+# ---- Square attack (csrc/square.hip): per-sample control state ist [4, N] int32 / fst [1, N] fp32, rows as in the header -------
+SQUARE_I = {"k": 0, "accepted": 1, "active": 2, "queries": 3}
+SQUARE_F = {"f_best": 0}
+
+
+def _chk_i32(t, shape, what):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{what} must be a contiguous int32 CUDA tensor {list(shape)}, got {t.dtype} {t.device} {tuple(t.shape)}")
+
+
+def _chk_square_state(ist, fst, N):
+    _chk_i32(ist, (len(SQUARE_I), N), "ist")
+    _chk(fst)
+    if tuple(fst.shape) != (len(SQUARE_F), N):
+        raise ValueError(f"fst must be [{len(SQUARE_F)}, {N}], got {tuple(fst.shape)}")
+
+
+def square_state(N, device):
+    """(ist, fst): zeroed control state for N samples"""
+    return (torch.zeros(len(SQUARE_I), N, dtype=torch.int32, device=device),
+            torch.zeros(len(SQUARE_F), N, dtype=torch.float32, device=device))
+
+
+def square_propose(x_try, x_best, x0, ist, side, dh, dw, dsign, eps, lo, hi, closing=False):
+    """In place on x_try and x_best [N, 3, size, size]: settle the window of proposal k - 1 (kept where ist's accepted row says so,
+    undone otherwise) and write the window of proposal k = ist's counter, x0 + dsign eps clamped to [lo, hi], from row k - 1 of
+    the draw tables side [steps] / dh, dw [steps, N] int32 and dsign [steps, N, 3] fp32; closing: settle only."""
+    _chk_same(x_try, x_best, x0)
+    if x_try.dim() != 4 or x_try.shape[1] != 3 or x_try.shape[2] != x_try.shape[3]:
+        raise ValueError(f"expected [N, 3, size, size] images, got {tuple(x_try.shape)}")
+    N, size, steps = x_try.shape[0], x_try.shape[2], side.numel()
+    _chk_i32(ist, (len(SQUARE_I), N), "ist")
+    _chk_i32(side, (steps,), "side")
+    _chk_i32(dh, (steps, N), "dh")
+    _chk_i32(dw, (steps, N), "dw")
+    _chk(dsign)
+    if tuple(dsign.shape) != (steps, N, 3):
+        raise ValueError(f"dsign must be [{steps}, {N}, 3], got {tuple(dsign.shape)}")
+    _call("ud_square_propose", _p(x_try), _p(x_best), _p(x0), _p(ist), _p(side), _p(dh), _p(dw), _p(dsign), N, size, steps,
+          float(eps), float(lo), float(hi), int(bool(closing)), _stream())
+    return x_try
+
+
+def square_control(f, ist, fst, history, decisions, steps, early_stop=True):
+    """One step of the per-sample Square state machine on f [N] fp32: keep the last proposal where f fell below f_best, count
+    the query, recompute who is still searched (early_stop: f_best > 0), record history / decisions row k."""
+    _chk(f, history)
+    N = f.numel()
+    _chk_square_state(ist, fst, N)
+    if tuple(history.shape) != (int(steps) + 1, N):
+        raise ValueError(f"history must be [{int(steps) + 1}, {N}], got {tuple(history.shape)}")
+    _chk_i32(decisions, (int(steps) + 1, N), "decisions")
+    _call("ud_square_control", _p(f), _p(ist), _p(fst), _p(history), _p(decisions), N, int(steps), int(bool(early_stop)), _stream())
+
+
 def conv_gather_wgrad(a, x, g):
     """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)]."""
     _chk(a, x)

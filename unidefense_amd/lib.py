@@ -173,6 +173,8 @@ _SIGNATURES = {
     "ud_apgd_step_l2": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _P],
     "ud_apgd_combine_l2": [_P, _P, _P, _P, _I, _L, _P],
     "ud_apgd_project_l2": [_P, _P, _P, _P, _I, _L, _F, _F, _F, _P],
+    "ud_square_propose": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _I, _P],
+    "ud_square_control": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "ud_absdiff_bwd": [_P, _P, _P, _P, _P, _L, _P],
     "ud_outer": [_P, _P, _P, _L, _I, _P],
     "ud_gather2d": [_P, _P, _P, _P, _L, _I, _I, _P],

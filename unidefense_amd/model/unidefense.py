@@ -293,6 +293,13 @@ class UniDefenseModelEb4(nn.Module):
         from ..attack import apgd_runner
         return apgd_runner(self, batch, size, **kwargs)
 
+    def square_runner(self, batch, size, **kwargs):
+        """The graph-replayed Square attack (black-box, L-infinity, forward only) for [batch, 3, size, size] inputs
+        (unidefense_amd/attack.py: SquareRunner; kwargs: eps, steps, p_init, restarts, early_stop, check_every, clip, objective,
+        precision), cached per argument tuple in a dictionary of its own."""
+        from ..attack import square_runner
+        return square_runner(self, batch, size, **kwargs)
+
     # -- pretrained backbone (model/efficientnet/utils.py:589-634): missing sf_coef / freq_conv keys tolerated
     def load_backbone_weights(self, path):
         sd = torch.load(path, map_location="cpu")

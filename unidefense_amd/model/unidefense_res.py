@@ -175,6 +175,13 @@ class UniDefenseModelRes18(nn.Module):
         from ..attack import apgd_runner
         return apgd_runner(self, batch, size, **kwargs)
 
+    def square_runner(self, batch, size, **kwargs):
+        """The graph-replayed Square attack (black-box, L-infinity, forward only) for [batch, 3, size, size] inputs
+        (unidefense_amd/attack.py: SquareRunner; kwargs: eps, steps, p_init, restarts, early_stop, check_every, clip, objective,
+        precision), cached per argument tuple in a dictionary of its own."""
+        from ..attack import square_runner
+        return square_runner(self, batch, size, **kwargs)
+
     # ---------------------------------------------------------------------------------------
     def _conv(self, tape, x, conv, stride):
         if isinstance(conv, _SFConv2dParams):
