@@ -303,6 +303,34 @@ def test_l2_pieces_vs_float64(per):
             assert within(f"ud_apgd_project_l2 per {per} sample {n}: |d| / (4 2^-24 (|x0| + |d|))", worst, 1.0)
 
 
+@pytest.mark.parametrize("N,per", [(3, 5), (4, 4099)])
+def test_project_l2_is_attack_project_l2_on_the_momentum_samples(N, per):
+    """The two entry points share one ball element: on the samples with a != 1 ud_apgd_project_l2 gives the bits of
+    ud_attack_project_l2, the samples with a == 1 keep every byte.  per is no multiple of 4, so ud_attack_project_l2's float4
+    groups straddle samples and its tail runs.  Sample 0 (a != 1) lies inside the ball: factor exactly 1, unchanged before the
+    clip; every other sample lies outside; one element of sample 2 (a != 1) is NaN and stays NaN."""
+    from unidefense_amd import kernels as K
+    dev = _dev()
+    eps = 0.5
+    gen = torch.Generator().manual_seed(N * per)
+    x0 = torch.rand(N, per, generator=gen) * 2 - 1
+    d = torch.rand(N, per, generator=gen) * 2 - 1
+    d = d / d.norm(dim=1, keepdim=True) * eps * torch.tensor([0.5] + [3.0] * (N - 1)).reshape(-1, 1)
+    x = (x0 + d).to(dev)
+    a = [0.75 if n % 2 == 0 else 1.0 for n in range(N)]
+    _, fst = _state_for([0] * N, [0] * N, [0.0] * N, a, dev)
+    dss = K.sample_sumsq(x, x0.to(dev))
+    norms = dss.sqrt().cpu()
+    assert float(norms[0]) < 0.9 * eps and all(float(v) > 1.1 * eps for v in norms[1:])
+    x[2, per // 2] = float("nan")                          # after the norms: dss is an input of both entry points
+    want = K.attack_project_l2(x.clone(), x0.to(dev), dss, eps, LO, HI)
+    got = K.apgd_project_l2(x.clone(), x0.to(dev), dss, fst, eps, LO, HI)
+    momentum = torch.tensor(a, device=dev).reshape(-1, 1) != 1.0
+    assert torch.equal(got.view(torch.int32), torch.where(momentum, want, x).view(torch.int32))
+    assert torch.equal(got[0], x[0].clamp(LO, HI)) and not torch.equal(want[1], x[1])
+    assert bool(torch.isnan(got[2, per // 2])) and int(torch.isnan(got).sum()) == 1
+
+
 # ---- 4. the runner: exact properties -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("norm", ["linf", "l2"])
 @pytest.mark.parametrize("name,size,n,seed,steps", [("UDR18", 128, 2, 5, 1), ("UDR18", 128, 2, 5, 3), ("UDR18", 128, 2, 5, 10),

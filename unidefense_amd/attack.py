@@ -1,13 +1,16 @@
 """Graph-replayed input gradients and FGSM / PGD / Auto-PGD / Square attacks on a frozen eval-mode detector: InputGradRunner,
 AttackRunner, APGDRunner, SquareRunner.
 
-Both follow InferenceRunner's life cycle (unidefense_amd/infer.py): call 1 runs eagerly (it settles the on-line GEMM tuner and
-every lazily made workspace of the forward AND the backward for the shape), call 2 captures one hipGraph on static buffers,
-later calls copy the inputs in and replay.  The captured work is `autograd.grad(objective(model(x_buf), y_buf), x_buf)` on the
-eval-mode model with every parameter frozen for the duration of the warm-up and the capture, so the backward is the tape's
-frozen sequence (Tape.wgrad_on = False: no weight-gradient launch, no parameter gets a .grad).  K.begin_forward runs inside the
-graph and every BatchNorm reads its running buffers in place, so a runner captured before an optimizer step, a load_state_dict
-or a change of running statistics differentiates the updated model.
+All four sit on one base class (_Runner) and follow InferenceRunner's life cycle (unidefense_amd/infer.py): call 1 runs eagerly
+(it settles the on-line GEMM tuner and every lazily made workspace of the forward AND the backward for the shape), call 2
+captures the runner's iteration on static buffers (_Runner._capture), later calls copy the inputs in and replay.  An attack's
+defaults are written once, in its class's signature: the *_key and *_runner accessors bind their arguments with it.
+
+The gradient runners capture `autograd.grad(objective(model(x_buf), y_buf), x_buf)` (_Runner._grad) on the eval-mode model with
+every parameter frozen for the duration of the warm-up and the capture, so the backward is the tape's frozen sequence
+(Tape.wgrad_on = False: no weight-gradient launch, no parameter gets a .grad).  K.begin_forward runs inside the graph and every
+BatchNorm reads its running buffers in place, so a runner captured before an optimizer step, a load_state_dict or a change of
+running statistics differentiates the updated model.
 
 AttackRunner's graph holds ONE iteration — forward on the static leaf x_adv, objective, d/dx, and the step written into x_adv in
 place by csrc/attack.hip (L-infinity: one launch; L2: norm, step, norm, projection) — and a call replays it `steps` times.
@@ -21,10 +24,10 @@ power of two, default 1024: 99.95 % of the unscaled x-gradient's entries lie bel
 the fp32 result divided by it inside the graph: runner.g is unscaled; a non-finite gradient stays non-finite.  The eager
 model(x), the fp32 runners and the training step do not change.
 
-APGDRunner (Auto-PGD, APGD-CE) has the same life cycle next to AttackRunner, which it leaves as it is: its graph holds one
-iteration whose per-sample control — which samples improved, whose step size is halved, who restarts from their best point —
-is device state written by csrc/apgd.hip (ud_apgd_control: one thread per sample; ud_apgd_update_linf: one pass), plus a
-forward-only graph that scores the last point; the best point per sample over all iterations and restarts is returned.
+APGDRunner (Auto-PGD, APGD-CE): its graph holds one iteration whose per-sample control — which samples improved, whose step size
+is halved, who restarts from their best point — is device state written by csrc/apgd.hip (ud_apgd_control: one thread per
+sample; ud_apgd_update_linf: one pass), plus a forward-only graph that scores the last point; the best point per sample over all
+iterations and restarts is returned.
 
 SquareRunner (Square Attack, L-infinity, as in AutoAttack) is the black-box member: it needs the forward only — InferenceRunner's,
 in either precision — and no gradient, so it cross-checks the gradient attacks above, which all differentiate the same frozen
@@ -33,12 +36,13 @@ the forward, the per-sample objective and ud_square_control (keep or undo, who i
 torch outside the graph (square_draws) into device tables that the kernels index with the sample's own counter.
 """
 import contextlib
+import inspect
 import math
 
 import torch
 import torch.nn.functional as F
 
-from .infer import _MAX_RUNNERS, _check_precision, _eval_nodes
+from .infer import _MAX_RUNNERS, _check_model, _check_precision, _eval_nodes
 
 DEFAULT_GRAD_SCALE = 1024.0          # fp16 runners: the loss scale of the half-storage training tests
 
@@ -108,27 +112,57 @@ def resolve_step(eps, steps, step=None):
     return float(eps) if steps == 1 else 2.5 * float(eps) / steps
 
 
-class _GradRunnerBase:
-    _what = "runner"
+# ---- argument refusals: each written once, raised by the constructors in their own order -------------------------------------
+def _refuse_norm(norm):
+    if norm not in NORMS:
+        raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
 
-    def _init_model(self, model, batch, size, objective, precision="fp32", grad_scale=None):
-        from .model import MODEL
-        if not isinstance(model, tuple(MODEL.values())):
-            raise ValueError(f"{self._what} takes a UDEB4 / UDR18 / UDR50 model, got {type(model).__name__}")
-        _check_precision(model, precision)
+
+def _refuse_eps(eps):
+    if eps is None or not float(eps) >= 0.0:
+        raise ValueError(f"eps must be >= 0, got {eps!r}")
+
+
+def _refuse_count(name, v, least):
+    if not v >= least or int(v) != v:
+        raise ValueError(f"{name} must be an integer >= {least}, got {v!r}")
+
+
+def _refuse_fraction(name, v):
+    if not 0.0 < float(v) <= 1.0:
+        raise ValueError(f"{name} must be in (0, 1], got {v!r}")
+
+
+def _refuse_clip(clip):
+    if len(clip) != 2 or not float(clip[0]) < float(clip[1]):
+        raise ValueError(f"clip must be (lo, hi) with lo < hi, got {clip!r}")
+
+
+def _objective_name(objective):
+    return objective if isinstance(objective, str) else getattr(objective, "__name__", repr(objective))
+
+
+class _Runner:
+    """What the four runners share: the model checks, the input checks, the capture, the forward + d/dx with fp16's loss scale,
+    and the per-sample pieces of the attacks with restarts."""
+    _what = "runner"
+    _backward = True                     # the captured work differentiates: the parameters are frozen around it
+
+    def _init_model(self, model, batch, size, precision, arguments):
+        """The one place a runner looks at its model: its kind and the precision; then arguments(), the runner's own refusals,
+        which need no device; then eval mode and the device."""
         self.precision, self.half = precision, precision == "fp16"
-        self.grad_scale = resolve_grad_scale(precision, grad_scale)
-        self.objective = _objective(objective)
-        if model.training:
-            raise ValueError(f"{self._what} needs model.eval(): the captured forward reads the running statistics")
-        p = next(model.parameters())
-        if not p.is_cuda:
-            raise ValueError(f"{self._what} needs a cuda model")
+        self.device = _check_model(self._what, model, precision, arguments)
         self.model, self.batch, self.size = model, int(batch), int(size)
         self.shape = (self.batch, 3, self.size, self.size)
-        self.device = p.device
         self.calls = 0
-        self.graph = self.out = self.g = None
+        self.graph = self.out = None
+
+    def _init_loss(self, objective, grad_scale):
+        """the gradient runners' arguments(): the loss scale and the objective"""
+        self.grad_scale = resolve_grad_scale(self.precision, grad_scale)
+        self.objective = _objective(objective)
+        self.g = None
 
     def _check(self, x, y):
         if not isinstance(x, torch.Tensor) or not x.is_cuda or not isinstance(y, torch.Tensor) or not y.is_cuda:
@@ -140,23 +174,68 @@ class _GradRunnerBase:
         if self.model.training:
             raise ValueError("the model is in training mode: call model.eval() before the runner")
 
-    def _grad(self, x, y):
-        """forward + objective + d/dx on the leaf x: (gradient, detached output dict)"""
-        if not self.half:
-            out = self.model(x)
-            g, = torch.autograd.grad(self.objective(out, y), x)
-            return g, _detached(out)
-        # fp16: the trunk's frozen half nodes (runner-scoped flag); the scaled objective keeps the half gradients off fp16's
-        # subnormals, the fp32 result is unscaled in place (inside the graph when capturing)
+    def _capture(self, *bodies):
+        """One hipGraph per body, captured in order on the static buffers after a device synchronise, the parameters frozen
+        where the runner has a backward: the graphs."""
+        torch.cuda.synchronize(self.device)
+        graphs = [torch.cuda.CUDAGraph() for _ in bodies]
+        with frozen(self.model) if self._backward else contextlib.nullcontext():
+            for g, body in zip(graphs, bodies):
+                with torch.cuda.graph(g):
+                    body()
+        return graphs
+
+    def _nodes(self):
+        return _eval_nodes(self.model, half=True) if self.half else contextlib.nullcontext()
+
+    def _grad(self, x, value):
+        """forward on the leaf x, f = value(out) (a scalar, or one value per sample: their sum is differentiated), d/dx:
+        (gradient, detached output dict, f).  fp16: the trunk's frozen half nodes (runner-scoped flag); the scaled objective
+        keeps the half gradients off fp16's subnormals, the fp32 result is unscaled in place (inside the graph when capturing)."""
         from . import kernels as K
-        with _eval_nodes(self.model, half=True):
+        with self._nodes():
             out = self.model(x)
-            g, = torch.autograd.grad(self.objective(out, y) * self.grad_scale, x)
-        g = g.contiguous()
-        return K.axpby(g, 1.0 / self.grad_scale, out=g), _detached(out)
+            f = value(out)
+            total = f if f.dim() == 0 else f.sum()
+            g, = torch.autograd.grad(total * self.grad_scale if self.half else total, x)
+        if self.half:
+            g = g.contiguous()
+            K.axpby(g, 1.0 / self.grad_scale, out=g)
+        return g, _detached(out), f
+
+    def _each(self, out):
+        """the per-sample objective on the static labels, [batch]"""
+        f = self.objective(out, self.y)
+        if not isinstance(f, torch.Tensor) or tuple(f.shape) != (self.batch,):
+            raise ValueError(f"{self._what}'s objective must return a [{self.batch}] tensor, one value per sample, got "
+                             f"{tuple(f.shape) if isinstance(f, torch.Tensor) else type(f).__name__}")
+        return f
+
+    def _draw(self, sample, generator):
+        """sample = torch.rand / torch.randn of the input's shape, drawn on the generator's device"""
+        gdev = generator.device if generator is not None else self.device
+        return sample(self.shape, generator=generator, device=gdev, dtype=torch.float32).to(self.device)
+
+    def _box_start(self, x, generator):
+        """clamp(x + U(-eps, eps), clip)"""
+        return (x + (self._draw(torch.rand, generator) * 2.0 - 1.0) * self.eps).clamp_(self.lo, self.hi)
+
+    def _merge(self, restart, better):
+        """the per-sample best of f_best over the restarts so far, outside the graph; better: torch.gt where f is maximised,
+        torch.lt where it is minimised"""
+        from . import kernels as K
+        with torch.no_grad():
+            if restart == 0:
+                self.loss0.copy_(self.history[0])
+                self.x_adv.copy_(self.x_best)
+                self.best_loss.copy_(self._f_best)
+            else:
+                keep = better(self._f_best, self.best_loss).to(torch.int32)
+                K.apgd_keep(self.x_adv, self.x_best, keep)
+                self.best_loss.copy_(torch.where(keep.bool(), self._f_best, self.best_loss))
 
 
-class InputGradRunner(_GradRunnerBase):
+class InputGradRunner(_Runner):
     """runner = InputGradRunner(model, batch, size[, objective]); g = runner(x, y) with x [batch, 3, size, size] fp32 and y
     [batch] int64 on the model's GPU: the gradient of objective(model(x), y) with respect to x for the frozen eval-mode model.
     g and runner.out (the forward's output dict, detached) live in static buffers that the next call overwrites.
@@ -166,8 +245,11 @@ class InputGradRunner(_GradRunnerBase):
     _what = "InputGradRunner"
 
     def __init__(self, model, batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
-        self._init_model(model, batch, size, objective, precision, grad_scale)
+        self._init_model(model, batch, size, precision, lambda: self._init_loss(objective, grad_scale))
         self.x = self.y = None
+
+    def _iteration(self, x, y):
+        self.g, self.out, _ = self._grad(x, lambda out: self.objective(out, y))
 
     def __call__(self, x, y):
         self._check(x, y)
@@ -175,16 +257,12 @@ class InputGradRunner(_GradRunnerBase):
         with torch.enable_grad():
             if self.calls == 1:                                   # eager warm-up of what the graph records
                 with frozen(self.model):
-                    self.g, self.out = self._grad(x.detach().clone().contiguous().requires_grad_(), y)
+                    self._iteration(x.detach().clone().contiguous().requires_grad_(), y)
                 return self.g
             if self.graph is None:
                 self.x = x.detach().clone().contiguous().requires_grad_()
                 self.y = y.detach().clone()
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with frozen(self.model), torch.cuda.graph(g):
-                    self.g, self.out = self._grad(self.x, self.y)
-                self.graph = g
+                self.graph, = self._capture(lambda: self._iteration(self.x, self.y))
             else:
                 with torch.no_grad():
                     self.x.copy_(x)
@@ -193,7 +271,7 @@ class InputGradRunner(_GradRunnerBase):
         return self.g
 
 
-class AttackRunner(_GradRunnerBase):
+class AttackRunner(_Runner):
     """runner = AttackRunner(model, batch, size, norm="linf", eps=..., steps=10, ...); x_adv = runner(x, y[, generator]).
 
     `steps` iterations of  x_adv <- project(x_adv + step * direction(d objective / d x_adv))  from x_adv = x, ascending the
@@ -209,24 +287,19 @@ class AttackRunner(_GradRunnerBase):
 
     def __init__(self, model, batch, size, norm="linf", eps=None, steps=10, step=None, random_start=False, targeted=False,
                  clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
-        if norm not in NORMS:
-            raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
-        if eps is None or not float(eps) >= 0.0:
-            raise ValueError(f"eps must be >= 0, got {eps!r}")
-        if int(steps) != steps or steps < 1:
-            raise ValueError(f"steps must be an integer >= 1, got {steps!r}")
-        if len(clip) != 2 or not float(clip[0]) < float(clip[1]):
-            raise ValueError(f"clip must be (lo, hi) with lo < hi, got {clip!r}")
+        _refuse_norm(norm)
+        _refuse_eps(eps)
+        _refuse_count("steps", steps, 1)
+        _refuse_clip(clip)
         if norm == "l2" and random_start:
             raise ValueError("random_start is built for norm 'linf' only")
-        self._init_model(model, batch, size, objective, precision, grad_scale)
+        self._init_model(model, batch, size, precision, lambda: self._init_loss(objective, grad_scale))
         self.norm, self.eps, self.steps = norm, float(eps), int(steps)
         self.step = resolve_step(eps, self.steps, step)
         self.random_start, self.targeted = bool(random_start), bool(targeted)
         self.lo, self.hi = float(clip[0]), float(clip[1])
         self.args = {"norm": norm, "eps": self.eps, "steps": self.steps, "step": self.step, "random_start": self.random_start,
-                     "targeted": self.targeted, "clip": (self.lo, self.hi),
-                     "objective": objective if isinstance(objective, str) else getattr(objective, "__name__", repr(objective)),
+                     "targeted": self.targeted, "clip": (self.lo, self.hi), "objective": _objective_name(objective),
                      "precision": self.precision, "grad_scale": self.grad_scale}
         self.x0 = self.x_adv = self.y = self._ss = self._ws = None
 
@@ -243,7 +316,7 @@ class AttackRunner(_GradRunnerBase):
     def _iteration(self):
         """one attack iteration on the static buffers: what the graph holds"""
         from . import kernels as K
-        self.g, self.out = self._grad(self.x_adv, self.y)
+        self.g, self.out, _ = self._grad(self.x_adv, lambda out: self.objective(out, self.y))
         g = self.g.contiguous()
         signed = -self.step if self.targeted else self.step
         if self.norm == "linf":
@@ -258,12 +331,7 @@ class AttackRunner(_GradRunnerBase):
         with torch.no_grad():
             self.x0.copy_(x)
             self.y.copy_(y)
-            if self.random_start:
-                gdev = generator.device if generator is not None else self.device
-                u = torch.rand(self.shape, generator=generator, device=gdev, dtype=torch.float32).to(self.device)
-                self.x_adv.copy_((x + (u * 2.0 - 1.0) * self.eps).clamp_(self.lo, self.hi))
-            else:
-                self.x_adv.copy_(x)
+            self.x_adv.copy_(self._box_start(x, generator) if self.random_start else x)
 
     def __call__(self, x, y, generator=None):
         self._check(x, y)
@@ -277,11 +345,7 @@ class AttackRunner(_GradRunnerBase):
                         self._iteration()
                 return self.x_adv.detach()
             if self.graph is None:
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with frozen(self.model), torch.cuda.graph(g):
-                    self._iteration()
-                self.graph = g
+                self.graph, = self._capture(self._iteration)
             self._start(x, y, generator)
         for _ in range(self.steps):
             self.graph.replay()
@@ -299,38 +363,61 @@ def _cached(model, slot, key, make):
     return r
 
 
-def _precision_key(key, precision, grad_scale):
-    """an fp32 runner's key is what it was before the runners took a precision; an fp16 runner's carries (precision, scale)"""
-    return key if precision == "fp32" else key + (precision, resolve_grad_scale(precision, grad_scale))
+def _arguments(cls):
+    """cls's (batch, size, ...) bound as its constructor binds them, defaults filled in, as a name -> value dict in the
+    constructor's order: the class's signature is the one place an attack's defaults are written"""
+    sig = inspect.signature(cls.__init__)
+
+    def bind(*args, **kwargs):
+        b = sig.bind(None, None, *args, **kwargs)
+        b.apply_defaults()
+        return dict(list(b.arguments.items())[2:])
+    return bind
 
 
-def input_grad_key(batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
-    return _precision_key((int(batch), int(size), objective), precision, grad_scale)
+_KEY_FORMS = {"batch": int, "size": int, "random_start": bool, "targeted": bool, "early_stop": bool, "clip": tuple}
 
 
-def attack_key(batch, size, norm="linf", eps=None, steps=10, step=None, random_start=False, targeted=False,
-               clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
-    return _precision_key((int(batch), int(size), norm, eps, steps, step, bool(random_start), bool(targeted), tuple(clip),
-                           objective), precision, grad_scale)
+def _key(a):
+    """The cache key of the bound arguments a: an fp32 runner's is the arguments before the precision; an fp16 runner's carries
+    (precision, scale) behind them, or (precision,) where the runner has no loss scale."""
+    key = tuple(_KEY_FORMS.get(k, lambda v: v)(v) for k, v in a.items() if k not in ("precision", "grad_scale"))
+    precision = a["precision"]
+    if precision == "fp32":
+        return key
+    return key + ((precision, resolve_grad_scale(precision, a["grad_scale"])) if "grad_scale" in a else (precision,))
 
 
-def input_grad_runner(model, batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
-    """The model's InputGradRunner for the full argument tuple, made on first use; a model keeps at most _MAX_RUNNERS of them
-    (a dictionary of their own: InferenceRunner's cache and keys are untouched)."""
-    _check_precision(model, precision)
-    key = input_grad_key(batch, size, objective, precision, grad_scale)
-    return _cached(model, "_ud_grad_runners", key,
-                   lambda: InputGradRunner(model, batch, size, objective, precision, grad_scale))
+def _cached_runner(model, slot, a, make):
+    _check_precision(model, a["precision"])
+    return _cached(model, slot, _key(a), make)
 
 
-def attack_runner(model, batch, size, norm="linf", eps=None, steps=10, step=None, random_start=False, targeted=False,
-                  clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
-    """The model's AttackRunner for the full argument tuple, made on first use; at most _MAX_RUNNERS are kept."""
-    _check_precision(model, precision)
-    key = attack_key(batch, size, norm, eps, steps, step, random_start, targeted, clip, objective, precision, grad_scale)
-    return _cached(model, "_ud_attack_runners", key,
-                   lambda: AttackRunner(model, batch, size, norm, eps, steps, step, random_start, targeted, clip, objective,
-                                        precision, grad_scale))
+_input_grad_arguments, _attack_arguments = _arguments(InputGradRunner), _arguments(AttackRunner)
+
+
+def input_grad_key(*args, **kwargs):
+    """arguments: InputGradRunner's after the model"""
+    return _key(_input_grad_arguments(*args, **kwargs))
+
+
+def attack_key(*args, **kwargs):
+    """arguments: AttackRunner's after the model"""
+    return _key(_attack_arguments(*args, **kwargs))
+
+
+def input_grad_runner(model, *args, **kwargs):
+    """The model's InputGradRunner for the full argument tuple (InputGradRunner's after the model), made on first use; a model
+    keeps at most _MAX_RUNNERS of them (a dictionary of their own: InferenceRunner's cache and keys are untouched)."""
+    a = _input_grad_arguments(*args, **kwargs)
+    return _cached_runner(model, "_ud_grad_runners", a, lambda: InputGradRunner(model, *a.values()))
+
+
+def attack_runner(model, *args, **kwargs):
+    """The model's AttackRunner for the full argument tuple (AttackRunner's after the model), made on first use; at most
+    _MAX_RUNNERS are kept."""
+    a = _attack_arguments(*args, **kwargs)
+    return _cached_runner(model, "_ud_attack_runners", a, lambda: AttackRunner(model, *a.values()))
 
 
 # ---- Auto-PGD (APGD-CE, Croce & Hein 2020): per-sample step control, restarts from the best point, best-of ----------------------
@@ -367,7 +454,7 @@ def cross_entropy_each(out, y):
     return F.cross_entropy(cls, y, reduction="none")
 
 
-class APGDRunner(_GradRunnerBase):
+class APGDRunner(_Runner):
     """runner = APGDRunner(model, batch, size, norm="linf", eps=..., steps=100, restarts=1, ...); x_adv = runner(x, y[, generator]).
 
     Auto-PGD on the per-sample objective f (objective="cross_entropy": each sample's loss; or a callable (out, y) -> [batch];
@@ -388,21 +475,14 @@ class APGDRunner(_GradRunnerBase):
 
     def __init__(self, model, batch, size, norm="linf", eps=None, steps=100, restarts=1, random_start=False, rho=0.75, alpha=0.75,
                  targeted=False, clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
-        if norm not in NORMS:
-            raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
-        if eps is None or not float(eps) >= 0.0:
-            raise ValueError(f"eps must be >= 0, got {eps!r}")
-        if int(steps) != steps or steps < 1:
-            raise ValueError(f"steps must be an integer >= 1, got {steps!r}")
-        if int(restarts) != restarts or restarts < 1:
-            raise ValueError(f"restarts must be an integer >= 1, got {restarts!r}")
-        if not 0.0 < float(rho) <= 1.0:
-            raise ValueError(f"rho must be in (0, 1], got {rho!r}")
-        if not 0.0 < float(alpha) <= 1.0:
-            raise ValueError(f"alpha must be in (0, 1], got {alpha!r}")
-        if len(clip) != 2 or not float(clip[0]) < float(clip[1]):
-            raise ValueError(f"clip must be (lo, hi) with lo < hi, got {clip!r}")
-        self._init_model(model, batch, size, objective, precision, grad_scale)
+        _refuse_norm(norm)
+        _refuse_eps(eps)
+        _refuse_count("steps", steps, 1)
+        _refuse_count("restarts", restarts, 1)
+        _refuse_fraction("rho", rho)
+        _refuse_fraction("alpha", alpha)
+        _refuse_clip(clip)
+        self._init_model(model, batch, size, precision, lambda: self._init_loss(objective, grad_scale))
         self.objective = objective if callable(objective) else cross_entropy_each
         self.norm, self.eps, self.steps, self.restarts = norm, float(eps), int(steps), int(restarts)
         self.random_start, self.targeted = bool(random_start), bool(targeted)
@@ -411,8 +491,7 @@ class APGDRunner(_GradRunnerBase):
         self.checkpoints, self._thr = apgd_table(self.steps, self.rho)
         self.args = {"method": "apgd", "norm": norm, "eps": self.eps, "steps": self.steps, "restarts": self.restarts,
                      "random_start": self.random_start, "rho": self.rho, "alpha": self.alpha, "targeted": self.targeted,
-                     "clip": (self.lo, self.hi),
-                     "objective": objective if isinstance(objective, str) else getattr(objective, "__name__", repr(objective)),
+                     "clip": (self.lo, self.hi), "objective": _objective_name(objective),
                      "precision": self.precision, "grad_scale": self.grad_scale}
         self.closing_graph = None
         self.x0 = self.x = self.x_adv = self.y = None
@@ -438,27 +517,15 @@ class APGDRunner(_GradRunnerBase):
             self._gss, self._gss_best, self._dss = (torch.zeros(n, dtype=torch.float64, device=dev) for _ in range(3))
             self._ws = torch.zeros(max(K.sample_sumsq_ws_bytes(n, per) // 8, 1), dtype=torch.float64, device=dev)
 
-    def _each(self, out):
-        f = self.objective(out, self.y)
-        if not isinstance(f, torch.Tensor) or tuple(f.shape) != (self.batch,):
-            raise ValueError(f"APGDRunner's objective must return a [{self.batch}] tensor, one value per sample, got "
-                             f"{tuple(f.shape) if isinstance(f, torch.Tensor) else type(f).__name__}")
+    def _ascended(self, out):
+        f = self._each(out)
         return -f if self.targeted else f
-
-    def _nodes(self):
-        return _eval_nodes(self.model, half=True) if self.half else contextlib.nullcontext()
 
     def _iteration(self):
         """one APGD iteration on the static buffers: what the graph holds"""
         from . import kernels as K
-        with self._nodes():
-            out = self.model(self.x)
-            f = self._each(out)
-            g, = torch.autograd.grad(f.sum() * self.grad_scale if self.half else f.sum(), self.x)
-        g = g.contiguous()
-        if self.half:                                          # unscaled in place, inside the graph when capturing
-            K.axpby(g, 1.0 / self.grad_scale, out=g)
-        self.g, self.out = g, _detached(out)
+        g, self.out, f = self._grad(self.x, self._ascended)
+        self.g = g = g.contiguous()
         K.apgd_control(f.detach().float().contiguous(), self.ist, self.fst, self.history, self.steps, self.checkpoints, self._thr,
                        2.0 * self.eps, self.alpha)
         if self.norm == "linf":
@@ -477,7 +544,7 @@ class APGDRunner(_GradRunnerBase):
         """the closing evaluation: forward only at the last point; if it beats the best, it becomes the best"""
         from . import kernels as K
         with torch.no_grad(), self._nodes():
-            f = self._each(self.model(self.x))
+            f = self._ascended(self.model(self.x))
         K.apgd_control(f.float().contiguous(), self.ist, self.fst, self.history, self.steps, self.checkpoints, self._thr,
                        2.0 * self.eps, self.alpha, closing=True)
         K.apgd_keep(self.x_best, self.x, self._improved)
@@ -489,31 +556,15 @@ class APGDRunner(_GradRunnerBase):
             x0 = self.x0
             if restart == 0 and not self.random_start:
                 s = x0.clamp(self.lo, self.hi)
+            elif self.norm == "linf":
+                s = self._box_start(x0, generator)
             else:
-                gdev = generator.device if generator is not None else self.device
-                if self.norm == "linf":
-                    u = torch.rand(self.shape, generator=generator, device=gdev, dtype=torch.float32).to(self.device)
-                    s = (x0 + (u * 2.0 - 1.0) * self.eps).clamp_(self.lo, self.hi)
-                else:
-                    n = torch.randn(self.shape, generator=generator, device=gdev, dtype=torch.float32).to(self.device)
-                    nrm = n.flatten(1).norm(dim=1).clamp_min(1e-12).view(-1, 1, 1, 1)
-                    s = (x0 + n * (self.eps / nrm)).clamp_(self.lo, self.hi)
+                n = self._draw(torch.randn, generator)
+                nrm = n.flatten(1).norm(dim=1).clamp_min(1e-12).view(-1, 1, 1, 1)
+                s = (x0 + n * (self.eps / nrm)).clamp_(self.lo, self.hi)
             self.x.copy_(s)
             self.x_prev.copy_(s)
             self.ist[K.APGD_I["k"]].zero_()
-
-    def _merge(self, restart):
-        """the per-sample maximum of f_best over the restarts so far, outside the graph"""
-        from . import kernels as K
-        with torch.no_grad():
-            if restart == 0:
-                self.loss0.copy_(self.history[0])
-                self.x_adv.copy_(self.x_best)
-                self.best_loss.copy_(self._f_best)
-            else:
-                better = (self._f_best > self.best_loss).to(torch.int32)
-                K.apgd_keep(self.x_adv, self.x_best, better)
-                self.best_loss.copy_(torch.where(better.bool(), self._f_best, self.best_loss))
 
     def __call__(self, x, y, generator=None):
         self._check(x, y)
@@ -522,14 +573,7 @@ class APGDRunner(_GradRunnerBase):
             if self.calls == 1:                                   # eager warm-up: the same launches, a valid attack
                 self._buffers(x, y)
             elif self.graph is None:
-                torch.cuda.synchronize(self.device)
-                g, c = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                with frozen(self.model):
-                    with torch.cuda.graph(g):
-                        self._iteration()
-                    with torch.cuda.graph(c):
-                        self._closing()
-                self.graph, self.closing_graph = g, c
+                self.graph, self.closing_graph = self._capture(self._iteration, self._closing)
             with torch.no_grad():
                 self.x0.copy_(x)
                 self.y.copy_(y)
@@ -544,26 +588,23 @@ class APGDRunner(_GradRunnerBase):
                     for _ in range(self.steps):
                         self.graph.replay()
                     self.closing_graph.replay()
-                self._merge(r)
+                self._merge(r, torch.gt)
         return self.x_adv
 
 
-def apgd_key(batch, size, norm="linf", eps=None, steps=100, restarts=1, random_start=False, rho=0.75, alpha=0.75, targeted=False,
-             clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
-    return _precision_key((int(batch), int(size), norm, eps, steps, restarts, bool(random_start), rho, alpha, bool(targeted),
-                           tuple(clip), objective), precision, grad_scale)
+_apgd_arguments = _arguments(APGDRunner)
 
 
-def apgd_runner(model, batch, size, norm="linf", eps=None, steps=100, restarts=1, random_start=False, rho=0.75, alpha=0.75,
-                targeted=False, clip=(-1.0, 1.0), objective="cross_entropy", precision="fp32", grad_scale=None):
-    """The model's APGDRunner for the full argument tuple, made on first use; at most _MAX_RUNNERS are kept, in a dictionary of
-    their own (the other runners' caches are untouched)."""
-    _check_precision(model, precision)
-    key = apgd_key(batch, size, norm, eps, steps, restarts, random_start, rho, alpha, targeted, clip, objective, precision,
-                   grad_scale)
-    return _cached(model, "_ud_apgd_runners", key,
-                   lambda: APGDRunner(model, batch, size, norm, eps, steps, restarts, random_start, rho, alpha, targeted, clip,
-                                      objective, precision, grad_scale))
+def apgd_key(*args, **kwargs):
+    """arguments: APGDRunner's after the model"""
+    return _key(_apgd_arguments(*args, **kwargs))
+
+
+def apgd_runner(model, *args, **kwargs):
+    """The model's APGDRunner for the full argument tuple (APGDRunner's after the model), made on first use; at most
+    _MAX_RUNNERS are kept, in a dictionary of their own (the other runners' caches are untouched)."""
+    a = _apgd_arguments(*args, **kwargs)
+    return _cached_runner(model, "_ud_apgd_runners", a, lambda: APGDRunner(model, *a.values()))
 
 
 # ---- Square Attack, L-infinity (Andriushchenko et al. 2020, as AutoAttack runs it): score-based, forward only --------------------
@@ -620,7 +661,7 @@ def _neg_cross_entropy_each(out, y):
     return -cross_entropy_each(out, y)
 
 
-class SquareRunner(_GradRunnerBase):
+class SquareRunner(_Runner):
     """runner = SquareRunner(model, batch, size, eps=..., steps=5000, ...); x_adv = runner(x, y[, generator]).
 
     Square Attack in L-infinity on the per-sample objective f, which is MINIMISED (objective="margin": margin_each, the sample is
@@ -638,38 +679,22 @@ class SquareRunner(_GradRunnerBase):
     (f_k and kept-or-not of the LAST restart; rows past an early exit are zero), out (the last forward's output); args: the
     resolved arguments."""
     _what = "SquareRunner"
+    _backward = False
 
     def __init__(self, model, batch, size, norm="linf", eps=None, steps=5000, p_init=0.8, restarts=1, early_stop=True,
                  check_every=0, clip=(-1.0, 1.0), objective="margin", precision="fp32"):
-        from .model import MODEL
-        if not isinstance(model, tuple(MODEL.values())):
-            raise ValueError(f"{self._what} takes a UDEB4 / UDR18 / UDR50 model, got {type(model).__name__}")
-        _check_precision(model, precision)
-        if norm != "linf":
-            raise ValueError(f"norm must be 'linf': the L2 Square attack is not built, got {norm!r}")
-        if eps is None or not float(eps) >= 0.0:
-            raise ValueError(f"eps must be >= 0, got {eps!r}")
-        if int(steps) != steps or steps < 1:
-            raise ValueError(f"steps must be an integer >= 1, got {steps!r}")
-        if int(restarts) != restarts or restarts < 1:
-            raise ValueError(f"restarts must be an integer >= 1, got {restarts!r}")
-        if not check_every >= 0 or int(check_every) != check_every:
-            raise ValueError(f"check_every must be an integer >= 0, got {check_every!r}")
-        if not 0.0 < float(p_init) <= 1.0:
-            raise ValueError(f"p_init must be in (0, 1], got {p_init!r}")
-        if len(clip) != 2 or not float(clip[0]) < float(clip[1]):
-            raise ValueError(f"clip must be (lo, hi) with lo < hi, got {clip!r}")
-        if not callable(objective) and objective not in SQUARE_OBJECTIVES:
-            raise ValueError(f"objective must be one of {SQUARE_OBJECTIVES} or a callable (out, y) -> [batch], got {objective!r}")
-        if model.training:
-            raise ValueError(f"{self._what} needs model.eval(): the captured forward reads the running statistics")
-        p = next(model.parameters())
-        if not p.is_cuda:
-            raise ValueError(f"{self._what} needs a cuda model")
-        self.model, self.batch, self.size = model, int(batch), int(size)
-        self.shape = (self.batch, 3, self.size, self.size)
-        self.device = p.device
-        self.precision, self.half = precision, precision == "fp16"
+        def arguments():
+            if norm != "linf":
+                raise ValueError(f"norm must be 'linf': the L2 Square attack is not built, got {norm!r}")
+            _refuse_eps(eps)
+            _refuse_count("steps", steps, 1)
+            _refuse_count("restarts", restarts, 1)
+            _refuse_count("check_every", check_every, 0)
+            _refuse_fraction("p_init", p_init)
+            _refuse_clip(clip)
+            if not callable(objective) and objective not in SQUARE_OBJECTIVES:
+                raise ValueError(f"objective must be one of {SQUARE_OBJECTIVES} or a callable (out, y) -> [batch], got {objective!r}")
+        self._init_model(model, batch, size, precision, arguments)
         self.objective = objective if callable(objective) else (margin_each if objective == "margin" else _neg_cross_entropy_each)
         self.norm, self.eps, self.steps, self.restarts = norm, float(eps), int(steps), int(restarts)
         self.p_init, self.check_every = float(p_init), int(check_every)
@@ -679,11 +704,7 @@ class SquareRunner(_GradRunnerBase):
         self.sizes = square_sizes(self.steps, self.size, self.p_init)
         self.args = {"method": "square", "norm": norm, "eps": self.eps, "steps": self.steps, "p_init": self.p_init,
                      "restarts": self.restarts, "early_stop": self.early_stop, "check_every": self.check_every,
-                     "clip": (self.lo, self.hi),
-                     "objective": objective if isinstance(objective, str) else getattr(objective, "__name__", repr(objective)),
-                     "precision": self.precision}
-        self.calls = 0
-        self.graph = self.out = None
+                     "clip": (self.lo, self.hi), "objective": _objective_name(objective), "precision": self.precision}
         self.x0 = self.x_try = self.x_best = self.x_adv = self.y = None
 
     def _buffers(self, x, y):
@@ -704,13 +725,6 @@ class SquareRunner(_GradRunnerBase):
         self._dsign = torch.ones(steps, n, 3, dtype=torch.float32, device=dev)
         self._f_best = self.fst[K.SQUARE_F["f_best"]]
         self._active = self.ist[K.SQUARE_I["active"]]
-
-    def _each(self, out):
-        f = self.objective(out, self.y)
-        if not isinstance(f, torch.Tensor) or tuple(f.shape) != (self.batch,):
-            raise ValueError(f"SquareRunner's objective must return a [{self.batch}] tensor, one value per sample, got "
-                             f"{tuple(f.shape) if isinstance(f, torch.Tensor) else type(f).__name__}")
-        return f
 
     def _propose(self, closing=False):
         from . import kernels as K
@@ -741,31 +755,14 @@ class SquareRunner(_GradRunnerBase):
             self.history.zero_()
             self.decisions.zero_()
 
-    def _merge(self, restart):
-        """the per-sample minimum of f_best over the restarts so far, outside the graph"""
-        from . import kernels as K
-        with torch.no_grad():
-            if restart == 0:
-                self.loss0.copy_(self.history[0])
-                self.x_adv.copy_(self.x_best)
-                self.best_loss.copy_(self._f_best)
-            else:
-                better = (self._f_best < self.best_loss).to(torch.int32)
-                K.apgd_keep(self.x_adv, self.x_best, better)
-                self.best_loss.copy_(torch.where(better.bool(), self._f_best, self.best_loss))
-            self.queries.add_(self.ist[K.SQUARE_I["queries"]])
-
     def __call__(self, x, y, generator=None):
+        from . import kernels as K
         self._check(x, y)
         self.calls += 1
         if self.calls == 1:                                       # eager warm-up: the same launches, a valid attack
             self._buffers(x, y)
         elif self.graph is None:
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._iteration()
-            self.graph = g
+            self.graph, = self._capture(self._iteration)
         with torch.no_grad():
             self.x0.copy_(x)
             self.y.copy_(y)
@@ -780,23 +777,21 @@ class SquareRunner(_GradRunnerBase):
                 if self.check_every and (k + 1) % self.check_every == 0 and int(self._active.sum()) == 0:
                     break
             self._propose(closing=True)
-            self._merge(r)
+            self._merge(r, torch.lt)
+            self.queries.add_(self.ist[K.SQUARE_I["queries"]])
         return self.x_adv
 
 
-def square_key(batch, size, norm="linf", eps=None, steps=5000, p_init=0.8, restarts=1, early_stop=True, check_every=0,
-               clip=(-1.0, 1.0), objective="margin", precision="fp32"):
-    """an fp32 runner's key; an fp16 runner's carries the precision behind it, as _precision_key's (Square has no loss scale)"""
-    key = (int(batch), int(size), norm, eps, steps, p_init, restarts, bool(early_stop), check_every, tuple(clip), objective)
-    return key if precision == "fp32" else key + (precision,)
+_square_arguments = _arguments(SquareRunner)
 
 
-def square_runner(model, batch, size, norm="linf", eps=None, steps=5000, p_init=0.8, restarts=1, early_stop=True, check_every=0,
-                  clip=(-1.0, 1.0), objective="margin", precision="fp32"):
-    """The model's SquareRunner for the full argument tuple, made on first use; at most _MAX_RUNNERS are kept, in a dictionary of
-    their own (the other runners' caches are untouched)."""
-    _check_precision(model, precision)
-    key = square_key(batch, size, norm, eps, steps, p_init, restarts, early_stop, check_every, clip, objective, precision)
-    return _cached(model, "_ud_square_runners", key,
-                   lambda: SquareRunner(model, batch, size, norm, eps, steps, p_init, restarts, early_stop, check_every, clip,
-                                        objective, precision))
+def square_key(*args, **kwargs):
+    """arguments: SquareRunner's after the model; Square has no loss scale: an fp16 runner's key carries (precision,)"""
+    return _key(_square_arguments(*args, **kwargs))
+
+
+def square_runner(model, *args, **kwargs):
+    """The model's SquareRunner for the full argument tuple (SquareRunner's after the model), made on first use; at most
+    _MAX_RUNNERS are kept, in a dictionary of their own (the other runners' caches are untouched)."""
+    a = _square_arguments(*args, **kwargs)
+    return _cached_runner(model, "_ud_square_runners", a, lambda: SquareRunner(model, *a.values()))

@@ -7,16 +7,11 @@
 // and no two threads store to the same address.  The element-wise kernels follow csrc/attack.hip: contiguous fp32 planes
 // [N][3][H][W] (per = 3 H W), grid-stride, a float4 body with a scalar tail, a group that straddles two samples looks its
 // sample up per element, no atomics, NaN-transparent clamps — a replay gives the same bits.
-#include "ud_common.h"
+#include "attack_common.h"
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int MAXCK = UD_APGD_MAX_CHECKPOINTS;
-
-// rows of the [5][N] state arrays (UD_APGD_I_* / UD_APGD_F_* of the header)
-enum { I_K = 0, I_CNT = 1, I_HALVED = 2, I_IMPROVED = 3, I_RESET = 4 };
-enum { F_PREV = 0, F_BEST = 1, F_CKPT = 2, F_ETA = 3, F_A = 4 };
 
 struct Checkpoints {          // by value in the kernel arguments
     int w[MAXCK];             // iteration index of the checkpoint
@@ -24,25 +19,9 @@ struct Checkpoints {          // by value in the kernel arguments
     int n;
 };
 
-inline int ew_blocks(long work) {
-    long b = (work + NT - 1) / NT;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-inline bool shape_ok(int N, long per) { return N >= 1 && N <= 65535 && per >= 1 && per <= (1L << 40) / N; }
-
-// clamp that keeps a NaN (both comparisons are false for it)
-__device__ __forceinline__ float clampf(float v, float lo, float hi) {
-    v = v < lo ? lo : v;
-    return v > hi ? hi : v;
-}
-
 // ---- control --------------------------------------------------------------------------------------------------------------
-// closing == 0: iteration k = ist[I_K][n] of the state machine (k outside [0, steps) writes nothing), then k + 1 is stored.
+// closing == 0: iteration k = ist[UD_APGD_I_K][n] of the state machine (k outside [0, steps) writes nothing), then k + 1 is
+// stored.
 // closing != 0: the keep-best decision on the loss of the last point, history row `steps`; the counter is left alone.
 __global__ __launch_bounds__(64) void apgd_control(const float* __restrict__ f, int* __restrict__ ist,
                                                     float* __restrict__ fst, float* __restrict__ history, int N, int steps,
@@ -51,14 +30,14 @@ __global__ __launch_bounds__(64) void apgd_control(const float* __restrict__ f, 
     if (n >= N) return;
     const float fk = f[n];
     if (closing) {
-        const float fb = fst[(long)F_BEST * N + n];
+        const float fb = fst[(long)UD_APGD_F_BEST * N + n];
         const int imp = fk > fb;
-        if (imp) fst[(long)F_BEST * N + n] = fk;
-        ist[(long)I_IMPROVED * N + n] = imp;
+        if (imp) fst[(long)UD_APGD_F_BEST * N + n] = fk;
+        ist[(long)UD_APGD_I_IMPROVED * N + n] = imp;
         history[(long)steps * N + n] = fk;
         return;
     }
-    const int k = ist[(long)I_K * N + n];
+    const int k = ist[(long)UD_APGD_I_K * N + n];
     if (k < 0 || k >= steps) return;
     float fbest, fckpt, eta, a;
     int cnt, halved, improved;
@@ -68,11 +47,11 @@ __global__ __launch_bounds__(64) void apgd_control(const float* __restrict__ f, 
         improved = 1, cnt = 0, halved = 0;
         a = 1.f;
     } else {
-        fbest = fst[(long)F_BEST * N + n];
-        fckpt = fst[(long)F_CKPT * N + n];
-        eta = fst[(long)F_ETA * N + n];
-        cnt = ist[(long)I_CNT * N + n] + (fk > fst[(long)F_PREV * N + n] ? 1 : 0);
-        halved = ist[(long)I_HALVED * N + n];
+        fbest = fst[(long)UD_APGD_F_BEST * N + n];
+        fckpt = fst[(long)UD_APGD_F_CKPT * N + n];
+        eta = fst[(long)UD_APGD_F_ETA * N + n];
+        cnt = ist[(long)UD_APGD_I_CNT * N + n] + (fk > fst[(long)UD_APGD_F_PREV * N + n] ? 1 : 0);
+        halved = ist[(long)UD_APGD_I_HALVED * N + n];
         improved = fk > fbest;
         if (improved) fbest = fk;
         a = alpha;
@@ -92,16 +71,16 @@ __global__ __launch_bounds__(64) void apgd_control(const float* __restrict__ f, 
         fckpt = fbest;
         cnt = 0;
     }
-    fst[(long)F_PREV * N + n] = fk;
-    fst[(long)F_BEST * N + n] = fbest;
-    fst[(long)F_CKPT * N + n] = fckpt;
-    fst[(long)F_ETA * N + n] = eta;
-    fst[(long)F_A * N + n] = a;
-    ist[(long)I_K * N + n] = k + 1;
-    ist[(long)I_CNT * N + n] = cnt;
-    ist[(long)I_HALVED * N + n] = halved;
-    ist[(long)I_IMPROVED * N + n] = improved;
-    ist[(long)I_RESET * N + n] = reset;
+    fst[(long)UD_APGD_F_PREV * N + n] = fk;
+    fst[(long)UD_APGD_F_BEST * N + n] = fbest;
+    fst[(long)UD_APGD_F_CKPT * N + n] = fckpt;
+    fst[(long)UD_APGD_F_ETA * N + n] = eta;
+    fst[(long)UD_APGD_F_A * N + n] = a;
+    ist[(long)UD_APGD_I_K * N + n] = k + 1;
+    ist[(long)UD_APGD_I_CNT * N + n] = cnt;
+    ist[(long)UD_APGD_I_HALVED * N + n] = halved;
+    ist[(long)UD_APGD_I_IMPROVED * N + n] = improved;
+    ist[(long)UD_APGD_I_RESET * N + n] = reset;
     history[(long)k * N + n] = fk;
 }
 
@@ -113,82 +92,52 @@ struct Sample {               // what the control left for one sample
 
 __device__ __forceinline__ Sample load_sample(const int* __restrict__ ist, const float* __restrict__ fst, int N, long n) {
     Sample s;
-    s.improved = ist[(long)I_IMPROVED * N + n];
-    s.reset = ist[(long)I_RESET * N + n];
-    s.eta = fst[(long)F_ETA * N + n];
-    s.a = fst[(long)F_A * N + n];
+    s.improved = ist[(long)UD_APGD_I_IMPROVED * N + n];
+    s.reset = ist[(long)UD_APGD_I_RESET * N + n];
+    s.eta = fst[(long)UD_APGD_F_ETA * N + n];
+    s.a = fst[(long)UD_APGD_F_A * N + n];
     return s;
-}
-
-// projection onto the box around x0, then onto clip, as csrc/attack.hip forms it
-__device__ __forceinline__ float proj_linf(float v, float x0, float eps, float lo, float hi) {
-#pragma clang fp contract(off)
-    const float bl = x0 - eps, bh = x0 + eps;
-    return clampf(clampf(v, bl, bh), lo, hi);
 }
 
 // One element, one fp32 rounding per operation, in the order of the torch expression
 //   z = P(src + eta sign(gs));   x' = z  if a == 1  else  P((src + a (z - src)) + (1 - a) (src - x_prev))
-// eta sign(gs) is +-eta or 0 exactly; a NaN gs gives a NaN.  x_best / g_best are read only for a sample that resets
-// without having improved, and written only for a sample that improved.
-__device__ __forceinline__ void linf_elem(float* __restrict__ x, float* __restrict__ xprev, float* __restrict__ xbest,
-                                          float* __restrict__ gbest, const float* __restrict__ x0,
-                                          const float* __restrict__ g, long i, const Sample s, float eps, float lo, float hi) {
+// with P = proj_linf.  prev is looked at only for a sample with a != 1.
+__device__ __forceinline__ float linf_new(float src, float gs, float prev, float x0, const Sample s, float eps, float lo,
+                                          float hi) {
 #pragma clang fp contract(off)
-    float src = x[i], gs = g[i];
-    if (s.improved) {
-        xbest[i] = src;
-        gbest[i] = gs;
-    } else if (s.reset) {
-        src = xbest[i];
-        gs = gbest[i];
-    }
-    const float b = x0[i];
-    const float inc = gs > 0.f ? s.eta : (gs < 0.f ? -s.eta : (gs == gs ? 0.f : gs));
-    const float z = proj_linf(src + inc, b, eps, lo, hi);
-    float xn = z;
-    if (s.a != 1.f) {
-        const float t1 = s.a * (z - src);
-        const float t2 = (1.f - s.a) * (src - xprev[i]);
-        xn = proj_linf((src + t1) + t2, b, eps, lo, hi);
-    }
-    xprev[i] = src;
-    x[i] = xn;
+    const float z = proj_linf(src + sign_inc(gs, s.eta), x0, eps, lo, hi);
+    if (s.a == 1.f) return z;
+    const float t1 = s.a * (z - src);
+    const float t2 = (1.f - s.a) * (src - prev);
+    return proj_linf((src + t1) + t2, x0, eps, lo, hi);
 }
 
-// the same on a float4 group that lies inside one sample
-__device__ __forceinline__ void linf_group(float* __restrict__ x, float* __restrict__ xprev, float* __restrict__ xbest,
-                                           float* __restrict__ gbest, const float* __restrict__ x0,
-                                           const float* __restrict__ g, long i4, const Sample s, float eps, float lo, float hi) {
-#pragma clang fp contract(off)
-    f32x4 src = reinterpret_cast<const f32x4*>(x)[i4];
-    f32x4 gs = reinterpret_cast<const f32x4*>(g)[i4];
+// The update of one element (V = float) or of a float4 group that lies inside one sample (V = f32x4), i counting in units
+// of V.  x_best / g_best are read only for a sample that resets without having improved and written only for a sample that
+// improved; x_prev is read only for a sample with a != 1.
+template <typename V>
+__device__ __forceinline__ void linf_update(float* __restrict__ x, float* __restrict__ xprev, float* __restrict__ xbest,
+                                            float* __restrict__ gbest, const float* __restrict__ x0,
+                                            const float* __restrict__ g, long i, const Sample s, float eps, float lo, float hi) {
+    V src = reinterpret_cast<const V*>(x)[i], gs = reinterpret_cast<const V*>(g)[i];
     if (s.improved) {
-        reinterpret_cast<f32x4*>(xbest)[i4] = src;
-        reinterpret_cast<f32x4*>(gbest)[i4] = gs;
+        reinterpret_cast<V*>(xbest)[i] = src;
+        reinterpret_cast<V*>(gbest)[i] = gs;
     } else if (s.reset) {
-        src = reinterpret_cast<const f32x4*>(xbest)[i4];
-        gs = reinterpret_cast<const f32x4*>(gbest)[i4];
+        src = reinterpret_cast<const V*>(xbest)[i];
+        gs = reinterpret_cast<const V*>(gbest)[i];
     }
-    const f32x4 b = reinterpret_cast<const f32x4*>(x0)[i4];
-    f32x4 xn;
+    const V b = reinterpret_cast<const V*>(x0)[i];
+    V prev = src, xn;
+    if (s.a != 1.f) prev = reinterpret_cast<const V*>(xprev)[i];
+    if constexpr (sizeof(V) == sizeof(float)) {
+        xn = linf_new(src, gs, prev, b, s, eps, lo, hi);
+    } else {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float inc = gs[e] > 0.f ? s.eta : (gs[e] < 0.f ? -s.eta : (gs[e] == gs[e] ? 0.f : gs[e]));
-        xn[e] = proj_linf(src[e] + inc, b[e], eps, lo, hi);
+        for (int e = 0; e < 4; ++e) xn[e] = linf_new(src[e], gs[e], prev[e], b[e], s, eps, lo, hi);
     }
-    if (s.a != 1.f) {
-        const f32x4 p = reinterpret_cast<const f32x4*>(xprev)[i4];
-        const float oma = 1.f - s.a;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float t1 = s.a * (xn[e] - src[e]);
-            const float t2 = oma * (src[e] - p[e]);
-            xn[e] = proj_linf((src[e] + t1) + t2, b[e], eps, lo, hi);
-        }
-    }
-    reinterpret_cast<f32x4*>(xprev)[i4] = src;
-    reinterpret_cast<f32x4*>(x)[i4] = xn;
+    reinterpret_cast<V*>(xprev)[i] = src;
+    reinterpret_cast<V*>(x)[i] = xn;
 }
 
 __global__ __launch_bounds__(NT) void apgd_update_linf(float* __restrict__ x, float* __restrict__ xprev,
@@ -200,14 +149,14 @@ __global__ __launch_bounds__(NT) void apgd_update_linf(float* __restrict__ x, fl
     for (long i = tid; i < nvec; i += nthr) {
         const long n0 = (4 * i) / per, n3 = (4 * i + 3) / per;
         if (n3 == n0) {
-            linf_group(x, xprev, xbest, gbest, x0, g, i, load_sample(ist, fst, N, n0), eps, lo, hi);
+            linf_update<f32x4>(x, xprev, xbest, gbest, x0, g, i, load_sample(ist, fst, N, n0), eps, lo, hi);
         } else {
-            for (int e = 0; e < 4; ++e)
-                linf_elem(x, xprev, xbest, gbest, x0, g, 4 * i + e, load_sample(ist, fst, N, (4 * i + e) / per), eps, lo, hi);
+            for (long j = 4 * i; j < 4 * i + 4; ++j)
+                linf_update<float>(x, xprev, xbest, gbest, x0, g, j, load_sample(ist, fst, N, j / per), eps, lo, hi);
         }
     }
     for (long i = 4 * nvec + tid; i < total; i += nthr)
-        linf_elem(x, xprev, xbest, gbest, x0, g, i, load_sample(ist, fst, N, i / per), eps, lo, hi);
+        linf_update<float>(x, xprev, xbest, gbest, x0, g, i, load_sample(ist, fst, N, i / per), eps, lo, hi);
 }
 
 // ---- keep-best copy: dst[n] <- src[n] where flag[n] != 0 ------------------------------------------------------------------
@@ -228,8 +177,6 @@ __global__ __launch_bounds__(NT) void apgd_keep(float* __restrict__ dst, const f
 }
 
 // ---- L2: step and combination (the two projections are ud_sample_sumsq + apgd_project_l2 / ud_attack_project_l2) ----------
-__device__ __forceinline__ double l2_dir_factor(double ss, float eta) { return (double)eta / fmax(sqrt(ss), 1e-12); }
-
 // One element of the L2 step: keep-best copy, source selection, x <- src, z <- src + eta gs / max(|gs|, 1e-12) formed in
 // double and rounded once.  gss[n] = |g[n]|^2; gss_best[n] is kept beside g_best (written by the thread of the sample's
 // first element when the sample improved, read only when it resets without having improved: never both in one launch).
@@ -271,7 +218,7 @@ __global__ __launch_bounds__(NT) void apgd_combine_l2(float* __restrict__ x, flo
                                                        long per, long total) {
     const long tid = (long)blockIdx.x * NT + threadIdx.x, nthr = (long)gridDim.x * NT;
     for (long i = tid; i < total; i += nthr) {
-        const float a = fst[(long)F_A * N + i / per];
+        const float a = fst[(long)UD_APGD_F_A * N + i / per];
         const float src = x[i], zz = z[i];
         float xn = zz;
         if (a != 1.f) {
@@ -283,19 +230,17 @@ __global__ __launch_bounds__(NT) void apgd_combine_l2(float* __restrict__ x, flo
     }
 }
 
-// ud_attack_project_l2 on the samples whose a != 1 (the momentum point); a sample with a == 1 holds z, which is projected
-// already, and is left exactly as it is
+// csrc/attack.hip's ball projection on the samples whose a != 1 (the momentum point); a sample with a == 1 holds z, which is
+// projected already, and is left exactly as it is
 __global__ __launch_bounds__(NT) void apgd_project_l2(float* __restrict__ x, const float* __restrict__ x0,
                                                        const double* __restrict__ dss, const float* __restrict__ fst, int N,
                                                        long per, long total, double eps, float lo, float hi) {
     const long tid = (long)blockIdx.x * NT + threadIdx.x, nthr = (long)gridDim.x * NT;
     for (long i = tid; i < total; i += nthr) {
         const long n = i / per;
-        if (fst[(long)F_A * N + n] == 1.f) continue;
-        const double f = fmin(1.0, eps / fmax(sqrt(dss[n]), 1e-12));
-        const float xi = x[i], b = x0[i];
-        const float v = f < 1.0 ? (float)((double)b + ((double)xi - (double)b) * f) : xi;
-        x[i] = clampf(v, lo, hi);
+        if (fst[(long)UD_APGD_F_A * N + n] == 1.f) continue;
+        const double f = l2_ball_factor(dss[n], eps);
+        x[i] = l2_ball_elem(x[i], x0[i], f, lo, hi);
     }
 }
 

@@ -6,37 +6,18 @@
 // the iteration stays inside one captured graph with one launch where torch would issue six.  So: plain grid-stride
 // kernels, a float4 body with a scalar tail (total and per need not be multiples of 4), no atomics, no data-dependent
 // partition — a replay gives the same bits.
-#include "ud_common.h"
+#include "attack_common.h"
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int CHUNK = 4096;          // elements of one sample that one workgroup of ud_sample_sumsq sums (16 per thread)
-
-inline int ew_blocks(long work) {
-    long b = (work + NT - 1) / NT;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// clamp that keeps a NaN (both comparisons are false for it)
-__device__ __forceinline__ float clampf(float v, float lo, float hi) {
-    v = v < lo ? lo : v;
-    return v > hi ? hi : v;
-}
 
 // One element of the L-infinity step, in the order torch evaluates
 //   clamp(clamp(x + step * sign(g), x0 - eps, x0 + eps), lo, hi)
-// with one fp32 rounding per operation.  step * sign(g) is +-step or 0 exactly; a NaN g gives a NaN increment.
+// with one fp32 rounding per operation
 __device__ __forceinline__ float linf_elem(float x, float x0, float g, float step, float eps, float lo, float hi) {
 #pragma clang fp contract(off)
-    const float inc = g > 0.f ? step : (g < 0.f ? -step : (g == g ? 0.f : g));
-    const float v = x + inc;
-    const float bl = x0 - eps, bh = x0 + eps;
-    return clampf(clampf(v, bl, bh), lo, hi);
+    return proj_linf(x + sign_inc(g, step), x0, eps, lo, hi);
 }
 
 // nvec float4 groups from the start, then the scalar elements [4 nvec, total)
@@ -107,21 +88,7 @@ __global__ __launch_bounds__(64) void sample_sumsq_fold(const double* __restrict
     out[n] = s;
 }
 
-// per-sample factors, in double
-__device__ __forceinline__ double l2_step_factor(const double* gss, long n, double step) {
-    return step / fmax(sqrt(gss[n]), 1e-12);
-}
-__device__ __forceinline__ double l2_proj_factor(const double* dss, long n, double eps) {
-    return fmin(1.0, eps / fmax(sqrt(dss[n]), 1e-12));
-}
-
 __device__ __forceinline__ float l2_step_elem(float x, float g, double f) { return (float)((double)x + (double)g * f); }
-
-// x0 + d f with d = x_adv - x0; a factor of exactly 1 (d inside the ball) leaves x_adv as it is before the clamp
-__device__ __forceinline__ float l2_proj_elem(float x, float x0, double f, float lo, float hi) {
-    const float v = f < 1.0 ? (float)((double)x0 + ((double)x - (double)x0) * f) : x;
-    return clampf(v, lo, hi);
-}
 
 // PROJ = false: x_adv[n] += step g[n] / max(|g[n]|, 1e-12), other = g, ss = gss, c = step
 // PROJ = true : x_adv[n] <- clamp(x0[n] + d[n] min(1, eps / max(|d[n]|, 1e-12))), other = x0, ss = dss, c = eps
@@ -135,26 +102,24 @@ __global__ __launch_bounds__(NT) void attack_l2(float* __restrict__ xa, const fl
         f32x4 v = reinterpret_cast<const f32x4*>(xa)[i];
         const f32x4 o = reinterpret_cast<const f32x4*>(other)[i];
         const long n0 = (4 * i) / per, n3 = (4 * i + 3) / per;
-        const double f0 = PROJ ? l2_proj_factor(ss, n0, c) : l2_step_factor(ss, n0, c);
+        const double f0 = PROJ ? l2_ball_factor(ss[n0], c) : l2_dir_factor(ss[n0], c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             double f = f0;
             if (n3 != n0) {
                 const long n = (4 * i + e) / per;
-                if (n != n0) f = PROJ ? l2_proj_factor(ss, n, c) : l2_step_factor(ss, n, c);
+                if (n != n0) f = PROJ ? l2_ball_factor(ss[n], c) : l2_dir_factor(ss[n], c);
             }
-            v[e] = PROJ ? l2_proj_elem(v[e], o[e], f, lo, hi) : l2_step_elem(v[e], o[e], f);
+            v[e] = PROJ ? l2_ball_elem(v[e], o[e], f, lo, hi) : l2_step_elem(v[e], o[e], f);
         }
         reinterpret_cast<f32x4*>(xa)[i] = v;
     }
     for (long i = 4 * nvec + tid; i < total; i += nthr) {
         const long n = i / per;
-        const double f = PROJ ? l2_proj_factor(ss, n, c) : l2_step_factor(ss, n, c);
-        xa[i] = PROJ ? l2_proj_elem(xa[i], other[i], f, lo, hi) : l2_step_elem(xa[i], other[i], f);
+        const double f = PROJ ? l2_ball_factor(ss[n], c) : l2_dir_factor(ss[n], c);
+        xa[i] = PROJ ? l2_ball_elem(xa[i], other[i], f, lo, hi) : l2_step_elem(xa[i], other[i], f);
     }
 }
-
-inline bool shape_ok(int N, long per) { return N >= 1 && N <= 65535 && per >= 1 && per <= (1L << 40) / N; }
 
 }  // namespace
 

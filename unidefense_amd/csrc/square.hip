@@ -9,22 +9,11 @@
 // identical, overlapping and disjoint consecutive windows need no ordering between threads.  Ordinary vector stores only, no
 // atomics, nothing shared between threads, NaN-transparent clamps — a replay gives the same bits.  Only the windows' bytes
 // are touched: at most 2 (s'^2 + s^2) 3 N 4 bytes of reads and as many of writes.
-#include "ud_common.h"
+#include "attack_common.h"
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int MAX_BLOCKS_X = 64;      // per sample; the threads stride over the windows' elements
-
-// rows of the state arrays (UD_SQUARE_I_* / UD_SQUARE_F_* of the header)
-enum { I_K = 0, I_ACCEPTED = 1, I_ACTIVE = 2, I_QUERIES = 3 };
-enum { F_BEST = 0 };
-
-// clamp that keeps a NaN (both comparisons are false for it)
-__device__ __forceinline__ float clampf(float v, float lo, float hi) {
-    v = v < lo ? lo : v;
-    return v > hi ? hi : v;
-}
 
 struct Window {               // rows [h, h + s) x columns [w, w + s); s == 0: none
     int s, h, w;
@@ -50,13 +39,13 @@ __global__ __launch_bounds__(NT) void square_propose(float* __restrict__ x_try, 
                                                      int size, int steps, float eps, float lo, float hi, int closing) {
 #pragma clang fp contract(off)
     const int n = blockIdx.y;
-    const int k = ist[(long)I_K * N + n];
+    const int k = ist[(long)UD_SQUARE_I_K * N + n];
     Window prev{0, 0, 0}, next{0, 0, 0};
     int accepted = 0;
     float inc[3] = {0.f, 0.f, 0.f};
     if (k >= 2 && k <= steps + 1) {
         prev = load_window(side, dh, dw, k - 2, N, n, size);
-        accepted = ist[(long)I_ACCEPTED * N + n];
+        accepted = ist[(long)UD_SQUARE_I_ACCEPTED * N + n];
     }
     if (!closing && k >= 1 && k <= steps) {
         next = load_window(side, dh, dw, k - 1, N, n, size);
@@ -100,7 +89,7 @@ __global__ __launch_bounds__(64) void square_control(const float* __restrict__ f
                                                      int* __restrict__ decisions, int N, int steps, int early_stop) {
     const int n = blockIdx.x * 64 + threadIdx.x;
     if (n >= N) return;
-    const int k = ist[(long)I_K * N + n];
+    const int k = ist[(long)UD_SQUARE_I_K * N + n];
     if (k < 0 || k > steps) return;
     const float fk = f[n];
     float fbest;
@@ -109,17 +98,17 @@ __global__ __launch_bounds__(64) void square_control(const float* __restrict__ f
         fbest = fk;
         queries = 1;
     } else {
-        fbest = fst[(long)F_BEST * N + n];
-        const int active = ist[(long)I_ACTIVE * N + n];
-        queries = ist[(long)I_QUERIES * N + n] + (active ? 1 : 0);
+        fbest = fst[(long)UD_SQUARE_F_BEST * N + n];
+        const int active = ist[(long)UD_SQUARE_I_ACTIVE * N + n];
+        queries = ist[(long)UD_SQUARE_I_QUERIES * N + n] + (active ? 1 : 0);
         accepted = active && fk < fbest;
         if (accepted) fbest = fk;
     }
-    fst[(long)F_BEST * N + n] = fbest;
-    ist[(long)I_K * N + n] = k + 1;
-    ist[(long)I_ACCEPTED * N + n] = accepted;
-    ist[(long)I_ACTIVE * N + n] = early_stop ? (fbest > 0.f ? 1 : 0) : 1;
-    ist[(long)I_QUERIES * N + n] = queries;
+    fst[(long)UD_SQUARE_F_BEST * N + n] = fbest;
+    ist[(long)UD_SQUARE_I_K * N + n] = k + 1;
+    ist[(long)UD_SQUARE_I_ACCEPTED * N + n] = accepted;
+    ist[(long)UD_SQUARE_I_ACTIVE * N + n] = early_stop ? (fbest > 0.f ? 1 : 0) : 1;
+    ist[(long)UD_SQUARE_I_QUERIES * N + n] = queries;
     history[(long)k * N + n] = fk;
     decisions[(long)k * N + n] = accepted;
 }

@@ -43,25 +43,33 @@ def _check_precision(model, precision):
         raise ValueError(f"precision 'fp16' is built for UDEB4 only; {type(model).__name__} has no half-storage path")
 
 
+def _check_model(what, model, precision, arguments=None):
+    """What every runner (`what`: its name) asks of its model, in this order: one of the three models and a precision it has;
+    then arguments(), the runner's own refusals that need no device; then eval mode and a GPU.  Returns the model's device."""
+    from .model import MODEL
+    if not isinstance(model, tuple(MODEL.values())):
+        raise ValueError(f"{what} takes a UDEB4 / UDR18 / UDR50 model, got {type(model).__name__}")
+    _check_precision(model, precision)
+    if arguments is not None:
+        arguments()
+    if model.training:
+        raise ValueError(f"{what} needs model.eval(): the captured forward reads the running statistics")
+    p = next(model.parameters())
+    if not p.is_cuda:
+        raise ValueError(f"{what} needs a cuda model")
+    return p.device
+
+
 class InferenceRunner:
     """runner = InferenceRunner(model, batch, size[, precision]); out = runner(x) with x [batch, 3, size, size] fp32 on the
     model's GPU; out is the dict model(x) returns under no_grad ({"cls_out", "rec", "loss_dict"}, every tensor fp32), held in the
     runner's static buffers: the next call overwrites it (clone what must outlive it).  precision: "fp32" or "fp16" (UDEB4)."""
 
     def __init__(self, model, batch, size, precision="fp32"):
-        from .model import MODEL
-        if not isinstance(model, tuple(MODEL.values())):
-            raise ValueError(f"InferenceRunner takes a UDEB4 / UDR18 / UDR50 model, got {type(model).__name__}")
-        _check_precision(model, precision)
-        if model.training:
-            raise ValueError("InferenceRunner needs model.eval(): the captured forward reads the running statistics")
-        p = next(model.parameters())
-        if not p.is_cuda:
-            raise ValueError("InferenceRunner needs a cuda model")
+        self.device = _check_model("InferenceRunner", model, precision)
         self.model, self.batch, self.size, self.precision = model, int(batch), int(size), precision
         self.half = precision == "fp16"
         self.shape = (self.batch, 3, self.size, self.size)
-        self.device = p.device
         self.calls = 0
         self.graph = self.x = self.out = None
 

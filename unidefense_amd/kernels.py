@@ -1472,23 +1472,36 @@ def attack_project_l2(x_adv, x0, dss, eps, lo, hi):
     return x_adv
 
 
-# ---- Auto-PGD (csrc/apgd.hip): per-sample control state ist [5, N] int32 / fst [5, N] fp32, rows as in the header -------------
+# ---- per-sample control state of Auto-PGD and Square: ist [len(I), N] int32 / fst [len(F), N] fp32, I and F the attack's row
+# names (APGD_I / APGD_F, SQUARE_I / SQUARE_F: the header's UD_APGD_* / UD_SQUARE_* rows) -------------------------------------
+def _chk_i32(t, shape, what):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{what} must be a contiguous int32 CUDA tensor {list(shape)}, got {t.dtype} {t.device} {tuple(t.shape)}")
+
+
+def _chk_state(ist, fst, N, I, F):
+    """either may be None: an entry point that takes only the other"""
+    if ist is not None:
+        _chk_i32(ist, (len(I), N), "ist")
+    if fst is not None:
+        _chk(fst)
+        if tuple(fst.shape) != (len(F), N):
+            raise ValueError(f"fst must be [{len(F)}, {N}], got {tuple(fst.shape)}")
+
+
+def _state(N, device, I, F):
+    return (torch.zeros(len(I), N, dtype=torch.int32, device=device), torch.zeros(len(F), N, dtype=torch.float32, device=device))
+
+
+# ---- Auto-PGD (csrc/apgd.hip) -------------------------------------------------------------------------------------------------
 APGD_MAX_CHECKPOINTS = 16
 APGD_I = {"k": 0, "cnt": 1, "halved": 2, "improved": 3, "reset": 4}
 APGD_F = {"f_prev": 0, "f_best": 1, "f_ckpt": 2, "eta": 3, "a": 4}
 
 
-def _chk_apgd_state(ist, fst, N):
-    if not (ist.is_cuda and ist.dtype == torch.int32 and ist.is_contiguous() and tuple(ist.shape) == (5, N)):
-        raise ValueError(f"ist must be a contiguous int32 CUDA tensor [5, {N}], got {ist.dtype} {ist.device} {tuple(ist.shape)}")
-    _chk(fst)
-    if tuple(fst.shape) != (5, N):
-        raise ValueError(f"fst must be [5, {N}], got {tuple(fst.shape)}")
-
-
 def apgd_state(N, device):
     """(ist, fst): zeroed control state for N samples"""
-    return (torch.zeros(5, N, dtype=torch.int32, device=device), torch.zeros(5, N, dtype=torch.float32, device=device))
+    return _state(N, device, APGD_I, APGD_F)
 
 
 def apgd_control(f, ist, fst, history, steps, ck_w, ck_thr, eta0, alpha, closing=False):
@@ -1496,7 +1509,7 @@ def apgd_control(f, ist, fst, history, steps, ck_w, ck_thr, eta0, alpha, closing
     ck_w / ck_thr: the checkpoint iterations and their integer thresholds ceil(rho window), passed by value."""
     _chk(f, history)
     N = f.numel()
-    _chk_apgd_state(ist, fst, N)
+    _chk_state(ist, fst, N, APGD_I, APGD_F)
     if tuple(history.shape) != (int(steps) + 1, N):
         raise ValueError(f"history must be [{int(steps) + 1}, {N}], got {tuple(history.shape)}")
     n = len(ck_w)
@@ -1512,7 +1525,7 @@ def apgd_update_linf(x, x_prev, x_best, g_best, x0, g, ist, fst, eps, lo, hi):
     expression evaluated operation by operation."""
     _chk_same(x, x_prev, x_best, g_best, x0, g)
     N = x.shape[0]
-    _chk_apgd_state(ist, fst, N)
+    _chk_state(ist, fst, N, APGD_I, APGD_F)
     _call("ud_apgd_update_linf", _p(x), _p(x_prev), _p(x_best), _p(g_best), _p(x0), _p(g), _p(ist), _p(fst), N,
           x.numel() // N, float(eps), float(lo), float(hi), _stream())
     return x
@@ -1535,7 +1548,7 @@ def apgd_step_l2(x, z, x_best, g_best, gss_best, g, gss, ist, fst):
     N = x.shape[0]
     _chk_f64(gss, N)
     _chk_f64(gss_best, N)
-    _chk_apgd_state(ist, fst, N)
+    _chk_state(ist, fst, N, APGD_I, APGD_F)
     _call("ud_apgd_step_l2", _p(x), _p(z), _p(x_best), _p(g_best), _p(gss_best), _p(g), _p(gss), _p(ist), _p(fst), N,
           x.numel() // N, _stream())
     return z
@@ -1545,9 +1558,7 @@ def apgd_combine_l2(x, x_prev, z, fst):
     """x holds src, z the projected step: x <- z where a == 1, else src + a (z - src) + (1 - a)(src - x_prev); x_prev <- src"""
     _chk_same(x, x_prev, z)
     N = x.shape[0]
-    _chk(fst)
-    if tuple(fst.shape) != (5, N):
-        raise ValueError(f"fst must be [5, {N}], got {tuple(fst.shape)}")
+    _chk_state(None, fst, N, APGD_I, APGD_F)
     _call("ud_apgd_combine_l2", _p(x), _p(x_prev), _p(z), _p(fst), N, x.numel() // N, _stream())
     return x
 
@@ -1557,34 +1568,19 @@ def apgd_project_l2(x, x0, dss, fst, eps, lo, hi):
     _chk_same(x, x0)
     N = x.shape[0]
     _chk_f64(dss, N)
-    _chk(fst)
-    if tuple(fst.shape) != (5, N):
-        raise ValueError(f"fst must be [5, {N}], got {tuple(fst.shape)}")
+    _chk_state(None, fst, N, APGD_I, APGD_F)
     _call("ud_apgd_project_l2", _p(x), _p(x0), _p(dss), _p(fst), N, x.numel() // N, float(eps), float(lo), float(hi), _stream())
     return x
 
 
-# ---- Square attack (csrc/square.hip): per-sample control state ist [4, N] int32 / fst [1, N] fp32, rows as in the header -------
+# ---- Square attack (csrc/square.hip) ------------------------------------------------------------------------------------------
 SQUARE_I = {"k": 0, "accepted": 1, "active": 2, "queries": 3}
 SQUARE_F = {"f_best": 0}
 
 
-def _chk_i32(t, shape, what):
-    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
-        raise ValueError(f"{what} must be a contiguous int32 CUDA tensor {list(shape)}, got {t.dtype} {t.device} {tuple(t.shape)}")
-
-
-def _chk_square_state(ist, fst, N):
-    _chk_i32(ist, (len(SQUARE_I), N), "ist")
-    _chk(fst)
-    if tuple(fst.shape) != (len(SQUARE_F), N):
-        raise ValueError(f"fst must be [{len(SQUARE_F)}, {N}], got {tuple(fst.shape)}")
-
-
 def square_state(N, device):
     """(ist, fst): zeroed control state for N samples"""
-    return (torch.zeros(len(SQUARE_I), N, dtype=torch.int32, device=device),
-            torch.zeros(len(SQUARE_F), N, dtype=torch.float32, device=device))
+    return _state(N, device, SQUARE_I, SQUARE_F)
 
 
 def square_propose(x_try, x_best, x0, ist, side, dh, dw, dsign, eps, lo, hi, closing=False):
@@ -1595,7 +1591,7 @@ def square_propose(x_try, x_best, x0, ist, side, dh, dw, dsign, eps, lo, hi, clo
     if x_try.dim() != 4 or x_try.shape[1] != 3 or x_try.shape[2] != x_try.shape[3]:
         raise ValueError(f"expected [N, 3, size, size] images, got {tuple(x_try.shape)}")
     N, size, steps = x_try.shape[0], x_try.shape[2], side.numel()
-    _chk_i32(ist, (len(SQUARE_I), N), "ist")
+    _chk_state(ist, None, N, SQUARE_I, SQUARE_F)
     _chk_i32(side, (steps,), "side")
     _chk_i32(dh, (steps, N), "dh")
     _chk_i32(dw, (steps, N), "dw")
@@ -1612,7 +1608,7 @@ def square_control(f, ist, fst, history, decisions, steps, early_stop=True):
     the query, recompute who is still searched (early_stop: f_best > 0), record history / decisions row k."""
     _chk(f, history)
     N = f.numel()
-    _chk_square_state(ist, fst, N)
+    _chk_state(ist, fst, N, SQUARE_I, SQUARE_F)
     if tuple(history.shape) != (int(steps) + 1, N):
         raise ValueError(f"history must be [{int(steps) + 1}, {N}], got {tuple(history.shape)}")
     _chk_i32(decisions, (int(steps) + 1, N), "decisions")

@@ -212,7 +212,43 @@ class _NetFunction(torch.autograd.Function):
         return (None, dx, None, None) + tuple(grads)
 
 
-class UniDefenseModelEb4(nn.Module):
+class RunnerMethods:
+    """The graph-replayed runners of a model, each cached per argument tuple in a dictionary of its own (unidefense_amd/infer.py,
+    unidefense_amd/attack.py).  precision "fp16": UDEB4 only (the ResNet variants have no half-storage path: ValueError)."""
+
+    def inference_runner(self, batch, size, precision="fp32"):
+        """The graph-captured eval forward for [batch, 3, size, size] inputs (InferenceRunner); precision "fp16": the MBConv
+        trunk in half storage (tape.mbconv_eval_half)."""
+        from ..infer import inference_runner
+        return inference_runner(self, batch, size, precision)
+
+    def input_grad_runner(self, batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
+        """The graph-replayed gradient of objective(model(x), y) with respect to x for [batch, 3, size, size] inputs
+        (InputGradRunner).  precision "fp16": the MBConv trunk's forward and backward in half storage (tape.mbconv_frozen_half),
+        the objective scaled by grad_scale (default 1024) and the result unscaled."""
+        from ..attack import input_grad_runner
+        return input_grad_runner(self, batch, size, objective, precision, grad_scale)
+
+    def attack_runner(self, batch, size, **kwargs):
+        """The graph-replayed FGSM / PGD attack for [batch, 3, size, size] inputs (AttackRunner; kwargs: norm, eps, steps, step,
+        random_start, targeted, clip, objective, precision, grad_scale)."""
+        from ..attack import attack_runner
+        return attack_runner(self, batch, size, **kwargs)
+
+    def apgd_runner(self, batch, size, **kwargs):
+        """The graph-replayed Auto-PGD (APGD-CE) attack for [batch, 3, size, size] inputs (APGDRunner; kwargs: norm, eps, steps,
+        restarts, random_start, rho, alpha, targeted, clip, objective, precision, grad_scale)."""
+        from ..attack import apgd_runner
+        return apgd_runner(self, batch, size, **kwargs)
+
+    def square_runner(self, batch, size, **kwargs):
+        """The graph-replayed Square attack (black-box, L-infinity, forward only) for [batch, 3, size, size] inputs
+        (SquareRunner; kwargs: eps, steps, p_init, restarts, early_stop, check_every, clip, objective, precision)."""
+        from ..attack import square_runner
+        return square_runner(self, batch, size, **kwargs)
+
+
+class UniDefenseModelEb4(RunnerMethods, nn.Module):
     """UniDefense model with EfficientNet backbone (reference: model/unidefense.py:28-256)."""
 
     path = "model/unidefense.py"
@@ -266,39 +302,6 @@ class UniDefenseModelEb4(nn.Module):
 
         if extractor_weights is not None:
             self.load_backbone_weights(extractor_weights)
-
-    def inference_runner(self, batch, size, precision="fp32"):
-        """The graph-captured eval forward for [batch, 3, size, size] inputs (unidefense_amd/infer.py: InferenceRunner);
-        precision "fp16": the MBConv trunk in half storage (tape.mbconv_eval_half)."""
-        from ..infer import inference_runner
-        return inference_runner(self, batch, size, precision)
-
-    def input_grad_runner(self, batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
-        """The graph-replayed gradient of objective(model(x), y) with respect to x for [batch, 3, size, size] inputs
-        (unidefense_amd/attack.py: InputGradRunner), cached per argument tuple.  precision "fp16": the MBConv trunk's forward and
-        backward in half storage (tape.mbconv_frozen_half), the objective scaled by grad_scale (default 1024) and the result unscaled."""
-        from ..attack import input_grad_runner
-        return input_grad_runner(self, batch, size, objective, precision, grad_scale)
-
-    def attack_runner(self, batch, size, **kwargs):
-        """The graph-replayed FGSM / PGD attack for [batch, 3, size, size] inputs (unidefense_amd/attack.py: AttackRunner;
-        kwargs: norm, eps, steps, step, random_start, targeted, clip, objective, precision, grad_scale), cached per argument tuple."""
-        from ..attack import attack_runner
-        return attack_runner(self, batch, size, **kwargs)
-
-    def apgd_runner(self, batch, size, **kwargs):
-        """The graph-replayed Auto-PGD (APGD-CE) attack for [batch, 3, size, size] inputs (unidefense_amd/attack.py: APGDRunner;
-        kwargs: norm, eps, steps, restarts, random_start, rho, alpha, targeted, clip, objective, precision, grad_scale), cached per
-        argument tuple in a dictionary of its own."""
-        from ..attack import apgd_runner
-        return apgd_runner(self, batch, size, **kwargs)
-
-    def square_runner(self, batch, size, **kwargs):
-        """The graph-replayed Square attack (black-box, L-infinity, forward only) for [batch, 3, size, size] inputs
-        (unidefense_amd/attack.py: SquareRunner; kwargs: eps, steps, p_init, restarts, early_stop, check_every, clip, objective,
-        precision), cached per argument tuple in a dictionary of its own."""
-        from ..attack import square_runner
-        return square_runner(self, batch, size, **kwargs)
 
     # -- pretrained backbone (model/efficientnet/utils.py:589-634): missing sf_coef / freq_conv keys tolerated
     def load_backbone_weights(self, path):

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .. import kernels as K
 from .. import tape as T
-from .unidefense import Classifier, UniDefenseModelEb4, _FilterParams
+from .unidefense import Classifier, RunnerMethods, UniDefenseModelEb4, _FilterParams
 
 
 class _SFConv2dParams(nn.Conv2d):
@@ -99,7 +99,7 @@ def _dec2(bias=False, affine=True):
                          nn.Conv2d(32, 3, 3, 1, 1, bias=bias), nn.Identity())
 
 
-class UniDefenseModelRes18(nn.Module):
+class UniDefenseModelRes18(RunnerMethods, nn.Module):
     """UniDefense model with ResNet18 backbone (reference: model/unidefense.py:259-436)."""
 
     path = "model/unidefense.py"
@@ -147,40 +147,6 @@ class UniDefenseModelRes18(nn.Module):
             bad = [k for k in ret.missing_keys if "sf_coef" not in k and "freq_conv" not in k]
             if bad:
                 raise RuntimeError(f"pretrained weights mismatch: missing {bad}")
-
-    def inference_runner(self, batch, size, precision="fp32"):
-        """The graph-captured eval forward for [batch, 3, size, size] inputs (unidefense_amd/infer.py: InferenceRunner);
-        fp32 only (precision "fp16" raises ValueError: the ResNet variants have no half-storage path)."""
-        from ..infer import inference_runner
-        return inference_runner(self, batch, size, precision)
-
-    def input_grad_runner(self, batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
-        """The graph-replayed gradient of objective(model(x), y) with respect to x for [batch, 3, size, size] inputs
-        (unidefense_amd/attack.py: InputGradRunner), cached per argument tuple.  fp32 only (precision "fp16" raises ValueError:
-        the ResNet variants have no half-storage path)."""
-        from ..attack import input_grad_runner
-        return input_grad_runner(self, batch, size, objective, precision, grad_scale)
-
-    def attack_runner(self, batch, size, **kwargs):
-        """The graph-replayed FGSM / PGD attack for [batch, 3, size, size] inputs (unidefense_amd/attack.py: AttackRunner;
-        kwargs: norm, eps, steps, step, random_start, targeted, clip, objective, precision — "fp32" only here), cached per
-        argument tuple."""
-        from ..attack import attack_runner
-        return attack_runner(self, batch, size, **kwargs)
-
-    def apgd_runner(self, batch, size, **kwargs):
-        """The graph-replayed Auto-PGD (APGD-CE) attack for [batch, 3, size, size] inputs (unidefense_amd/attack.py: APGDRunner;
-        kwargs: norm, eps, steps, restarts, random_start, rho, alpha, targeted, clip, objective), cached per argument tuple in a
-        dictionary of its own.  fp32 only."""
-        from ..attack import apgd_runner
-        return apgd_runner(self, batch, size, **kwargs)
-
-    def square_runner(self, batch, size, **kwargs):
-        """The graph-replayed Square attack (black-box, L-infinity, forward only) for [batch, 3, size, size] inputs
-        (unidefense_amd/attack.py: SquareRunner; kwargs: eps, steps, p_init, restarts, early_stop, check_every, clip, objective,
-        precision), cached per argument tuple in a dictionary of its own."""
-        from ..attack import square_runner
-        return square_runner(self, batch, size, **kwargs)
 
     # ---------------------------------------------------------------------------------------
     def _conv(self, tape, x, conv, stride):
