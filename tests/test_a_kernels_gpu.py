@@ -853,3 +853,50 @@ def test_conv_as_im2col_planes_gemm(N, H, Ci, Co, k, stride, pad):
         check(f"{tag}: y", to_nchw(outs[0]), yr)
         check(f"{tag}: dx", to_nchw(gin[0]), xr.grad)
         check(f"{tag}: dw", gp[0], wr.grad)
+
+
+# ---------------------------------------------------------------------------------------------
+# scratch buffers under captured graphs (unidefense_amd/devmem.py): a graph keeps the pointer it was captured with
+# ---------------------------------------------------------------------------------------------
+def _scratch_rfft2_planes(K, dev, g):
+    shapes = [(1, 128, 128), (4, 128, 128)]
+    return "_FFT_PLANES_WS", [(torch.randn(*s, generator=g).to(dev),) for s in shapes], K.dft_rfft2_planes
+
+
+def _scratch_dwtile_bwd_weight(K, dev, g):
+    shapes = [(1, 8, 8, 8), (2, 16, 16, 8)]
+    args = [(torch.randn(*s, generator=g).to(dev), torch.randn(*s, generator=g).to(dev)) for s in shapes]
+    return "_WGRAD_PART_WS", args, lambda x, dy: K.dwtile_bwd_weight(x, dy, 3, 1, 1)
+
+
+@pytest.mark.parametrize("case", [_scratch_rfft2_planes, _scratch_dwtile_bwd_weight])
+def test_scratch_growth_keeps_a_captured_graphs_buffer(case, monkeypatch):
+    """A graph captured at shape A replays bit for bit after a larger shape B regrew the op's scratch and other tensors of the old
+    scratch's size were allocated and filled: the superseded buffer stays owned by the Scratch, nobody else gets its block."""
+    from unidefense_amd import kernels as K
+    from unidefense_amd.devmem import Scratch
+    dev = _dev()
+    name, (a, b), fn = case(K, dev, torch.Generator().manual_seed(5))
+    ws = Scratch(torch.float32)          # a fresh one: earlier tests of the process have grown the module's own past both shapes
+    monkeypatch.setattr(K, name, ws)
+    assert K._WGRAD_FOLDS is None
+    eager_a = fn(*a).clone()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = fn(*a)
+    graph.replay()
+    r1 = out.clone()
+    assert torch.equal(r1, eager_a)
+    old = ws.current[dev.index]
+    old_ptr, old_bytes = old.data_ptr(), old.numel() * old.element_size()
+    eager_b = fn(*b).clone()
+    # host checks first: the replay below may only ever touch memory the process still owns
+    assert ws.current[dev.index].data_ptr() != old_ptr, "shape B did not regrow the scratch: the test would test nothing"
+    assert any(t.data_ptr() == old_ptr and t.numel() == old.numel() for t in ws.retired[dev.index])
+    del old
+    sentinels = [torch.full((old_bytes,), 0xA5, dtype=torch.uint8, device=dev) for _ in range(2)]
+    graph.replay()
+    assert torch.equal(out, r1)
+    for s in sentinels:
+        assert bool((s == 0xA5).all())
+    assert torch.equal(fn(*b), eager_b)

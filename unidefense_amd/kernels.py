@@ -13,6 +13,7 @@ import torch
 
 from . import lib as _lib
 from .config import cfg as CFG
+from .devmem import Scratch, ZeroPool
 from .lib import ConvGeom, GemmDesc, GemmP3Desc
 
 _call = _lib.call
@@ -23,12 +24,6 @@ GEMM_PROFILE = None
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-# Every scratch buffer / zero pool below is keyed by the device and shared by the launches of its ONE stream in order: a
-# reduction's finalize launch has consumed the scratch before the next reduction starts.
-def _key(ref):
-    return ref.device.index
 
 
 def _p(t):
@@ -66,55 +61,22 @@ def empty(shape, like, dtype=torch.float32):
     return torch.empty(shape, dtype=dtype, device=like.device)
 
 
-# Zero-initialised outputs of the split-K launches (atomic accumulation): ~180 per step, each a 5 us fill launch of
-# its own.  They are carved instead from a few large zero blocks (one fill per 32 MB); a block is never reused, so
-# every carve is still zero.  reset_zero_pool() at the start of a forward / backward makes a step captured into a
-# hipGraph contain the fills of every block it carves from.
-_ZERO_BLOCK = 8 << 20            # floats per block (32 MB)
-_ZERO_OWN = 2 << 20              # tensors of at least this many floats get their own torch.zeros
-_ZERO_POOL = {}
+_ZEROS = ZeroPool(torch.float32, 8 << 20, 64, own_elems=2 << 20)          # split-K results (atomic accumulation): 32 MB blocks
+_ZEROS64 = ZeroPool(torch.float64, 1 << 20, 32)          # fp64 accumulators of the fused path (BatchNorm / SE sums, gate gradients)
 
 
 def reset_zero_pool():
-    _ZERO_POOL.clear()
-    _ZERO64_POOL.clear()
-
-
-# fp64 accumulators of the fused path (BatchNorm sums, SE pooling sums, gate gradients): carved from zero blocks the
-# same way — one fill per block instead of one per accumulator (~10 accumulators per MBConv block and pass).
-_ZERO64_BLOCK = 1 << 20        # doubles per block (8 MB)
-_ZERO64_POOL = {}
+    _ZEROS.reset()
+    _ZEROS64.reset()
 
 
 def zeros64(n, like):
     """n zero-initialised doubles (a view; never recycled within a forward / backward)."""
-    n = int(n)
-    key = _key(like)
-    st = _ZERO64_POOL.get(key)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if st is None or st[1] + n > st[0].numel() or st[2] != capturing:
-        st = _ZERO64_POOL[key] = [torch.zeros(max(_ZERO64_BLOCK, n), dtype=torch.float64, device=like.device), 0,
-                                  capturing]
-    out = st[0][st[1]:st[1] + n]
-    st[1] += (n + 31) // 32 * 32
-    return out
+    return _ZEROS64.take(n, like)
 
 
 def zeros(shape, like):
-    n = 1
-    for d in shape:
-        n *= int(d)
-    if n >= _ZERO_OWN or n == 0:
-        return torch.zeros(shape, dtype=torch.float32, device=like.device)
-    key = _key(like)
-    st = _ZERO_POOL.get(key)
-    capturing = torch.cuda.is_current_stream_capturing()
-    # a block filled outside a capture must not serve carves inside one (the replay would not re-zero it), nor vice versa
-    if st is None or st[1] + n > _ZERO_BLOCK or st[2] != capturing:
-        st = _ZERO_POOL[key] = [torch.zeros(_ZERO_BLOCK, dtype=torch.float32, device=like.device), 0, capturing]
-    out = st[0][st[1]:st[1] + n].view(shape)
-    st[1] += (n + 63) // 64 * 64
-    return out
+    return _ZEROS.take(math.prod(int(d) for d in shape), like).view(shape)
 
 
 def split_out(shape, like):
@@ -135,14 +97,8 @@ def split_out(shape, like):
 # give the same result on every run and box (the fp64 accumulators of the fused MBConv path are order-dependent at 1e-16
 # only).  Default (False): fp32 atomics — one launch less per split GEMM (2.3 ms of the 35.8 ms deterministic bs-32 step),
 # last-bit run-to-run variation.
-_SLICE_WS = {}
-
-
-def _slice_ws(ref, n):
-    ws = _SLICE_WS.get(_key(ref))
-    if ws is None or ws.numel() < n:
-        ws = _SLICE_WS[_key(ref)] = torch.empty(max(n, 1 << 22), dtype=torch.float32, device=ref.device)
-    return ws
+_SLICE_WS = Scratch(torch.float32, 1 << 22)
+_slice_ws = _SLICE_WS.get
 
 
 def _gemm(A, B, Cout, M, N, K, lda, ldb, ldc, a_mode, b_mode, out_mode=0, split_k=1, geom=None,
@@ -1309,7 +1265,7 @@ def _conv_small_supported(Ci, Co, KH, KW):
     return _CONV_SMALL_OK[key]
 
 
-_CONV_SMALL_WS = {}
+_CONV_SMALL_WS = Scratch(torch.float32)
 _CONV_SMALL_WGRAD_OK = {}
 
 
@@ -1624,10 +1580,7 @@ def conv_gather_wgrad(a, x, g):
     Ncols = g.KH * g.KW * g.Cin
     if _CONV_SMALL and Kdim >= _CONV_SMALL_MIN_M and _conv_small_wgrad_supported(g.Cin, Ma, g.KH, g.KW):
         # a 20 x 180 (3 x 180, 48 x 27) result reduced over 524 288 rows: streamed through LDS, register-blocked
-        need = _call("ud_conv_small_wgrad_ws_floats", g.Cin, Ma)
-        ws = _CONV_SMALL_WS.get(_key(a))
-        if ws is None or ws.numel() < need:
-            ws = _CONV_SMALL_WS[_key(a)] = empty((need,), a)
+        ws = _CONV_SMALL_WS.get(a, _call("ud_conv_small_wgrad_ws_floats", g.Cin, Ma))
         out = empty((Ma, Ncols), a)
         _call("ud_conv_small_wgrad", C.byref(g), _p(a), _p(x), _p(ws), _p(out), Ma, _stream())
         return out
@@ -1657,19 +1610,17 @@ def conv_gather_wgrad(a, x, g):
 # ---------------------------------------------------------------------------------------------
 # normalisation / column reductions
 # ---------------------------------------------------------------------------------------------
-_REDUCE_WS = {}          # device -> fp64 scratch shared by every column reduction
-_REDUCE_WS_MIN = 1 << 20
+_REDUCE_WS = Scratch(torch.float64, 1 << 20)          # shared by every column reduction and fused fp64 partial sum
+
+
+def _ws64(ref, need):
+    """Pointer to `need` doubles of scratch (None for need <= 0: the launch runs without)."""
+    return _p(_REDUCE_WS.get(ref, need)) if need > 0 else None
 
 
 def _reduce_ws(ref, G, R, Cc):
-    """Scratch for the per-workgroup partial sums (include/unidefense_hip.h): a reduction's finalize launch has
-    consumed it before the next reduction on the stream starts, so one buffer per device serves all calls."""
-    need = _call("ud_reduce_ws_doubles", G, R, Cc)
-    ws = _REDUCE_WS.get(_key(ref))
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, _REDUCE_WS_MIN), dtype=torch.float64, device=ref.device)
-        _REDUCE_WS[_key(ref)] = ws
-    return ws
+    """Scratch for the per-workgroup partial sums (include/unidefense_hip.h)."""
+    return _ws64(ref, _call("ud_reduce_ws_doubles", G, R, Cc))
 
 
 def norm_stats(x2, G, R, eps, momentum=0.0, running_mean=None, running_var=None):
@@ -1678,7 +1629,7 @@ def norm_stats(x2, G, R, eps, momentum=0.0, running_mean=None, running_var=None)
     Cc = x2.shape[-1]
     mean = empty((G, Cc), x2)
     invstd = empty((G, Cc), x2)
-    _call("ud_norm_stats", _p(x2), G, R, Cc, eps, _p(_reduce_ws(x2, G, R, Cc)), _p(mean), _p(invstd), None,
+    _call("ud_norm_stats", _p(x2), G, R, Cc, eps, _reduce_ws(x2, G, R, Cc), _p(mean), _p(invstd), None,
           momentum, _p(running_mean), _p(running_var), _stream())
     return mean, invstd
 
@@ -1690,7 +1641,7 @@ def norm_stats_local(x2, G, R, eps):
     Cc = x2.shape[-1]
     mv = empty((2, G, Cc), x2)
     invstd = empty((G, Cc), x2)
-    _call("ud_norm_stats", _p(x2), G, R, Cc, eps, _p(_reduce_ws(x2, G, R, Cc)), _p(mv[0]), _p(invstd), _p(mv[1]),
+    _call("ud_norm_stats", _p(x2), G, R, Cc, eps, _reduce_ws(x2, G, R, Cc), _p(mv[0]), _p(invstd), _p(mv[1]),
           0.0, None, None, _stream())
     return mv
 
@@ -1713,7 +1664,7 @@ def norm_bwd_sums(x2, dy, G, R, mean, invstd, gamma, beta, act):
     dg = empty((Cc,), x2)
     db = empty((Cc,), x2)
     _call("ud_norm_bwd", _p(x2), _p(dy), G, R, Cc, _p(mean), _p(invstd), _p(gamma), _p(beta), int(act),
-          _p(_reduce_ws(x2, G, R, Cc)), _p(s[0]), _p(s[1]), _p(dg), _p(db), None, _stream())
+          _reduce_ws(x2, G, R, Cc), _p(s[0]), _p(s[1]), _p(dg), _p(db), None, _stream())
     return s, dg, db
 
 
@@ -1742,7 +1693,7 @@ def norm_bwd(x2, dy, G, R, mean, invstd, gamma, beta, act):
     db = empty((Cc,), x2)
     dx = torch.empty_like(x2)
     _call("ud_norm_bwd", _p(x2), _p(dy), G, R, Cc, _p(mean), _p(invstd), _p(gamma), _p(beta), int(act),
-          _p(_reduce_ws(x2, G, R, Cc)), _p(s[0]), _p(s[1]), _p(dg), _p(db), _p(dx), _stream())
+          _reduce_ws(x2, G, R, Cc), _p(s[0]), _p(s[1]), _p(dg), _p(db), _p(dx), _stream())
     return dx, dg, db
 
 
@@ -1750,7 +1701,7 @@ def group_colsum(x2, G, R, scale):
     _chk(x2)
     Cc = x2.shape[-1]
     out = empty((G, Cc), x2)
-    _call("ud_group_colsum", _p(x2), G, R, Cc, scale, _p(_reduce_ws(x2, G, R, Cc)), _p(out), _stream())
+    _call("ud_group_colsum", _p(x2), G, R, Cc, scale, _reduce_ws(x2, G, R, Cc), _p(out), _stream())
     return out
 
 
@@ -1758,7 +1709,7 @@ def group_coldot(a2, b2, G, R, scale=1.0):
     _chk(a2, b2)
     Cc = a2.shape[-1]
     out = empty((G, Cc), a2)
-    _call("ud_group_coldot", _p(a2), _p(b2), G, R, Cc, scale, _p(_reduce_ws(a2, G, R, Cc)), _p(out), _stream())
+    _call("ud_group_coldot", _p(a2), _p(b2), G, R, Cc, scale, _reduce_ws(a2, G, R, Cc), _p(out), _stream())
     return out
 
 
@@ -2294,16 +2245,12 @@ def _dft_mats(S, device, ortho=True):
     return mats
 
 
-_FFT_PLANES_WS = {}
+_FFT_PLANES_WS = Scratch(torch.float32)
 _FFT_PLANES_SIZES = (128, 256, 320)          # csrc/fft_large.hip
 
 
 def _fft_planes_ws(ref, P, S):
-    need = _call("ud_rfft2_planes_ws_floats", P, S)
-    ws = _FFT_PLANES_WS.get(_key(ref))
-    if ws is None or ws.numel() < need:
-        ws = _FFT_PLANES_WS[_key(ref)] = empty((need,), ref)
-    return ws
+    return _FFT_PLANES_WS.get(ref, _call("ud_rfft2_planes_ws_floats", P, S))
 
 
 def dft_rfft2_planes(d, ortho=True):
@@ -2523,7 +2470,7 @@ def loss_tail(cls_out, tgt, n_real, n_fake, feats, fm, sm, spatial, freq, weight
 # ---------------------------------------------------------------------------------------------
 # pass-2 input perturbations on NCHW planes (perturb.hip; model/unidefense.py:177-198 of the reference)
 # ---------------------------------------------------------------------------------------------
-_PERTURB_WS = {}
+_PERTURB_WS = Scratch(torch.uint8)
 
 
 def gather2d(x, iy, ix):
@@ -2559,11 +2506,7 @@ def efdm(content, style, lmda, rows_per_sample):
     _chk(content, style, lmda)
     rows, L = content.shape
     assert style.shape == content.shape and lmda.numel() * rows_per_sample == rows
-    need = _call("ud_efdm_ws_bytes", rows, L)
-    key = content.device.index
-    ws = _PERTURB_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _PERTURB_WS[key] = torch.empty(need, dtype=torch.uint8, device=content.device)
+    ws = _PERTURB_WS.get(content, _call("ud_efdm_ws_bytes", rows, L))
     out = torch.empty_like(content)
     _call("ud_efdm", _p(content), _p(style), _p(lmda), _p(out), rows, L, rows_per_sample, _p(ws), ws.numel(), _stream())
     return out
@@ -2696,16 +2639,6 @@ def _fused_ws(ref, G, R, C_, per_group, min_rows=8):
     """Scratch pointer for the two-launch form of a fused reduction (None when it runs as one launch of atomics)."""
     need = _call("ud_fused_reduce_ws_doubles", G, R, C_, int(per_group), min_rows)
     return _ws64(ref, need)
-
-
-def _ws64(ref, need):
-    if need <= 0:
-        return None
-    ws = _REDUCE_WS.get(_key(ref))
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, _REDUCE_WS_MIN), dtype=torch.float64, device=ref.device)
-        _REDUCE_WS[_key(ref)] = ws
-    return C.c_void_p(ws.data_ptr())
 
 
 def colstats(x2, acc, G=1, R=None):
@@ -3205,15 +3138,13 @@ def dwtile_dgrad_eval(dy, wt, K, pad_t, pad_l, x, bn, gate_alpha=None, gate_mode
     return dx
 
 
-_DWTILE_PART = {}
-
-
 # The depthwise weight gradients come out of their kernels as partial rows [parts][K*K][C] that a small launch folds into the
 # parameter's layout: 47 such launches per UDEB4 backward (~5 us each, the floor).  While a tape's backward collects them
 # (begin_wgrad_folds ... flush_wgrad_folds: Tape.backward), every conv keeps its rows in a buffer of its own and ONE launch folds
 # them all at the end (ud_dwtile_wgrad_finalize_multi).  A gradient that is read before the end — a second use of the parameter,
 # a data-parallel reducer taking it as soon as it is complete — flushes first (Tape.add_param_grad).
 _WGRAD_FOLDS = None
+_WGRAD_PART_WS = Scratch(torch.float32)
 
 
 def begin_wgrad_folds():
@@ -3243,10 +3174,7 @@ def _wgrad_part(like, need):
     """the partial-row buffer of one depthwise weight gradient: the shared scratch, or (folds being collected) its own"""
     if _WGRAD_FOLDS is not None:
         return torch.empty(need, dtype=torch.float32, device=like.device), True
-    part = _DWTILE_PART.get(_key(like))
-    if part is None or part.numel() < need:
-        part = _DWTILE_PART[_key(like)] = torch.empty(need, dtype=torch.float32, device=like.device)
-    return part, False
+    return _WGRAD_PART_WS.get(like, need), False
 
 
 def _defer_wgrad_fold(part, nparts, K_, Cc, gate_alpha, gate_mode, dwt):
