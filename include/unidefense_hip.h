@@ -514,6 +514,68 @@ int ud_apgd_combine_l2(float* x, float* x_prev, const float* z, const float* fst
 int ud_apgd_project_l2(float* x, const float* x0, const double* dss, const float* fst, int N, long per, float eps, float lo,
                        float hi, ud_stream_t stream);
 
+/* ---- Fast Minimum-Norm attack (csrc/fmn.hip; unidefense_amd/attack.py: FMNRunner) ------------------------------------
+ * The smallest perturbation that makes each sample adversarial (objective f < 0), norm UD_FMN_LINF or UD_FMN_L2.  The budget
+ * eps is per-sample device state, so that one iteration is a static launch sequence inside a captured graph:
+ *   ist [3][N] int32 : rows UD_FMN_I_K (iteration index), _FOUND (some iterate was adversarial), _IMPROVED (this iterate is
+ *                      the sample's best: what ud_fmn_update and ud_apgd_keep obey)
+ *   fst [2][N] fp32  : rows UD_FMN_F_EPS (the budget of this iteration's projection), _BEST (the smallest adversarial norm)
+ *   fac [N] double   : alpha_k / max(|g|_2, 1e-12), the factor of this iteration's step
+ *   history [steps + 1][N] fp32 : row k = f_k, row steps = f of the closing evaluation;  eps_history [steps][N] fp32: eps_k
+ *   alpha, gamma [steps] fp32 (device tables, indexed with the sample's own counter), worst [N] fp32 (the cap on eps)
+ * ud_fmn_norm_parts: x, x0, g fp32 [N][per].  For part p (UD_FMN_CHUNK elements) of sample n, ws[(n parts + p) UD_FMN_PARTS +
+ *   j], parts = ceil(per / UD_FMN_CHUNK), holds as doubles j = UD_FMN_P_GSS: sum g^2, _GABS: sum |g|, _DSS: sum (x - x0)^2,
+ *   _DMAX: max |x - x0|.  Differences, squares and sums in double; the maximum keeps a NaN; a fixed tree (thread order, wave
+ *   shuffles, waves in order), no atomics.  g == NULL writes the two d entries only.  float4 loads where per % 4 == 0 and all
+ *   bases are 16-byte aligned, scalar loads otherwise.  ws holds ud_fmn_norms_ws_bytes(N, per) bytes (ws_bytes: what the
+ *   caller holds); there is no fold launch: ud_fmn_control adds a sample's parts itself.
+ * ud_fmn_control: f [N] fp32 at the current point, ws as ud_fmn_norm_parts left it.  One thread per sample, every operation
+ *   below in double with one rounding (no contraction) unless it says fp32; (float) is round-to-nearest-even:
+ *     GSS, GABS, DSS = 0.0 + part 0 + part 1 + ... in index order;  DMAX = m(... m(m(0.0, part 0), part 1) ...) with
+ *     m(a, v) = v if v is NaN or v > a, else a;       dn = (float)(l2 ? sqrt(DSS) : DMAX)      (sqrt correctly rounded)
+ *     k = ist[K][n]; k outside [0, steps) writes nothing.  k == 0: eps = best = +inf (fp32), found = 0; else as stored.
+ *     adv = f < 0 (fp32);  improved = adv && dn < best (fp32);  improved: best = dn
+ *     g = (double)gamma[k], E = (double)eps, q = l2 ? sqrt(GSS) : GABS
+ *     adv: t = E (1 - g); e = t < (double)best ? t : (double)best       else found: e = E (1 + g)
+ *     else: e = (double)dn + |(double)f| / (q < 1e-12 ? 1e-12 : q)
+ *     w = (double)worst[n]; e = w < e ? w : e;   e == e (not NaN): eps = (float)e;   found |= adv
+ *     fac[n] = (double)alpha[k] / (s < 1e-12 ? 1e-12 : s), s = sqrt(GSS)          (a NaN norm gives a NaN factor)
+ *     stored: fst[EPS] = eps, fst[BEST] = best, ist[K] = k + 1, ist[FOUND], ist[IMPROVED], history[k][n] = f, eps_history[k][n] = eps
+ *   A NaN f is never adversarial.  The caller zeroes row UD_FMN_I_K to start a run.  closing != 0 (any k): the GSS / GABS
+ *   entries are not read; adv, improved and best as above from the stored state; stored: fst[BEST], ist[FOUND] |= adv,
+ *   ist[IMPROVED], history[steps][n] = f — nothing else.
+ * ud_fmn_update: one pass over [N][per].  improved: x_best <- x.  Then t = (double)g fac[n], z = (float)((double)x - t) (product
+ *   and difference rounded once each), UD_FMN_LINF: x <- clamp(clamp(z, x0 - eps[n], x0 + eps[n]), lo, hi) as
+ *   ud_attack_step_linf evaluates it (an infinite eps[n] projects nothing); UD_FMN_L2: x <- z (projected by ud_sample_sumsq(x, x0)
+ *   + ud_fmn_project_l2 next).  A NaN gradient element stays a NaN in x at that element.
+ * ud_fmn_project_l2: ud_attack_project_l2 with the budget read per sample from fst[UD_FMN_F_EPS] (the same per-element
+ *   functions: a finite equal eps gives its bits; an infinite eps leaves the clip only).
+ * UD_EINVAL before any HIP call: a NULL pointer (g of ud_fmn_norm_parts excepted), N < 1, per < 1, steps < 1, a norm that is
+ * neither, lo > hi or NaN, ws_bytes < ud_fmn_norms_ws_bytes(N, per). */
+#define UD_FMN_CHUNK 4096
+#define UD_FMN_PARTS 4
+#define UD_FMN_P_GSS 0
+#define UD_FMN_P_GABS 1
+#define UD_FMN_P_DSS 2
+#define UD_FMN_P_DMAX 3
+#define UD_FMN_LINF 0
+#define UD_FMN_L2 1
+#define UD_FMN_I_K 0
+#define UD_FMN_I_FOUND 1
+#define UD_FMN_I_IMPROVED 2
+#define UD_FMN_F_EPS 0
+#define UD_FMN_F_BEST 1
+long ud_fmn_norms_ws_bytes(int N, long per);
+int ud_fmn_norm_parts(const float* x, const float* x0, const float* g, int N, long per, double* ws, long ws_bytes,
+                      ud_stream_t stream);
+int ud_fmn_control(const float* f, const double* ws, long ws_bytes, int* ist, float* fst, double* fac, float* history,
+                   float* eps_history, const float* alpha, const float* gamma, const float* worst, int N, long per, int steps,
+                   int norm, int closing, ud_stream_t stream);
+int ud_fmn_update(float* x, float* x_best, const float* x0, const float* g, const int* ist, const float* fst, const double* fac,
+                  int N, long per, int norm, float lo, float hi, ud_stream_t stream);
+int ud_fmn_project_l2(float* x, const float* x0, const double* dss, const float* fst, int N, long per, float lo, float hi,
+                      ud_stream_t stream);
+
 /* ---- Square attack, L-infinity (csrc/square.hip; unidefense_amd/attack.py: SquareRunner) ------------------------------
  * Score-based black-box search: proposal j (j = 1..steps) overwrites one side[j-1] x side[j-1] window of the trial image
  * with x0 +- eps per channel; the control keeps it where the objective f fell.  Device state, so that one iteration

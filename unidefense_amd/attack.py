@@ -1,7 +1,7 @@
-"""Graph-replayed input gradients and FGSM / PGD / Auto-PGD / Square attacks on a frozen eval-mode detector: InputGradRunner,
-AttackRunner, APGDRunner, SquareRunner.
+"""Graph-replayed input gradients and FGSM / PGD / Auto-PGD / Square / FMN attacks on a frozen eval-mode detector:
+InputGradRunner, AttackRunner, APGDRunner, SquareRunner, FMNRunner.
 
-All four sit on one base class (_Runner) and follow InferenceRunner's life cycle (unidefense_amd/infer.py): call 1 runs eagerly
+All five sit on one base class (_Runner) and follow InferenceRunner's life cycle (unidefense_amd/infer.py): call 1 runs eagerly
 (it settles the on-line GEMM tuner and every lazily made workspace of the forward AND the backward for the shape), call 2
 captures the runner's iteration on static buffers (_Runner._capture), later calls copy the inputs in and replay.  An attack's
 defaults are written once, in its class's signature: the *_key and *_runner accessors bind their arguments with it.
@@ -34,6 +34,13 @@ in either precision — and no gradient, so it cross-checks the gradient attacks
 backward.  Its graph holds one query: csrc/square.hip's ud_square_propose (settle the last proposal's window, write the next),
 the forward, the per-sample objective and ud_square_control (keep or undo, who is still searched); every random choice is drawn by
 torch outside the graph (square_draws) into device tables that the kernels index with the sample's own counter.
+
+FMNRunner (Fast Minimum-Norm attack, linf and l2) is the minimum-norm member: where the others ask how far the loss rises at a
+budget chosen in advance, it returns per sample the smallest perturbation that flips it (radius), so ONE run gives the robust
+accuracy at every eps (robust_curve).  Its graph holds one iteration whose per-sample budget adapts on the device
+(csrc/fmn.hip: ud_fmn_norm_parts, the four norms of the iteration in one streaming pass; ud_fmn_control, one thread per sample;
+ud_fmn_update, step + projection in one pass), plus a forward-only closing graph; the step and shrink schedules
+(fmn_schedule) are device tables that the control kernel indexes with the sample's own counter.
 """
 import contextlib
 import inspect
@@ -143,7 +150,7 @@ def _objective_name(objective):
 
 
 class _Runner:
-    """What the four runners share: the model checks, the input checks, the capture, the forward + d/dx with fp16's loss scale,
+    """What the five runners share: the model checks, the input checks, the capture, the forward + d/dx with fp16's loss scale,
     and the per-sample pieces of the attacks with restarts."""
     _what = "runner"
     _backward = True                     # the captured work differentiates: the parameters are frozen around it
@@ -795,3 +802,183 @@ def square_runner(model, *args, **kwargs):
     _MAX_RUNNERS are kept, in a dictionary of their own (the other runners' caches are untouched)."""
     a = _square_arguments(*args, **kwargs)
     return _cached_runner(model, "_ud_square_runners", a, lambda: SquareRunner(model, *a.values()))
+
+
+# ---- Fast Minimum-Norm attack (FMN, Pintor et al. 2021), linf and l2: the smallest perturbation that flips each sample -------------
+FMN_OBJECTIVES = ("margin",)
+
+
+def fmn_schedule(steps, alpha_init=1.0, alpha_final=None, gamma_init=0.05, gamma_final=0.001):
+    """(alpha, gamma): the cosine schedules v_k = v1 + (v0 - v1)(1 + cos(pi k / steps)) / 2 for k = 0 .. steps - 1, computed in
+    float64 on the host and rounded to fp32 (CPU tensors [steps]); alpha_final None: alpha_init / 100."""
+    steps = int(steps)
+    a0 = float(alpha_init)
+    a1 = a0 / 100.0 if alpha_final is None else float(alpha_final)
+    g0, g1 = float(gamma_init), float(gamma_final)
+    c = [(1.0 + math.cos(math.pi * k / steps)) / 2.0 for k in range(steps)]
+    return (torch.tensor([a1 + (a0 - a1) * v for v in c], dtype=torch.float64).to(torch.float32),
+            torch.tensor([g1 + (g0 - g1) * v for v in c], dtype=torch.float64).to(torch.float32))
+
+
+def robust_curve(radius, grid):
+    """For each eps of grid the fraction of samples that no perturbation within eps flips: mean(radius > eps).  radius [N] as
+    FMNRunner leaves it: +inf where nothing was found, 0 for a sample that the clean model gets wrong (never robust).  The
+    comparison is made in radius's dtype (an fp32 radius of 0.1 is not above an eps of 0.1).  Returns a float64 tensor like grid."""
+    radius = torch.as_tensor(radius).detach().reshape(-1).cpu()
+    if not radius.is_floating_point():
+        radius = radius.double()
+    grid = torch.as_tensor(grid).detach().cpu().to(radius.dtype)
+    return (radius.reshape(1, -1) > grid.reshape(-1, 1)).double().mean(1).reshape(grid.shape)
+
+
+class FMNRunner(_Runner):
+    """runner = FMNRunner(model, batch, size, norm="linf", steps=100, ...); x_adv = runner(x, y).
+
+    Fast Minimum-Norm attack: per sample the smallest perturbation (in `norm`) that makes the objective f negative
+    (objective="margin": margin_each, negative once the sample is misclassified; targeted=True: -margin_each with y the target; or
+    a callable (out, y) -> [batch]).  Each sample carries its own budget eps on the device: while the sample is adversarial eps
+    shrinks by (1 - gamma_k) (never above the best norm found), after it was lost again eps grows by (1 + gamma_k), and before
+    anything was found eps is the linearised distance |x - x0| + |f| / |g|_dual; the step is alpha_k along -g / |g|_2, projected
+    onto the eps-ball around x and onto clip; alpha_k and gamma_k follow fmn_schedule.  One hipGraph holds ONE iteration —
+    forward, f, d sum(f) / dx, ud_fmn_norm_parts (the four norms in one pass), ud_fmn_control (one thread per sample),
+    ud_fmn_update (linf: step, box and clip in one pass; l2: followed by ud_sample_sumsq + ud_fmn_project_l2) — and a call replays
+    it `steps` times, then a forward-only graph that scores the last point.  No restarts, no random start: x starts at
+    clamp(x, clip).
+
+    Static buffers that the next call overwrites: x_adv (returned: the best adversarial point, x where none was found), radius [N]
+    (its norm, +inf where none was found), found [N] int32, margin0 [N] (f at the start: history[0]), history [steps + 1, N] and
+    eps_history [steps, N] (f_k and eps_k; history[steps] is the closing evaluation), g (the last iteration's gradient), out (the
+    last forward's output); args: the resolved arguments.  precision / grad_scale: as InputGradRunner."""
+    _what = "FMNRunner"
+
+    def __init__(self, model, batch, size, norm="linf", steps=100, alpha_init=1.0, alpha_final=None, gamma_init=0.05,
+                 gamma_final=0.001, targeted=False, clip=(-1.0, 1.0), objective="margin", precision="fp32", grad_scale=None):
+        _refuse_norm(norm)
+        _refuse_count("steps", steps, 1)
+        for name, v in (("alpha_init", alpha_init), ("alpha_final", alpha_init if alpha_final is None else alpha_final)):
+            if not 0.0 < float(v) < float("inf"):
+                raise ValueError(f"{name} must be a finite step length > 0, got {v!r}")
+        for name, v in (("gamma_init", gamma_init), ("gamma_final", gamma_final)):
+            if not 0.0 < float(v) < 1.0:
+                raise ValueError(f"{name} must be in (0, 1), got {v!r}")
+        _refuse_clip(clip)
+
+        def arguments():
+            self.grad_scale = resolve_grad_scale(precision, grad_scale)
+            if not callable(objective) and objective not in FMN_OBJECTIVES:
+                raise ValueError(f"objective must be one of {FMN_OBJECTIVES} or a callable (out, y) -> [batch], got {objective!r}")
+        self._init_model(model, batch, size, precision, arguments)
+        self.objective = objective if callable(objective) else margin_each
+        self.g = None
+        self.norm, self.steps, self.targeted = norm, int(steps), bool(targeted)
+        self.alpha_init = float(alpha_init)
+        self.alpha_final = self.alpha_init / 100.0 if alpha_final is None else float(alpha_final)
+        self.gamma_init, self.gamma_final = float(gamma_init), float(gamma_final)
+        self.lo, self.hi = float(clip[0]), float(clip[1])
+        self.alpha, self.gamma = fmn_schedule(self.steps, self.alpha_init, self.alpha_final, self.gamma_init, self.gamma_final)
+        self.args = {"method": "fmn", "norm": norm, "steps": self.steps, "alpha_init": self.alpha_init,
+                     "alpha_final": self.alpha_final, "gamma_init": self.gamma_init, "gamma_final": self.gamma_final,
+                     "targeted": self.targeted, "clip": (self.lo, self.hi), "objective": _objective_name(objective),
+                     "precision": self.precision, "grad_scale": self.grad_scale}
+        self.closing_graph = None
+        self.x0 = self.x = self.x_adv = self.y = self.radius = self.found = self.margin0 = None
+
+    def _buffers(self, x, y):
+        from . import kernels as K
+        n, dev, per = self.batch, self.device, 3 * self.size * self.size
+        self.x0 = x.detach().clone().contiguous()
+        self.x = self.x0.clone().requires_grad_()                 # the static leaf: the current iterate
+        self.x_adv = torch.zeros_like(self.x0)                    # the best point per sample
+        self.y = y.detach().clone()
+        self.ist, self.fst = K.fmn_state(n, dev)
+        self.history = torch.zeros(self.steps + 1, n, dtype=torch.float32, device=dev)
+        self.eps_history = torch.zeros(self.steps, n, dtype=torch.float32, device=dev)
+        self.margin0 = self.history[0]
+        self.radius = self.fst[K.FMN_F["best"]]
+        self.found = self.ist[K.FMN_I["found"]]
+        self._improved = self.ist[K.FMN_I["improved"]]
+        self._fac = torch.zeros(n, dtype=torch.float64, device=dev)
+        self._worst = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._alpha, self._gamma = self.alpha.to(dev), self.gamma.to(dev)
+        self._per = per
+        self._ws = K.fmn_ws(self.x0, n, per)
+        if self.norm == "l2":
+            self._dss = torch.zeros(n, dtype=torch.float64, device=dev)
+            self._ss_ws = K.fmn_sumsq_ws(self.x0, n, per)
+
+    def _descended(self, out):
+        f = self._each(out)
+        return -f if self.targeted else f
+
+    def _control(self, f, closing=False):
+        from . import kernels as K
+        K.fmn_control(f.detach().float().contiguous(), self._ws, self._per, self.ist, self.fst, self._fac, self.history,
+                      self.eps_history, self._alpha, self._gamma, self._worst, self.norm, closing=closing)
+
+    def _iteration(self):
+        """one FMN iteration on the static buffers: what the graph holds"""
+        from . import kernels as K
+        g, self.out, f = self._grad(self.x, self._descended)
+        self.g = g = g.contiguous()
+        K.fmn_norm_parts(self.x, self.x0, g, ws=self._ws)
+        self._control(f)
+        K.fmn_update(self.x, self.x_adv, self.x0, g, self.ist, self.fst, self._fac, self.norm, self.lo, self.hi)
+        if self.norm == "l2":
+            K.sample_sumsq(self.x, self.x0, out=self._dss, ws=self._ss_ws)
+            K.fmn_project_l2(self.x, self.x0, self._dss, self.fst, self.lo, self.hi)
+
+    def _closing(self):
+        """the closing evaluation: forward only at the last point; if it is adversarial and closer, it becomes the best"""
+        from . import kernels as K
+        with torch.no_grad(), self._nodes():
+            f = self._descended(self.model(self.x))
+        K.fmn_norm_parts(self.x, self.x0, None, ws=self._ws)
+        self._control(f, closing=True)
+        K.apgd_keep(self.x_adv, self.x, self._improved)
+
+    def _start(self, x, y):
+        """the start point, the cap on eps and the best point's default, outside the graph; the iteration counters back to 0"""
+        from . import kernels as K
+        with torch.no_grad():
+            self.x0.copy_(x)
+            self.y.copy_(y)
+            self.x.copy_(x.clamp(self.lo, self.hi))
+            self.x_adv.copy_(x)
+            far = torch.maximum(self.x0 - self.lo, self.hi - self.x0).flatten(1)
+            self._worst.copy_(far.amax(1) if self.norm == "linf" else far.norm(dim=1))
+            self.ist[K.FMN_I["k"]].zero_()
+
+    def __call__(self, x, y):
+        self._check(x, y)
+        self.calls += 1
+        with torch.enable_grad():
+            if self.calls == 1:                                   # eager warm-up: the same launches, a valid attack
+                self._buffers(x, y)
+            elif self.graph is None:
+                self.graph, self.closing_graph = self._capture(self._iteration, self._closing)
+            self._start(x, y)
+            if self.graph is None:
+                with frozen(self.model):
+                    for _ in range(self.steps):
+                        self._iteration()
+                    self._closing()
+            else:
+                for _ in range(self.steps):
+                    self.graph.replay()
+                self.closing_graph.replay()
+        return self.x_adv
+
+
+_fmn_arguments = _arguments(FMNRunner)
+
+
+def fmn_key(*args, **kwargs):
+    """arguments: FMNRunner's after the model"""
+    return _key(_fmn_arguments(*args, **kwargs))
+
+
+def fmn_runner(model, *args, **kwargs):
+    """The model's FMNRunner for the full argument tuple (FMNRunner's after the model), made on first use; at most
+    _MAX_RUNNERS are kept, in a dictionary of their own (the other runners' caches are untouched)."""
+    a = _fmn_arguments(*args, **kwargs)
+    return _cached_runner(model, "_ud_fmn_runners", a, lambda: FMNRunner(model, *a.values()))

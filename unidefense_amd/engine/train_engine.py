@@ -265,7 +265,12 @@ class TrainEngine(AbstractEngine):
         "method": "square" selects the black-box Square attack (the model's SquareRunner: eps, steps, p_init, restarts, ...; an
         optional "seed" seeds the CPU generator of its draws).  "method": "apgd+square" takes {"apgd": {...}, "square": {...},
         "seed": ...}: both attacks start from the clean batch, both results are scored, and each sample keeps the score with the
-        lower probability of its true label (the worst case over the ensemble); "attack" then holds both resolved dicts."""
+        lower probability of its true label (the worst case over the ensemble); "attack" then holds both resolved dicts.
+        "method": "fmn" selects the minimum-norm attack (the model's FMNRunner: norm, steps, alpha_init, gamma_init, ...) plus an
+        optional "eps": "adv" is scored on x_adv for the samples the attack flipped within eps (found and radius <= eps; eps absent:
+        every found sample) and on the clean input for the rest; "attack" then also holds "eps", "radius" (CPU tensor), "found"
+        (CPU tensor) and "median_radius", gathered over the ranks in the scores' order (robust_curve(radius, grid) gives the
+        robust accuracy at every eps from this one run)."""
         from .metrics import gather_scores
         attack = attack if attack is not None else self.config["config"].get("attack")
         if not attack:
@@ -285,8 +290,10 @@ class TrainEngine(AbstractEngine):
 
         attack = dict(attack)
         method = attack.pop("method", "pgd")
-        if method not in ("pgd", "apgd", "square", "apgd+square"):
-            raise ValueError(f"attack method must be 'pgd', 'apgd', 'square' or 'apgd+square', got {method!r}")
+        if method not in ("pgd", "apgd", "square", "apgd+square", "fmn"):
+            raise ValueError(f"attack method must be 'pgd', 'apgd', 'square', 'apgd+square' or 'fmn', got {method!r}")
+        if method == "fmn":
+            return self._test_robust_fmn(batches, attack, score)
         generator = square_generator = None
         square = None
         if method != "pgd":                                  # "seed" makes the random restarts / the draws reproducible
@@ -327,6 +334,35 @@ class TrainEngine(AbstractEngine):
             args = {"method": method, "apgd": dict(runner.args), "square": dict(square_runner.args)}
         else:
             args = dict((square_runner if method == "square" else runner).args)
+        return {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"),
+                "adv": self._metrics(*gather_scores(torch.cat(adv), labels), "Test(adv)"),
+                "attack": args}
+
+    def _test_robust_fmn(self, batches, attack, score):
+        """test_robust's "method": "fmn": attack is the dict without "method", score the scoring forward"""
+        from .metrics import gather_scores
+        eps = attack.pop("eps", None)
+        if eps is not None and not float(eps) >= 0.0:
+            raise ValueError(f"eps must be >= 0, got {eps!r}")
+        clean, adv, labels, radius, found, runner = [], [], [], [], [], None
+        for step in range(1, batches + 1):
+            xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
+            x, y = torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
+            clean.append(score(x))
+            runner = self.model_without_ddp.fmn_runner(x.shape[0], x.shape[-1], **attack)
+            xa = runner(x, y)
+            take = runner.found.bool() if eps is None else runner.found.bool() & (runner.radius <= float(eps))
+            adv.append(score(torch.where(take.reshape(-1, 1, 1, 1), xa, x)))
+            labels.append(y)
+            radius.append(runner.radius.clone())
+            found.append(runner.found.clone())
+        labels = torch.cat(labels)
+        radius, _ = gather_scores(torch.cat(radius), labels)
+        found, _ = gather_scores(torch.cat(found), labels)
+        radius, found = radius.float().cpu(), found.to(torch.int32).cpu()
+        args = dict(runner.args)
+        args.update(eps=None if eps is None else float(eps), radius=radius, found=found,
+                    median_radius=float(radius.double().median()) if radius.numel() else float("nan"))
         return {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"),
                 "adv": self._metrics(*gather_scores(torch.cat(adv), labels), "Test(adv)"),
                 "attack": args}

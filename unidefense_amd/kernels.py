@@ -1529,6 +1529,94 @@ def apgd_project_l2(x, x0, dss, fst, eps, lo, hi):
     return x
 
 
+# ---- Fast Minimum-Norm attack (csrc/fmn.hip) ------------------------------------------------------------------------------------
+FMN_I = {"k": 0, "found": 1, "improved": 2}
+FMN_F = {"eps": 0, "best": 1}
+FMN_NORM = {"linf": 0, "l2": 1}
+FMN_PARTS = {"gss": 0, "gabs": 1, "dss": 2, "dmax": 3}          # the doubles of one part (UD_FMN_P_*)
+FMN_CHUNK = 4096
+_FMN_WS = Scratch(torch.float64)          # norm parts: written by fmn_norm_parts, consumed by the fmn_control behind it
+_FMN_SS_WS = Scratch(torch.float64)       # the L2 projection's sample_sumsq partial sums, consumed by its own fold launch
+
+
+def fmn_state(N, device):
+    """(ist, fst): zeroed control state for N samples"""
+    return _state(N, device, FMN_I, FMN_F)
+
+
+def fmn_norms_ws_bytes(N, per):
+    return _call("ud_fmn_norms_ws_bytes", int(N), int(per))
+
+
+def fmn_ws(ref, N, per):
+    """The norm parts' workspace for [N, per] on ref's device, float64 [N, parts, 4], from the scratch owner (never freed:
+    a captured graph keeps its pointer).  One buffer per device: fmn_control reads what the fmn_norm_parts before it wrote."""
+    need = fmn_norms_ws_bytes(N, per) // 8
+    return _FMN_WS.get(ref, need)[:need].view(N, need // (4 * N), 4)
+
+
+def fmn_sumsq_ws(ref, N, per):
+    """sample_sumsq's workspace for the L2 projection of [N, per], from the scratch owner (at least one double)"""
+    need = max(sample_sumsq_ws_bytes(N, per) // 8, 1)
+    return _FMN_SS_WS.get(ref, need)[:need]
+
+
+def _chk_fmn_ws(ws, N, per):
+    _chk_f64(ws, fmn_norms_ws_bytes(N, per) // 8)
+
+
+def fmn_norm_parts(x, x0, g=None, ws=None):
+    """One pass over x, x0, g [N, ...] fp32: per 4096-element part of every sample (sum g^2, sum |g|, sum (x - x0)^2,
+    max |x - x0|) as doubles into ws [N, parts, 4] (fmn_ws unless given); g None: the two (x - x0) entries only."""
+    _chk_same(*((x, x0) if g is None else (x, x0, g)))
+    N = x.shape[0]
+    per = x.numel() // N
+    if ws is None:
+        ws = fmn_ws(x, N, per)
+    _chk_fmn_ws(ws, N, per)
+    _call("ud_fmn_norm_parts", _p(x), _p(x0), _p(g), N, per, _p(ws), ws.numel() * 8, _stream())
+    return ws
+
+
+def fmn_control(f, ws, per, ist, fst, fac, history, eps_history, alpha, gamma, worst, norm, closing=False):
+    """One step of the per-sample FMN state machine (include/unidefense_hip.h) on f [N] fp32 and the norm parts ws of samples
+    of `per` elements; closing: the keep-best decision of the last point only."""
+    _chk(f, history, eps_history, alpha, gamma, worst)
+    N, steps = f.numel(), alpha.numel()
+    _chk_state(ist, fst, N, FMN_I, FMN_F)
+    _chk_fmn_ws(ws, N, per)
+    _chk_f64(fac, N)
+    if tuple(history.shape) != (steps + 1, N) or tuple(eps_history.shape) != (steps, N):
+        raise ValueError(f"history must be [{steps + 1}, {N}] and eps_history [{steps}, {N}], got {tuple(history.shape)} and "
+                         f"{tuple(eps_history.shape)}")
+    if gamma.numel() != steps or worst.numel() != N:
+        raise ValueError(f"gamma must hold {steps} values and worst {N}, got {gamma.numel()} and {worst.numel()}")
+    _call("ud_fmn_control", _p(f), _p(ws), ws.numel() * 8, _p(ist), _p(fst), _p(fac), _p(history), _p(eps_history), _p(alpha),
+          _p(gamma), _p(worst), N, int(per), steps, FMN_NORM[norm], int(bool(closing)), _stream())
+
+
+def fmn_update(x, x_best, x0, g, ist, fst, fac, norm, lo, hi):
+    """In place on x and x_best: the keep-best copy, the step z = x - g fac[n] (double, rounded once) and, for "linf", the box of
+    the sample's own eps and the clip — bitwise the torch expression; "l2" leaves z for sample_sumsq + fmn_project_l2."""
+    _chk_same(x, x_best, x0, g)
+    N = x.shape[0]
+    _chk_state(ist, fst, N, FMN_I, FMN_F)
+    _chk_f64(fac, N)
+    _call("ud_fmn_update", _p(x), _p(x_best), _p(x0), _p(g), _p(ist), _p(fst), _p(fac), N, x.numel() // N, FMN_NORM[norm],
+          float(lo), float(hi), _stream())
+    return x
+
+
+def fmn_project_l2(x, x0, dss, fst, lo, hi):
+    """attack_project_l2 with each sample's own budget fst[eps]; dss [N] float64 = sample_sumsq(x, x0)"""
+    _chk_same(x, x0)
+    N = x.shape[0]
+    _chk_f64(dss, N)
+    _chk_state(None, fst, N, FMN_I, FMN_F)
+    _call("ud_fmn_project_l2", _p(x), _p(x0), _p(dss), _p(fst), N, x.numel() // N, float(lo), float(hi), _stream())
+    return x
+
+
 # ---- Square attack (csrc/square.hip) ------------------------------------------------------------------------------------------
 SQUARE_I = {"k": 0, "accepted": 1, "active": 2, "queries": 3}
 SQUARE_F = {"f_best": 0}

@@ -241,6 +241,13 @@ class RunnerMethods:
         from ..attack import apgd_runner
         return apgd_runner(self, batch, size, **kwargs)
 
+    def fmn_runner(self, batch, size, **kwargs):
+        """The graph-replayed Fast Minimum-Norm attack for [batch, 3, size, size] inputs: per sample the smallest perturbation
+        that flips it (FMNRunner; kwargs: norm, steps, alpha_init, alpha_final, gamma_init, gamma_final, targeted, clip,
+        objective, precision, grad_scale)."""
+        from ..attack import fmn_runner
+        return fmn_runner(self, batch, size, **kwargs)
+
     def square_runner(self, batch, size, **kwargs):
         """The graph-replayed Square attack (black-box, L-infinity, forward only) for [batch, 3, size, size] inputs
         (SquareRunner; kwargs: eps, steps, p_init, restarts, early_stop, check_every, clip, objective, precision)."""
