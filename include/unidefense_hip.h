@@ -420,6 +420,26 @@ long ud_conv_small_wgrad_ws_floats(int Cin, int Ma);
 int ud_conv_small_wgrad(const ud_conv_geom* g, const float* a, const float* x, float* part, float* out, int Ma,
                         ud_stream_t stream);
 
+/* ---- direct 3x3 conv on the matrix pipe (csrc/conv_mfma.hip): the decoder's 20/40/80/160-channel convs, their data gradients,
+ * the ConvTranspose2d(k3, s2) forward and its stride-2 data gradient.  Same operation as ud_conv_small; one workgroup owns a
+ * tile of output pixels and all Cout, the input patch is staged and split into two fp16 pieces once, three fp16 MFMAs per
+ * k-step give fp32-GEMM accuracy.  ud_conv_mfma_mode: the geometry class of g — 0 stride 1 pad 1 with Hout = Hin, 1 transposed
+ * stride 2 pad 1 with Hout = 2 Hin, 2 stride 2 pad 1 with Hin = 2 Hout (3x3 windows only), -1 none of them.
+ * ud_conv_mfma_supported: 1 if a kernel exists for (Cin, Cout, mode), else 0; ud_conv_mfma classifies g the same way and returns
+ * UD_EINVAL for any other geometry or pair, and for pointers that are not 16-byte aligned. */
+int ud_conv_mfma_mode(const ud_conv_geom* g);
+int ud_conv_mfma_supported(int Cin, int Cout, int mode);
+int ud_conv_mfma(const ud_conv_geom* g, const float* x, const float* wmat, float* y, int Cout, ud_stream_t stream);
+/* weight gradient of the same convs (ud_gemm's b_mode 2; geometry classes 0 and 2): out[Ma][9*Cin] = sum over the rows
+ * m = (n,oh,ow) of g's output grid of a[m][Ma] (x) patch(x)[m][9*Cin] — a = dy and x gathered for a conv, a = x and dy gathered at
+ * stride 2 for a transposed conv.  Pixels are the MFMA's reduction index; exact bf16 x 3 split, six products.  part:
+ * ud_conv_mfma_wgrad_ws_floats(Cin, Ma) floats of scratch (per-workgroup partials, summed in a fixed order by a second launch:
+ * deterministic, no atomics, no zero fill). */
+int ud_conv_mfma_wgrad_supported(int Cin, int Ma, int mode);
+long ud_conv_mfma_wgrad_ws_floats(int Cin, int Ma);
+int ud_conv_mfma_wgrad(const ud_conv_geom* g, const float* a, const float* x, float* part, float* out, int Ma,
+                       ud_stream_t stream);
+
 /* ---- gradient with respect to the input image (csrc/inputgrad.hip): x.grad of model(x) ----------------------------
  * ud_stem_dgrad   : dx[N][3][Hin][Win] (+= when accumulate) the data gradient of the stem conv g (F.conv2d geometry, Cin 3,
  *                   stride 2) from dy[N][Hout][Wout][Cout] (pixel-major) and the module weight w[Cout][3][KH][KW]

@@ -24,7 +24,7 @@ CLASSES = (("gemm", ("gemm_",)),
            ("squeeze_excite", ("colsum_bn", "se_scale", "se_bwd", "fc_fwd", "fc_bwd", "se_fc")),
            ("depthwise", ("dw_tile", "dw_fwd", "dw_bwd", "dw_wt")),
            ("plane_splits", ("split_h2", "absmax", "planes_from", "im2col", "col2im", "weight_layouts")),
-           ("decoder_direct_conv", ("conv_small",)))
+           ("decoder_direct_conv", ("conv_small", "conv_mfma")))
 
 
 def klass(name):

@@ -43,6 +43,7 @@ ud_fmn_update, step + projection in one pass), plus a forward-only closing graph
 (fmn_schedule) are device tables that the control kernel indexes with the sample's own counter.
 """
 import contextlib
+import gc
 import inspect
 import math
 
@@ -186,10 +187,19 @@ class _Runner:
         where the runner has a backward: the graphs."""
         torch.cuda.synchronize(self.device)
         graphs = [torch.cuda.CUDAGraph() for _ in bodies]
-        with frozen(self.model) if self._backward else contextlib.nullcontext():
-            for g, body in zip(graphs, bodies):
-                with torch.cuda.graph(g):
-                    body()
+        # the cyclic collector must not run inside a capture: it would destroy whatever unreachable graphs, events and device
+        # buffers earlier runners or models left behind, and a device call of a destructor is illegal while a stream captures
+        # in the global error mode (the process aborts).  torch.cuda.graph collects once on entry; nothing may collect after it.
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with frozen(self.model) if self._backward else contextlib.nullcontext():
+                for g, body in zip(graphs, bodies):
+                    with torch.cuda.graph(g):
+                        body()
+        finally:
+            if gc_was_on:
+                gc.enable()
         return graphs
 
     def _nodes(self):

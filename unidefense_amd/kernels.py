@@ -1276,6 +1276,50 @@ def _conv_small_wgrad_supported(Ci, Ma, KH, KW):
     return _CONV_SMALL_WGRAD_OK[key]
 
 
+_CONV_MFMA = True
+_CONV_MFMA_MIN_M = 16384            # output pixels: below, the grid leaves most CUs idle
+# (Cin, Cout, geometry class of ud_conv_mfma_mode) routed to csrc/conv_mfma.hip: the shapes that won their isolated A/B clearly
+# and in the step (tools/probe_conv_mfma.py).  Instantiated but not routed: stride-2 40 -> 40 (1.04 x: inside the
+# noise) and the 16 x 16 layers 160 -> 80, 80 -> 160, stride-2 80 -> 80.  None: every shape the library has a kernel for (tests)
+_CONV_MFMA_SHAPES = frozenset({(20, 20, 0), (40, 20, 0), (40, 40, 0), (20, 40, 0), (80, 40, 0), (80, 80, 0), (40, 80, 0),
+                               (20, 20, 1), (40, 40, 1), (80, 80, 1), (20, 20, 2)})
+_CONV_MFMA_OK = {}
+
+
+def _conv_mfma_mode(g):
+    """geometry class of g (ud_conv_mfma_mode: the library's own rule): 0 stride 1 'same', 1 transposed stride 2, 2 stride 2; -1 none"""
+    return int(_lib.load().ud_conv_mfma_mode(C.byref(g)))          # (a class, not a status: -1 is an answer)
+
+
+def _conv_mfma_takes(g, Co, M, *tensors):
+    if not _CONV_MFMA or M < _CONV_MFMA_MIN_M:
+        return False
+    key = (g.Cin, Co, _conv_mfma_mode(g))
+    if key[2] < 0 or (_CONV_MFMA_SHAPES is not None and key not in _CONV_MFMA_SHAPES):
+        return False
+    if key not in _CONV_MFMA_OK:
+        _CONV_MFMA_OK[key] = _call("ud_conv_mfma_supported", *key) == 1
+    return _CONV_MFMA_OK[key] and all(t.dtype == torch.float32 and t.data_ptr() % 16 == 0 for t in tensors)
+
+
+# weight gradients on csrc/conv_mfma.hip's second kernel: (gathered Cin, Ma, geometry class) routed; None: every instantiated shape
+# (tests).  Empty: the kernel lost its isolated A/B on all nine shapes (0.66-1.02 x, DESIGN 3p), so none is routed
+_CONV_MFMA_WGRAD_SHAPES = frozenset()
+_CONV_MFMA_WGRAD_OK = {}
+_CONV_MFMA_WS = Scratch(torch.float32)
+
+
+def _conv_mfma_wgrad_takes(g, Ma, M, *tensors):
+    if not _CONV_MFMA or M < _CONV_MFMA_MIN_M:
+        return False
+    key = (g.Cin, Ma, _conv_mfma_mode(g))
+    if key[2] not in (0, 2) or (_CONV_MFMA_WGRAD_SHAPES is not None and key not in _CONV_MFMA_WGRAD_SHAPES):
+        return False
+    if key not in _CONV_MFMA_WGRAD_OK:
+        _CONV_MFMA_WGRAD_OK[key] = _call("ud_conv_mfma_wgrad_supported", *key) == 1
+    return _CONV_MFMA_WGRAD_OK[key] and all(t.dtype == torch.float32 and t.data_ptr() % 16 == 0 for t in tensors)
+
+
 def conv_gather_nt(x, wmat, g):
     """Implicit-GEMM conv: rows (n,oh,ow) x k=(tap,ci) gathered from x[N,Hin,Win,Cin]; wmat[Cout, KH*KW*Cin].
     Returns [N, Hout, Wout, Cout]."""
@@ -1284,6 +1328,11 @@ def conv_gather_nt(x, wmat, g):
     K = g.KH * g.KW * g.Cin
     Co = wmat.shape[0]
     assert wmat.shape[1] == K and x.numel() == g.N * g.Hin * g.Win * g.Cin
+    if _conv_mfma_takes(g, Co, M, x, wmat):
+        # decoder 3x3 / transposed convs: direct conv on the matrix pipe, the patch staged and split once per tile
+        out = empty((g.N, g.Hout, g.Wout, Co), x)
+        _call("ud_conv_mfma", C.byref(g), _p(x), _p(wmat), _p(out), Co, _stream())
+        return out
     if _CONV_SMALL and M >= _CONV_SMALL_MIN_M and _conv_small_supported(g.Cin, Co, g.KH, g.KW):
         # few channels at image resolution (decoder tail, stem): direct conv, one thread per output pixel
         out = empty((g.N, g.Hout, g.Wout, Co), x)
@@ -1666,6 +1715,12 @@ def conv_gather_wgrad(a, x, g):
     Ma = a.shape[-1]
     assert a.numel() == Kdim * Ma
     Ncols = g.KH * g.KW * g.Cin
+    if _conv_mfma_wgrad_takes(g, Ma, Kdim, a, x):
+        # decoder conv / transposed-conv weight gradients: pixels as the MFMA's reduction index, partials folded in a fixed order
+        ws = _CONV_MFMA_WS.get(a, _call("ud_conv_mfma_wgrad_ws_floats", g.Cin, Ma))
+        out = empty((Ma, Ncols), a)
+        _call("ud_conv_mfma_wgrad", C.byref(g), _p(a), _p(x), _p(ws), _p(out), Ma, _stream())
+        return out
     if _CONV_SMALL and Kdim >= _CONV_SMALL_MIN_M and _conv_small_wgrad_supported(g.Cin, Ma, g.KH, g.KW):
         # a 20 x 180 (3 x 180, 48 x 27) result reduced over 524 288 rows: streamed through LDS, register-blocked
         ws = _CONV_SMALL_WS.get(a, _call("ud_conv_small_wgrad_ws_floats", g.Cin, Ma))
