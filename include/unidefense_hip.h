@@ -596,6 +596,77 @@ int ud_fmn_update(float* x, float* x_best, const float* x0, const float* g, cons
 int ud_fmn_project_l2(float* x, const float* x0, const double* dss, const float* fst, int N, long per, float lo, float hi,
                       ud_stream_t stream);
 
+/* ---- Sparse minimum-norm attack (csrc/sfmn.hip; unidefense_amd/attack.py: SparseFMNRunner) ----------------------------
+ * The FMN state machine above with norm UD_SFMN_L1 (the budget bounds sum |x - x0|) or UD_SFMN_L0 (it bounds the NUMBER of
+ * elements with x != x0, an integer kept in fp32: per < UD_SFMN_L0_MAX_PER = 2^24).  ist [3][N], fst [2][N], fac [N], history,
+ * eps_history, alpha, gamma, worst as there (rows UD_SFMN_I_*, UD_SFMN_F_*);  thr [N] double: what ud_sfmn_select leaves.
+ * ud_sfmn_norm_parts: ud_fmn_norm_parts's pass, layout and tree with the four entries j = UD_SFMN_P_GSS: sum g^2, _GMAX:
+ *   max |g| (keeps a NaN), _DABS: sum |x - x0|, _DCNT: the number of x != x0 as a double (a NaN differs).  g == NULL writes
+ *   the two d entries only.  ws holds ud_sfmn_norms_ws_bytes(N, per) bytes.
+ * ud_sfmn_control: one thread per sample, every operation in double with one rounding (no contraction) unless it says fp32:
+ *     GSS, DABS, DCNT = 0.0 + part 0 + part 1 + ... in index order;  GMAX = m(... m(m(0.0, part 0), part 1) ...), m as above
+ *     dn = (float)(l0 ? DCNT : DABS)
+ *     k = ist[K][n]; k outside [0, steps) writes nothing.  k == 0: eps = best = +inf (fp32), found = 0; else as stored.
+ *     adv = f < 0 (fp32);  improved = adv && dn < best (fp32);  improved: best = dn
+ *     g = (double)gamma[k], E = (double)eps, b = (double)best, q = GMAX < 1e-12 ? 1e-12 : GMAX
+ *     adv  : t = E (1 - g);  l0: t = floor(t), u = E - 1, t = u < t ? u : t;          e = t < b ? t : b
+ *     else found: e = E (1 + g);  l0: e = floor(e), u = E + 1, e = u > e ? u : e
+ *     else : l1: e = (double)dn + |(double)f| / q
+ *            l0: c = ceil(|(double)f| / (((double)hi - (double)lo) q)), c = c < 1 ? 1 : c, e = (double)dn + c
+ *                (every coordinate moves f by at most (hi - lo) max |g|: the linearised lower bound on their number)
+ *     l0: e = e < 0 ? 0 : e;   w = (double)worst[n]; e = w < e ? w : e;   e == e (not NaN): eps = (float)e;   found |= adv
+ *     fac[n] = (double)alpha[k] / (s < 1e-12 ? 1e-12 : s), s = sqrt(GSS)
+ *     stored: as ud_fmn_control.  floor(inf) = inf.  An l0 eps is an integer or +inf at every step.
+ *   closing != 0: as ud_fmn_control's (the GSS / GMAX entries are not read).
+ * The step, for ud_sfmn_select and ud_sfmn_apply alike: z = (float)((double)x - (double)g fac[n]) (product and difference
+ *   rounded once each), d = (double)z - (double)x0, a = |d|.
+ * ud_sfmn_select: ONE workgroup (1024 threads) per sample reads the sample a bounded number of times and writes thr[n]:
+ *   UD_SFMN_L1: sum a <= eps[n] (an infinite eps included): thr = -1, nothing to project.  Else eps[n] <= 0 (or NaN): thr =
+ *     +inf, everything returns to x0, in one pass.  Else thr = tau with
+ *     sum max(a - tau, 0) = eps: G(t) = sum_{a > t} a - |{a > t}| t is evaluated for thresholds t whose bit pattern is fixed
+ *     in its top 44 bits (sign, exponent, 32 bits of the significand; the bits below all ones), two bits per pass (three
+ *     thresholds each), at most 22 passes after one that sums every a: v = the smallest such t with G(t) <= eps, (C, S) =
+ *     count and sum of the a above v's predecessor, tau = max((S - eps) / C, 0); C == 0: tau = +inf.  The passes stop early
+ *     once no a lies between the largest t seen with G > eps and the smallest with G <= eps (equal counts above the two): C, S
+ *     and tau are then the bits the remaining passes would give.  tau is within 2^-32 relative of the exact one.  Counts and
+ *     sums in double: thread order, wave shuffles, waves in order.
+ *   UD_SFMN_L0: kk = (integer) eps[n]; eps infinite or kk >= per: thr = -1, everything is kept; kk < 1: thr = +inf, nothing is
+ *     kept (neither reads the sample).  Else thr = the
+ *     (kk + 1)-th largest a counting multiplicity, exactly: a radix select on a's 64-bit pattern, 11 bits per pass, 6 passes,
+ *     integer counts in LDS (integer atomics only).
+ *   A NaN a counts as no element (L1) or as 0 (L0).  Every loop has a compile-time bound on its trip count: any input ends.
+ * ud_sfmn_apply: one pass over [N][per].  improved: x_best <- x.  Then with z, d, a as above: a NaN a: x <- z (the NaN).
+ *   thr < 0: x <- clamp(z, lo, hi).  UD_SFMN_L1: m = a - tau, m = m > 0 ? m : 0, x <- clamp((float)((double)x0 + (d < 0 ? -m :
+ *   m)), lo, hi).  UD_SFMN_L0: x <- clamp(a > thr ? z : x0, lo, hi): ties at the threshold are all dropped, at most kk
+ *   elements survive and no index order enters.
+ * UD_EINVAL before any HIP call: a NULL pointer (g of ud_sfmn_norm_parts excepted), N < 1, per < 1, steps < 1, a norm that is
+ * neither, UD_SFMN_L0 with per >= UD_SFMN_L0_MAX_PER (control, select), lo >= hi or NaN (control; apply: lo > hi),
+ * ws_bytes < ud_sfmn_norms_ws_bytes(N, per). */
+#define UD_SFMN_CHUNK 4096
+#define UD_SFMN_PARTS 4
+#define UD_SFMN_P_GSS 0
+#define UD_SFMN_P_GMAX 1
+#define UD_SFMN_P_DABS 2
+#define UD_SFMN_P_DCNT 3
+#define UD_SFMN_L1 0
+#define UD_SFMN_L0 1
+#define UD_SFMN_I_K 0
+#define UD_SFMN_I_FOUND 1
+#define UD_SFMN_I_IMPROVED 2
+#define UD_SFMN_F_EPS 0
+#define UD_SFMN_F_BEST 1
+#define UD_SFMN_L0_MAX_PER 16777216
+long ud_sfmn_norms_ws_bytes(int N, long per);
+int ud_sfmn_norm_parts(const float* x, const float* x0, const float* g, int N, long per, double* ws, long ws_bytes,
+                       ud_stream_t stream);
+int ud_sfmn_control(const float* f, const double* ws, long ws_bytes, int* ist, float* fst, double* fac, float* history,
+                    float* eps_history, const float* alpha, const float* gamma, const float* worst, int N, long per, int steps,
+                    int norm, float lo, float hi, int closing, ud_stream_t stream);
+int ud_sfmn_select(const float* x, const float* x0, const float* g, const float* fst, const double* fac, double* thr, int N,
+                   long per, int norm, ud_stream_t stream);
+int ud_sfmn_apply(float* x, float* x_best, const float* x0, const float* g, const int* ist, const double* fac, const double* thr,
+                  int N, long per, int norm, float lo, float hi, ud_stream_t stream);
+
 /* ---- Square attack, L-infinity (csrc/square.hip; unidefense_amd/attack.py: SquareRunner) ------------------------------
  * Score-based black-box search: proposal j (j = 1..steps) overwrites one side[j-1] x side[j-1] window of the trial image
  * with x0 +- eps per channel; the control keeps it where the objective f fell.  Device state, so that one iteration

@@ -1,7 +1,7 @@
-"""Graph-replayed input gradients and FGSM / PGD / Auto-PGD / Square / FMN attacks on a frozen eval-mode detector:
-InputGradRunner, AttackRunner, APGDRunner, SquareRunner, FMNRunner.
+"""Graph-replayed input gradients and FGSM / PGD / Auto-PGD / Square / FMN / sparse FMN attacks on a frozen eval-mode detector:
+InputGradRunner, AttackRunner, APGDRunner, SquareRunner, FMNRunner, SparseFMNRunner.
 
-All five sit on one base class (_Runner) and follow InferenceRunner's life cycle (unidefense_amd/infer.py): call 1 runs eagerly
+All six sit on one base class (_Runner) and follow InferenceRunner's life cycle (unidefense_amd/infer.py): call 1 runs eagerly
 (it settles the on-line GEMM tuner and every lazily made workspace of the forward AND the backward for the shape), call 2
 captures the runner's iteration on static buffers (_Runner._capture), later calls copy the inputs in and replay.  An attack's
 defaults are written once, in its class's signature: the *_key and *_runner accessors bind their arguments with it.
@@ -41,6 +41,13 @@ accuracy at every eps (robust_curve).  Its graph holds one iteration whose per-s
 (csrc/fmn.hip: ud_fmn_norm_parts, the four norms of the iteration in one streaming pass; ud_fmn_control, one thread per sample;
 ud_fmn_update, step + projection in one pass), plus a forward-only closing graph; the step and shrink schedules
 (fmn_schedule) are device tables that the control kernel indexes with the sample's own counter.
+
+SparseFMNRunner (l1 and l0) is FMNRunner's sibling for the sparse threat models — a sticker, a retouched patch, a few edited
+pixels: radius is sum |x_adv - x| or the number of changed elements.  The two share their body (_MinNormRunner); what differs is
+the norm pass and control rules (csrc/sfmn.hip: ud_sfmn_norm_parts, ud_sfmn_control) and the projection, which needs a
+per-sample selection over all 3 size^2 elements inside the graph: ud_sfmn_select (one workgroup per sample: the L1 ball's soft
+threshold by a fixed-count bisection with sums in double, the L0 threshold by a radix select on integer counts) and
+ud_sfmn_apply (one pass).  FMNRunner, ud_fmn_* and its norms are unchanged.
 """
 import contextlib
 import gc
@@ -151,7 +158,7 @@ def _objective_name(objective):
 
 
 class _Runner:
-    """What the five runners share: the model checks, the input checks, the capture, the forward + d/dx with fp16's loss scale,
+    """What the six runners share: the model checks, the input checks, the capture, the forward + d/dx with fp16's loss scale,
     and the per-sample pieces of the attacks with restarts."""
     _what = "runner"
     _backward = True                     # the captured work differentiates: the parameters are frozen around it
@@ -841,29 +848,19 @@ def robust_curve(radius, grid):
     return (radius.reshape(1, -1) > grid.reshape(-1, 1)).double().mean(1).reshape(grid.shape)
 
 
-class FMNRunner(_Runner):
-    """runner = FMNRunner(model, batch, size, norm="linf", steps=100, ...); x_adv = runner(x, y).
+class _MinNormRunner(_Runner):
+    """What FMNRunner and SparseFMNRunner share: the arguments and their refusals, the static buffers, the life cycle and the
+    closing evaluation.  A subclass names its norms and method, its kernels' state rows (_rows), the cap on eps (_worst_of), the
+    three launches that differ — _parts, _control, _project — and whatever state _project needs (_norm_buffers)."""
+    _norms = ()
+    _method = None
 
-    Fast Minimum-Norm attack: per sample the smallest perturbation (in `norm`) that makes the objective f negative
-    (objective="margin": margin_each, negative once the sample is misclassified; targeted=True: -margin_each with y the target; or
-    a callable (out, y) -> [batch]).  Each sample carries its own budget eps on the device: while the sample is adversarial eps
-    shrinks by (1 - gamma_k) (never above the best norm found), after it was lost again eps grows by (1 + gamma_k), and before
-    anything was found eps is the linearised distance |x - x0| + |f| / |g|_dual; the step is alpha_k along -g / |g|_2, projected
-    onto the eps-ball around x and onto clip; alpha_k and gamma_k follow fmn_schedule.  One hipGraph holds ONE iteration —
-    forward, f, d sum(f) / dx, ud_fmn_norm_parts (the four norms in one pass), ud_fmn_control (one thread per sample),
-    ud_fmn_update (linf: step, box and clip in one pass; l2: followed by ud_sample_sumsq + ud_fmn_project_l2) — and a call replays
-    it `steps` times, then a forward-only graph that scores the last point.  No restarts, no random start: x starts at
-    clamp(x, clip).
+    def _refuse_norm(self, norm, size):
+        raise NotImplementedError
 
-    Static buffers that the next call overwrites: x_adv (returned: the best adversarial point, x where none was found), radius [N]
-    (its norm, +inf where none was found), found [N] int32, margin0 [N] (f at the start: history[0]), history [steps + 1, N] and
-    eps_history [steps, N] (f_k and eps_k; history[steps] is the closing evaluation), g (the last iteration's gradient), out (the
-    last forward's output); args: the resolved arguments.  precision / grad_scale: as InputGradRunner."""
-    _what = "FMNRunner"
-
-    def __init__(self, model, batch, size, norm="linf", steps=100, alpha_init=1.0, alpha_final=None, gamma_init=0.05,
-                 gamma_final=0.001, targeted=False, clip=(-1.0, 1.0), objective="margin", precision="fp32", grad_scale=None):
-        _refuse_norm(norm)
+    def _init(self, model, batch, size, norm, steps, alpha_init, alpha_final, gamma_init, gamma_final, targeted, clip, objective,
+              precision, grad_scale):
+        self._refuse_norm(norm, size)
         _refuse_count("steps", steps, 1)
         for name, v in (("alpha_init", alpha_init), ("alpha_final", alpha_init if alpha_final is None else alpha_final)):
             if not 0.0 < float(v) < float("inf"):
@@ -886,7 +883,7 @@ class FMNRunner(_Runner):
         self.gamma_init, self.gamma_final = float(gamma_init), float(gamma_final)
         self.lo, self.hi = float(clip[0]), float(clip[1])
         self.alpha, self.gamma = fmn_schedule(self.steps, self.alpha_init, self.alpha_final, self.gamma_init, self.gamma_final)
-        self.args = {"method": "fmn", "norm": norm, "steps": self.steps, "alpha_init": self.alpha_init,
+        self.args = {"method": self._method, "norm": norm, "steps": self.steps, "alpha_init": self.alpha_init,
                      "alpha_final": self.alpha_final, "gamma_init": self.gamma_init, "gamma_final": self.gamma_final,
                      "targeted": self.targeted, "clip": (self.lo, self.hi), "objective": _objective_name(objective),
                      "precision": self.precision, "grad_scale": self.grad_scale}
@@ -894,69 +891,56 @@ class FMNRunner(_Runner):
         self.x0 = self.x = self.x_adv = self.y = self.radius = self.found = self.margin0 = None
 
     def _buffers(self, x, y):
-        from . import kernels as K
         n, dev, per = self.batch, self.device, 3 * self.size * self.size
+        state, I, F = self._rows()
         self.x0 = x.detach().clone().contiguous()
         self.x = self.x0.clone().requires_grad_()                 # the static leaf: the current iterate
         self.x_adv = torch.zeros_like(self.x0)                    # the best point per sample
         self.y = y.detach().clone()
-        self.ist, self.fst = K.fmn_state(n, dev)
+        self.ist, self.fst = state(n, dev)
         self.history = torch.zeros(self.steps + 1, n, dtype=torch.float32, device=dev)
         self.eps_history = torch.zeros(self.steps, n, dtype=torch.float32, device=dev)
         self.margin0 = self.history[0]
-        self.radius = self.fst[K.FMN_F["best"]]
-        self.found = self.ist[K.FMN_I["found"]]
-        self._improved = self.ist[K.FMN_I["improved"]]
+        self.radius = self.fst[F["best"]]
+        self.found = self.ist[I["found"]]
+        self._k = self.ist[I["k"]]
+        self._improved = self.ist[I["improved"]]
         self._fac = torch.zeros(n, dtype=torch.float64, device=dev)
         self._worst = torch.zeros(n, dtype=torch.float32, device=dev)
         self._alpha, self._gamma = self.alpha.to(dev), self.gamma.to(dev)
         self._per = per
-        self._ws = K.fmn_ws(self.x0, n, per)
-        if self.norm == "l2":
-            self._dss = torch.zeros(n, dtype=torch.float64, device=dev)
-            self._ss_ws = K.fmn_sumsq_ws(self.x0, n, per)
+        self._norm_buffers(n, dev, per)
 
     def _descended(self, out):
         f = self._each(out)
         return -f if self.targeted else f
 
-    def _control(self, f, closing=False):
-        from . import kernels as K
-        K.fmn_control(f.detach().float().contiguous(), self._ws, self._per, self.ist, self.fst, self._fac, self.history,
-                      self.eps_history, self._alpha, self._gamma, self._worst, self.norm, closing=closing)
-
     def _iteration(self):
-        """one FMN iteration on the static buffers: what the graph holds"""
-        from . import kernels as K
+        """one iteration on the static buffers: what the graph holds"""
         g, self.out, f = self._grad(self.x, self._descended)
         self.g = g = g.contiguous()
-        K.fmn_norm_parts(self.x, self.x0, g, ws=self._ws)
+        self._parts(g)
         self._control(f)
-        K.fmn_update(self.x, self.x_adv, self.x0, g, self.ist, self.fst, self._fac, self.norm, self.lo, self.hi)
-        if self.norm == "l2":
-            K.sample_sumsq(self.x, self.x0, out=self._dss, ws=self._ss_ws)
-            K.fmn_project_l2(self.x, self.x0, self._dss, self.fst, self.lo, self.hi)
+        self._project(g)
 
     def _closing(self):
         """the closing evaluation: forward only at the last point; if it is adversarial and closer, it becomes the best"""
         from . import kernels as K
         with torch.no_grad(), self._nodes():
             f = self._descended(self.model(self.x))
-        K.fmn_norm_parts(self.x, self.x0, None, ws=self._ws)
+        self._parts(None)
         self._control(f, closing=True)
         K.apgd_keep(self.x_adv, self.x, self._improved)
 
     def _start(self, x, y):
         """the start point, the cap on eps and the best point's default, outside the graph; the iteration counters back to 0"""
-        from . import kernels as K
         with torch.no_grad():
             self.x0.copy_(x)
             self.y.copy_(y)
             self.x.copy_(x.clamp(self.lo, self.hi))
             self.x_adv.copy_(x)
-            far = torch.maximum(self.x0 - self.lo, self.hi - self.x0).flatten(1)
-            self._worst.copy_(far.amax(1) if self.norm == "linf" else far.norm(dim=1))
-            self.ist[K.FMN_I["k"]].zero_()
+            self._worst.copy_(self._worst_of(torch.maximum(self.x0 - self.lo, self.hi - self.x0).flatten(1)))
+            self._k.zero_()
 
     def __call__(self, x, y):
         self._check(x, y)
@@ -979,6 +963,67 @@ class FMNRunner(_Runner):
         return self.x_adv
 
 
+class FMNRunner(_MinNormRunner):
+    """runner = FMNRunner(model, batch, size, norm="linf", steps=100, ...); x_adv = runner(x, y).
+
+    Fast Minimum-Norm attack: per sample the smallest perturbation (in `norm`) that makes the objective f negative
+    (objective="margin": margin_each, negative once the sample is misclassified; targeted=True: -margin_each with y the target; or
+    a callable (out, y) -> [batch]).  Each sample carries its own budget eps on the device: while the sample is adversarial eps
+    shrinks by (1 - gamma_k) (never above the best norm found), after it was lost again eps grows by (1 + gamma_k), and before
+    anything was found eps is the linearised distance |x - x0| + |f| / |g|_dual; the step is alpha_k along -g / |g|_2, projected
+    onto the eps-ball around x and onto clip; alpha_k and gamma_k follow fmn_schedule.  One hipGraph holds ONE iteration —
+    forward, f, d sum(f) / dx, ud_fmn_norm_parts (the four norms in one pass), ud_fmn_control (one thread per sample),
+    ud_fmn_update (linf: step, box and clip in one pass; l2: followed by ud_sample_sumsq + ud_fmn_project_l2) — and a call replays
+    it `steps` times, then a forward-only graph that scores the last point.  No restarts, no random start: x starts at
+    clamp(x, clip).
+
+    Static buffers that the next call overwrites: x_adv (returned: the best adversarial point, x where none was found), radius [N]
+    (its norm, +inf where none was found), found [N] int32, margin0 [N] (f at the start: history[0]), history [steps + 1, N] and
+    eps_history [steps, N] (f_k and eps_k; history[steps] is the closing evaluation), g (the last iteration's gradient), out (the
+    last forward's output); args: the resolved arguments.  precision / grad_scale: as InputGradRunner."""
+    _what = "FMNRunner"
+    _norms = NORMS
+    _method = "fmn"
+
+    def __init__(self, model, batch, size, norm="linf", steps=100, alpha_init=1.0, alpha_final=None, gamma_init=0.05,
+                 gamma_final=0.001, targeted=False, clip=(-1.0, 1.0), objective="margin", precision="fp32", grad_scale=None):
+        self._init(model, batch, size, norm, steps, alpha_init, alpha_final, gamma_init, gamma_final, targeted, clip, objective,
+                   precision, grad_scale)
+
+    def _refuse_norm(self, norm, size):
+        _refuse_norm(norm)
+
+    def _rows(self):
+        from . import kernels as K
+        return K.fmn_state, K.FMN_I, K.FMN_F
+
+    def _norm_buffers(self, n, dev, per):
+        from . import kernels as K
+        self._ws = K.fmn_ws(self.x0, n, per)
+        if self.norm == "l2":
+            self._dss = torch.zeros(n, dtype=torch.float64, device=dev)
+            self._ss_ws = K.fmn_sumsq_ws(self.x0, n, per)
+
+    def _worst_of(self, far):
+        return far.amax(1) if self.norm == "linf" else far.norm(dim=1)
+
+    def _parts(self, g):
+        from . import kernels as K
+        K.fmn_norm_parts(self.x, self.x0, g, ws=self._ws)
+
+    def _control(self, f, closing=False):
+        from . import kernels as K
+        K.fmn_control(f.detach().float().contiguous(), self._ws, self._per, self.ist, self.fst, self._fac, self.history,
+                      self.eps_history, self._alpha, self._gamma, self._worst, self.norm, closing=closing)
+
+    def _project(self, g):
+        from . import kernels as K
+        K.fmn_update(self.x, self.x_adv, self.x0, g, self.ist, self.fst, self._fac, self.norm, self.lo, self.hi)
+        if self.norm == "l2":
+            K.sample_sumsq(self.x, self.x0, out=self._dss, ws=self._ss_ws)
+            K.fmn_project_l2(self.x, self.x0, self._dss, self.fst, self.lo, self.hi)
+
+
 _fmn_arguments = _arguments(FMNRunner)
 
 
@@ -992,3 +1037,83 @@ def fmn_runner(model, *args, **kwargs):
     _MAX_RUNNERS are kept, in a dictionary of their own (the other runners' caches are untouched)."""
     a = _fmn_arguments(*args, **kwargs)
     return _cached_runner(model, "_ud_fmn_runners", a, lambda: FMNRunner(model, *a.values()))
+
+
+# ---- Sparse minimum-norm attack: FMN's state machine with an L1 or an L0 budget (csrc/sfmn.hip) -----------------------------------
+SPARSE_NORMS = ("l1", "l0")
+
+
+class SparseFMNRunner(_MinNormRunner):
+    """runner = SparseFMNRunner(model, batch, size, norm="l1", steps=100, ...); x_adv = runner(x, y).
+
+    FMNRunner for the sparse norms — the same arguments, life cycle and static results, args["method"] == "sparse_fmn":
+      norm "l1": radius = sum |x_adv - x| over the sample; the step is projected onto the L1 ball of the sample's eps around x
+        (soft threshold of z - x), then onto clip;
+      norm "l0": radius = the number of ELEMENTS of the [3, size, size] sample that differ from x (a float that is an exact
+        integer; refused where 3 size^2 >= 2^24); eps is an integer: the eps largest |z - x| keep their step, every other element
+        returns to x (ties at the threshold are all dropped), then clip.
+    The budget follows FMN's rules with these pieces: before anything was found eps = |x - x0| + |f| / max |g| (l1: the dual
+    norm is L-infinity) or the count + max(1, ceil(|f| / ((hi - lo) max |g|))) (l0: each coordinate moves f by at most
+    (hi - lo) max |g|); an l0 budget shrinks and grows by at least one element; eps never exceeds sum max(x - lo, hi - x) (l1) or
+    3 size^2 (l0).  The step is still alpha_k along -g / |g|_2: alpha_init (default 1.0) MUST be sized to the norm — an
+    L2-normalised step of length 1 spread over every pixel moves an L1 distance of up to sqrt(3 size^2) but each single pixel
+    hardly at all, so a sparse projection of it keeps almost nothing; the suite's fixtures use alpha_init 8 (l1) and 256 (l0) at
+    128^2.  One hipGraph holds ONE iteration — forward, f, d sum(f) / dx, ud_sfmn_norm_parts, ud_sfmn_control, ud_sfmn_select
+    (one workgroup per sample finds the threshold), ud_sfmn_apply (keep-best copy, step, projection and clip in one pass) — and a
+    forward-only closing graph.  precision / grad_scale: as InputGradRunner."""
+    _what = "SparseFMNRunner"
+    _norms = SPARSE_NORMS
+    _method = "sparse_fmn"
+
+    def __init__(self, model, batch, size, norm="l1", steps=100, alpha_init=1.0, alpha_final=None, gamma_init=0.05,
+                 gamma_final=0.001, targeted=False, clip=(-1.0, 1.0), objective="margin", precision="fp32", grad_scale=None):
+        self._init(model, batch, size, norm, steps, alpha_init, alpha_final, gamma_init, gamma_final, targeted, clip, objective,
+                   precision, grad_scale)
+
+    def _refuse_norm(self, norm, size):
+        from . import kernels as K
+        if norm not in SPARSE_NORMS:
+            raise ValueError(f"norm must be one of {SPARSE_NORMS}, got {norm!r}")
+        if norm == "l0" and 3 * int(size) * int(size) >= K.SFMN_L0_MAX_PER:
+            raise ValueError(f"norm 'l0' counts elements in fp32: 3 size^2 must stay below 2^24, got size {size!r}")
+
+    def _rows(self):
+        from . import kernels as K
+        return K.sfmn_state, K.SFMN_I, K.SFMN_F
+
+    def _norm_buffers(self, n, dev, per):
+        from . import kernels as K
+        self._ws = K.sfmn_ws(self.x0, n, per)
+        self._thr = torch.zeros(n, dtype=torch.float64, device=dev)
+
+    def _worst_of(self, far):
+        return far.sum(1) if self.norm == "l1" else torch.full_like(far[:, 0], float(far.shape[1]))
+
+    def _parts(self, g):
+        from . import kernels as K
+        K.sfmn_norm_parts(self.x, self.x0, g, ws=self._ws)
+
+    def _control(self, f, closing=False):
+        from . import kernels as K
+        K.sfmn_control(f.detach().float().contiguous(), self._ws, self._per, self.ist, self.fst, self._fac, self.history,
+                       self.eps_history, self._alpha, self._gamma, self._worst, self.norm, self.lo, self.hi, closing=closing)
+
+    def _project(self, g):
+        from . import kernels as K
+        K.sfmn_select(self.x, self.x0, g, self.fst, self._fac, self._thr, self.norm)
+        K.sfmn_apply(self.x, self.x_adv, self.x0, g, self.ist, self._fac, self._thr, self.norm, self.lo, self.hi)
+
+
+_sparse_fmn_arguments = _arguments(SparseFMNRunner)
+
+
+def sparse_fmn_key(*args, **kwargs):
+    """arguments: SparseFMNRunner's after the model"""
+    return _key(_sparse_fmn_arguments(*args, **kwargs))
+
+
+def sparse_fmn_runner(model, *args, **kwargs):
+    """The model's SparseFMNRunner for the full argument tuple (SparseFMNRunner's after the model), made on first use; at most
+    _MAX_RUNNERS are kept, in a dictionary of their own (the other runners' caches are untouched)."""
+    a = _sparse_fmn_arguments(*args, **kwargs)
+    return _cached_runner(model, "_ud_sparse_fmn_runners", a, lambda: SparseFMNRunner(model, *a.values()))

@@ -270,7 +270,8 @@ class TrainEngine(AbstractEngine):
         optional "eps": "adv" is scored on x_adv for the samples the attack flipped within eps (found and radius <= eps; eps absent:
         every found sample) and on the clean input for the rest; "attack" then also holds "eps", "radius" (CPU tensor), "found"
         (CPU tensor) and "median_radius", gathered over the ranks in the scores' order (robust_curve(radius, grid) gives the
-        robust accuracy at every eps from this one run)."""
+        robust accuracy at every eps from this one run).  "method": "sparse_fmn" is the same path on the model's SparseFMNRunner
+        (norm "l1": radius and eps are sums of |x_adv - x|; "l0": numbers of changed elements)."""
         from .metrics import gather_scores
         attack = attack if attack is not None else self.config["config"].get("attack")
         if not attack:
@@ -290,10 +291,12 @@ class TrainEngine(AbstractEngine):
 
         attack = dict(attack)
         method = attack.pop("method", "pgd")
-        if method not in ("pgd", "apgd", "square", "apgd+square", "fmn"):
-            raise ValueError(f"attack method must be 'pgd', 'apgd', 'square', 'apgd+square' or 'fmn', got {method!r}")
+        if method not in ("pgd", "apgd", "square", "apgd+square", "fmn", "sparse_fmn"):
+            raise ValueError(f"attack method must be 'pgd', 'apgd', 'square', 'apgd+square', 'fmn' or 'sparse_fmn', got {method!r}")
         if method == "fmn":
-            return self._test_robust_fmn(batches, attack, score)
+            return self._test_robust_fmn(batches, attack, score, self.model_without_ddp.fmn_runner)
+        if method == "sparse_fmn":
+            return self._test_robust_fmn(batches, attack, score, self.model_without_ddp.sparse_fmn_runner)
         generator = square_generator = None
         square = None
         if method != "pgd":                                  # "seed" makes the random restarts / the draws reproducible
@@ -338,8 +341,9 @@ class TrainEngine(AbstractEngine):
                 "adv": self._metrics(*gather_scores(torch.cat(adv), labels), "Test(adv)"),
                 "attack": args}
 
-    def _test_robust_fmn(self, batches, attack, score):
-        """test_robust's "method": "fmn": attack is the dict without "method", score the scoring forward"""
+    def _test_robust_fmn(self, batches, attack, score, runner_of):
+        """test_robust's "method": "fmn" and "sparse_fmn": attack is the dict without "method", score the scoring forward,
+        runner_of the model's accessor of the minimum-norm runner (fmn_runner / sparse_fmn_runner)"""
         from .metrics import gather_scores
         eps = attack.pop("eps", None)
         if eps is not None and not float(eps) >= 0.0:
@@ -349,7 +353,7 @@ class TrainEngine(AbstractEngine):
             xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
             x, y = torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
             clean.append(score(x))
-            runner = self.model_without_ddp.fmn_runner(x.shape[0], x.shape[-1], **attack)
+            runner = runner_of(x.shape[0], x.shape[-1], **attack)
             xa = runner(x, y)
             take = runner.found.bool() if eps is None else runner.found.bool() & (runner.radius <= float(eps))
             adv.append(score(torch.where(take.reshape(-1, 1, 1, 1), xa, x)))

@@ -1666,8 +1666,93 @@ def fmn_project_l2(x, x0, dss, fst, lo, hi):
     return x
 
 
+# ---- Sparse minimum-norm attack (csrc/sfmn.hip) -----------------------------------------------------------------------------------
+SFMN_I = {"k": 0, "found": 1, "improved": 2}
+SFMN_F = {"eps": 0, "best": 1}
+SFMN_NORM = {"l1": 0, "l0": 1}
+SFMN_PARTS = {"gss": 0, "gmax": 1, "dabs": 2, "dcnt": 3}        # the doubles of one part (UD_SFMN_P_*)
+SFMN_CHUNK = 4096
+SFMN_L0_MAX_PER = 1 << 24                 # an L0 count lives in an fp32 state row: exact below this
+_SFMN_WS = Scratch(torch.float64)         # norm parts: written by sfmn_norm_parts, consumed by the sfmn_control behind it
+
+
+def sfmn_state(N, device):
+    """(ist, fst): zeroed control state for N samples"""
+    return _state(N, device, SFMN_I, SFMN_F)
+
+
+def sfmn_norms_ws_bytes(N, per):
+    return _call("ud_sfmn_norms_ws_bytes", int(N), int(per))
+
+
+def sfmn_ws(ref, N, per):
+    """The norm parts' workspace for [N, per] on ref's device, float64 [N, parts, 4], from the scratch owner (never freed:
+    a captured graph keeps its pointer)."""
+    need = sfmn_norms_ws_bytes(N, per) // 8
+    return _SFMN_WS.get(ref, need)[:need].view(N, need // (4 * N), 4)
+
+
+def _chk_sfmn_ws(ws, N, per):
+    _chk_f64(ws, sfmn_norms_ws_bytes(N, per) // 8)
+
+
+def sfmn_norm_parts(x, x0, g=None, ws=None):
+    """One pass over x, x0, g [N, ...] fp32: per 4096-element part of every sample (sum g^2, max |g|, sum |x - x0|, the number of
+    x != x0) as doubles into ws [N, parts, 4] (sfmn_ws unless given); g None: the two (x - x0) entries only."""
+    _chk_same(*((x, x0) if g is None else (x, x0, g)))
+    N = x.shape[0]
+    per = x.numel() // N
+    if ws is None:
+        ws = sfmn_ws(x, N, per)
+    _chk_sfmn_ws(ws, N, per)
+    _call("ud_sfmn_norm_parts", _p(x), _p(x0), _p(g), N, per, _p(ws), ws.numel() * 8, _stream())
+    return ws
+
+
+def sfmn_control(f, ws, per, ist, fst, fac, history, eps_history, alpha, gamma, worst, norm, lo, hi, closing=False):
+    """One step of the per-sample sparse-FMN state machine (include/unidefense_hip.h) on f [N] fp32 and the norm parts ws of
+    samples of `per` elements; (lo, hi): the clip, whose width enters the L0 estimate; closing: the keep-best decision only."""
+    _chk(f, history, eps_history, alpha, gamma, worst)
+    N, steps = f.numel(), alpha.numel()
+    _chk_state(ist, fst, N, SFMN_I, SFMN_F)
+    _chk_sfmn_ws(ws, N, per)
+    _chk_f64(fac, N)
+    if tuple(history.shape) != (steps + 1, N) or tuple(eps_history.shape) != (steps, N):
+        raise ValueError(f"history must be [{steps + 1}, {N}] and eps_history [{steps}, {N}], got {tuple(history.shape)} and "
+                         f"{tuple(eps_history.shape)}")
+    if gamma.numel() != steps or worst.numel() != N:
+        raise ValueError(f"gamma must hold {steps} values and worst {N}, got {gamma.numel()} and {worst.numel()}")
+    _call("ud_sfmn_control", _p(f), _p(ws), ws.numel() * 8, _p(ist), _p(fst), _p(fac), _p(history), _p(eps_history), _p(alpha),
+          _p(gamma), _p(worst), N, int(per), steps, SFMN_NORM[norm], float(lo), float(hi), int(bool(closing)), _stream())
+
+
+def sfmn_select(x, x0, g, fst, fac, thr, norm):
+    """Per sample the number the projection of z = x - g fac[n] needs, into thr [N] float64: "l1" the soft threshold tau of the
+    ball of radius fst[eps], "l0" the (eps + 1)-th largest |z - x0|; -1 where nothing is projected.  One workgroup per sample."""
+    _chk_same(x, x0, g)
+    N = x.shape[0]
+    _chk_state(None, fst, N, SFMN_I, SFMN_F)
+    _chk_f64(fac, N)
+    _chk_f64(thr, N)
+    _call("ud_sfmn_select", _p(x), _p(x0), _p(g), _p(fst), _p(fac), _p(thr), N, x.numel() // N, SFMN_NORM[norm], _stream())
+    return thr
+
+
+def sfmn_apply(x, x_best, x0, g, ist, fac, thr, norm, lo, hi):
+    """In place on x and x_best: the keep-best copy, then the step z = x - g fac[n] projected with sfmn_select's thr[n] ("l1":
+    soft threshold of z - x0; "l0": the elements above the threshold keep z, the others return to x0) and the clip."""
+    _chk_same(x, x_best, x0, g)
+    N = x.shape[0]
+    _chk_state(ist, None, N, SFMN_I, SFMN_F)
+    _chk_f64(fac, N)
+    _chk_f64(thr, N)
+    _call("ud_sfmn_apply", _p(x), _p(x_best), _p(x0), _p(g), _p(ist), _p(fac), _p(thr), N, x.numel() // N, SFMN_NORM[norm],
+          float(lo), float(hi), _stream())
+    return x
+
+
 # ---- Square attack (csrc/square.hip) ------------------------------------------------------------------------------------------
-SQUARE_I = {"k": 0, "accepted": 1, "active": 2, "queries": 3}
+SQUARE_I ={"k": 0, "accepted": 1, "active": 2, "queries": 3}
 SQUARE_F = {"f_best": 0}
 
 

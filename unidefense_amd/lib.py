@@ -184,6 +184,11 @@ _SIGNATURES = {
     "ud_fmn_control": [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P],
     "ud_fmn_update": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _F, _F, _P],
     "ud_fmn_project_l2": [_P, _P, _P, _P, _I, _L, _F, _F, _P],
+    "ud_sfmn_norms_ws_bytes": [_I, _L],
+    "ud_sfmn_norm_parts": [_P, _P, _P, _I, _L, _P, _L, _P],
+    "ud_sfmn_control": [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _F, _F, _I, _P],
+    "ud_sfmn_select": [_P, _P, _P, _P, _P, _P, _I, _L, _I, _P],
+    "ud_sfmn_apply": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _F, _F, _P],
     "ud_square_propose": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _I, _P],
     "ud_square_control": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "ud_absdiff_bwd": [_P, _P, _P, _P, _P, _L, _P],
@@ -277,10 +282,10 @@ _SIGNATURES = {
 _COUNT_FUNCS = {"ud_mb_eval_dw_ok", "ud_mb_eval_dw_tiles", "ud_mb_eval_dw_h_ok", "ud_mb_eval_dw_h_tiles", "ud_pj_fwd_fused_ok", "ud_pj_bwd_fused_ok", "ud_pj_bwd_fused_grid", "ud_pw_bwd_fused_ok", "ud_pw_bwd_fused_grid", "ud_loss_tail_ws_floats", "ud_dwtile_wgrad", "ud_dwtile_bwd", "ud_fft32_set_wave", "ud_fft2_two_pass_ws_floats", "ud_dwtile_ws_doubles", "ud_dwtile_wgrad_part_rows", "ud_reduce_ws_doubles", "ud_gemm_query_path", "ud_gemm_get_path", "ud_gemm_stats_slots", "ud_adamw_chunk_elems", "ud_rfft2_planes_ws_floats", "ud_fused_reduce_ws_doubles", "ud_dwconv_bwd_data_bn_ws_doubles", "ud_dwconv_bwd_weight_parts", "ud_sfmix_blocks", "ud_gate_mix_blocks",
                 "ud_l1_chunks", "ud_efdm_ws_bytes", "ud_conv_small_supported", "ud_conv_small_wgrad_supported", "ud_conv_mfma_supported", "ud_conv_mfma_wgrad_supported", "ud_conv_mfma_wgrad_ws_floats",
                 "ud_conv_small_wgrad_ws_floats", "ud_xchg_bytes", "ud_stem_dgrad_supported", "ud_sample_sumsq_ws_bytes",
-                "ud_coldot_bn_eval_ws_doubles", "ud_fmn_norms_ws_bytes"}
+                "ud_coldot_bn_eval_ws_doubles", "ud_fmn_norms_ws_bytes", "ud_sfmn_norms_ws_bytes"}
 _LONG_FUNCS = {"ud_mb_eval_dw_tiles", "ud_mb_eval_dw_h_tiles", "ud_pj_bwd_fused_grid", "ud_pw_bwd_fused_grid", "ud_fft2_two_pass_ws_floats", "ud_dwtile_ws_doubles", "ud_dwtile_wgrad_part_rows", "ud_xchg_bytes", "ud_efdm_ws_bytes", "ud_rfft2_planes_ws_floats", "ud_conv_small_wgrad_ws_floats", "ud_conv_mfma_wgrad_ws_floats", "ud_fused_reduce_ws_doubles",
                "ud_dwconv_bwd_data_bn_ws_doubles", "ud_sample_sumsq_ws_bytes", "ud_coldot_bn_eval_ws_doubles",
-               "ud_fmn_norms_ws_bytes"}        # return a C long
+               "ud_fmn_norms_ws_bytes", "ud_sfmn_norms_ws_bytes"}        # return a C long
 
 EXPORTED = tuple(_SIGNATURES)
 

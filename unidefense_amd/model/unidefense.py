@@ -248,6 +248,13 @@ class RunnerMethods:
         from ..attack import fmn_runner
         return fmn_runner(self, batch, size, **kwargs)
 
+    def sparse_fmn_runner(self, batch, size, **kwargs):
+        """The graph-replayed sparse minimum-norm attack for [batch, 3, size, size] inputs: per sample the smallest L1 distance
+        or the smallest number of changed elements that flips it (SparseFMNRunner; kwargs: norm ("l1" / "l0"), steps,
+        alpha_init, alpha_final, gamma_init, gamma_final, targeted, clip, objective, precision, grad_scale)."""
+        from ..attack import sparse_fmn_runner
+        return sparse_fmn_runner(self, batch, size, **kwargs)
+
     def square_runner(self, batch, size, **kwargs):
         """The graph-replayed Square attack (black-box, L-infinity, forward only) for [batch, 3, size, size] inputs
         (SquareRunner; kwargs: eps, steps, p_init, restarts, early_stop, check_every, clip, objective, precision)."""
