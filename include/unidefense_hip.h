@@ -702,6 +702,45 @@ int ud_square_propose(float* x_try, float* x_best, const float* x0, const int* i
 int ud_square_control(const float* f, int* ist, float* fst, float* history, int* decisions, int N, int steps, int early_stop,
                       ud_stream_t stream);
 
+/* ---- common image corruptions (csrc/corrupt.hip; unidefense_amd/corrupt.py: corrupt, CorruptionRunner) -------------------
+ * x, out fp32 [N][3][size][size], out != x.  Every corruption works on 8-bit levels and is ONE launch that reads x once and
+ * writes out once:
+ *   level  u = clamp(floor((x + 1) 127.5 + 0.5), 0, 255), fp32 without contraction; a NaN is level 0
+ *   out    = lut[level]: lut [256] fp32 made by the host in float64 (level / 127.5 - 1)
+ * and everything in between is int32 arithmetic that tests/test_corrupt_cpu.py restates in numpy bit for bit.
+ * ud_corrupt_jpeg: baseline JPEG without the (lossless) entropy coding.  Pad to a multiple of 16 (4:4:4: 8) by replicating the
+ *   last column and row; JFIF RGB -> YCbCr in Q16; 4:2:0: (a + b + c + d + 2) >> 2; level shift by 128; 8 x 8 DCT as two
+ *   integer products with T[k][n] = round(c_k cos((2n + 1) k pi / 16) 2^13): columns (s + 2^9) >> 10, rows (s + 2^12) >> 13
+ *   (eight times the coefficient); round-half-away division by 8 Q and multiplication by Q with qtab [128] int32 (luma
+ *   then chroma, row-major natural order, each 1..255); inverse columns (s + 2^10) >> 11, rows (s + 2^14) >> 15; + 128, clamp;
+ *   4:2:0 chroma back by the triangle filter (3/4, 1/4 in both directions, bias 8 on even and 7 on odd output columns, edges of
+ *   the padded plane replicated); YCbCr -> RGB in Q16, clamp; crop.  quality (1..100) is what qtab was made for; the kernel
+ *   reads qtab only.  subsampling: UD_CORRUPT_JPEG_420 or _444.
+ * ud_corrupt_blur: separable k-tap blur (k odd, <= 31, size >= (k + 1) / 2), reflect-101 borders, w [k] int32 summing to
+ *   2^14; per pass (sum w u + 2^13) >> 14.
+ * ud_corrupt_point: mode UD_CORRUPT_CONTRAST: 128 + (((u - 128) f8 + 128) >> 8) clamped; _SATURATION: the same on Cb and Cr
+ *   between the Q16 colour transforms; _NOISE: clamp(floor((u + s z) + 0.5)) with z fp32 [N][3][size][size] (one fp32 product,
+ *   two fp32 sums, no contraction; a NaN gives level 0).  f8 in 0..65536 (256 = factor 1), s in [0, 65536].
+ * ud_corrupt_pixelate: every factor x factor cell (1 <= factor <= 256) becomes (sum + cnt / 2) / cnt over the cnt pixels the
+ *   cell has inside the image.
+ * ud_corrupt_blocks: pos [N][count][2] int32 (row, column of a block's first pixel; any value): every pixel inside one of the
+ *   sample's 8 x 8 blocks becomes level 128, the rest lut[u].  0 <= count <= 1024; pos may be NULL when count == 0.
+ * UD_EINVAL before any HIP call: a NULL pointer, out == x, N < 1 or > 65535, size < 1 or > 32768, quality outside 1..100, an
+ * unknown subsampling or mode, k even, < 1, > 31 or > 2 size - 1, factor < 1 or > 256, f8 or count out of range, s < 0 or NaN. */
+#define UD_CORRUPT_JPEG_420 0
+#define UD_CORRUPT_JPEG_444 1
+#define UD_CORRUPT_CONTRAST 0
+#define UD_CORRUPT_SATURATION 1
+#define UD_CORRUPT_NOISE 2
+int ud_corrupt_jpeg(const float* x, float* out, const float* lut, const int* qtab, int N, int size, int quality, int subsampling,
+                    ud_stream_t stream);
+int ud_corrupt_blur(const float* x, float* out, const float* lut, const int* w, int N, int size, int k, ud_stream_t stream);
+int ud_corrupt_point(const float* x, float* out, const float* lut, const float* z, int N, int size, int mode, int f8, float s,
+                     ud_stream_t stream);
+int ud_corrupt_pixelate(const float* x, float* out, const float* lut, int N, int size, int factor, ud_stream_t stream);
+int ud_corrupt_blocks(const float* x, float* out, const float* lut, const int* pos, int N, int size, int count,
+                      ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

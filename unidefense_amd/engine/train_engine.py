@@ -371,6 +371,60 @@ class TrainEngine(AbstractEngine):
                 "adv": self._metrics(*gather_scores(torch.cat(adv), labels), "Test(adv)"),
                 "attack": args}
 
+    def test_corrupted(self, batches=4, corruptions=None, levels=(1, 2, 3, 4, 5), seed=None, subsampling="420"):
+        """test() on clean and on commonly corrupted inputs (unidefense_amd/corrupt.py): every test batch is scored as _score
+        does (inference_graph / inference_precision keep their meaning), then once per (kind, level) on corrupt(x, kind, level) —
+        one extra launch in front of the same scoring forward.  corruptions (default config['config']['corruptions'], then all
+        seven): names of corrupt.CORRUPTIONS; levels: severities 1..5; seed: seeds the device generator of the noise fields and
+        block positions; subsampling: JPEG's chroma format.  Returns {"clean": what test() returns, "corrupted": {kind: {level:
+        the same keys}}, "mean": {kind: {"AUC", "ACC"}} averaged over the levels (where both classes are present),
+        "corruptions": {kind: {level: the resolved parameter}}}.  Scores are gathered over the ranks as in _score."""
+        from .. import corrupt as CR
+        from .metrics import gather_scores
+        kinds = corruptions if corruptions is not None else self.config["config"].get("corruptions")
+        kinds = list(kinds) if kinds else list(CR.CORRUPTIONS)
+        levels = tuple(levels)
+        resolved = {k: {lv: CR.resolve(k, lv)[0][1] for lv in levels} for k in kinds}        # refuses before any kernel runs
+        if subsampling not in CR.SUBSAMPLINGS:
+            raise ValueError(f"subsampling must be one of {CR.SUBSAMPLINGS}, got {subsampling!r}")
+        self._select_gemm_path()
+        self.model.eval()
+        graphed = bool(self.config["config"].get("inference_graph", False))
+        precision = self.config["config"].get("inference_precision", "fp32")
+        generator = None if seed is None else torch.Generator(device=self.device).manual_seed(int(seed))
+
+        @torch.no_grad()
+        def score(x):
+            if graphed:
+                out = self.model_without_ddp.inference_runner(x.shape[0], x.shape[-1], precision)(x)
+            else:
+                out = self.model(x)
+            return torch.softmax(out["cls_out"], 1)[:, 0]
+
+        clean, labels, cor, x_cor = [], [], {(k, lv): [] for k in kinds for lv in levels}, None
+        for step in range(1, batches + 1):
+            xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
+            x = torch.cat([xr, xf], 0).contiguous()
+            clean.append(score(x))
+            labels.append(torch.cat([yr, yf], 0))
+            x_cor = torch.empty_like(x) if x_cor is None or x_cor.shape != x.shape else x_cor
+            for key in cor:
+                cor[key].append(score(CR.corrupt(x, key[0], key[1], generator=generator, subsampling=subsampling, out=x_cor)))
+        labels = torch.cat(labels)
+        ret = {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"), "corrupted": {}, "mean": {},
+               "corruptions": resolved}
+        for k in kinds:
+            ret["corrupted"][k] = {lv: self._metrics(*gather_scores(torch.cat(cor[(k, lv)]), labels), "Test(%s %d)" % (k, lv))
+                                   for lv in levels}
+            both = [r for r in ret["corrupted"][k].values() if "AUC" in r]
+            if both:
+                ret["mean"][k] = {m: float(sum(r[m] for r in both) / len(both)) for m in ("AUC", "ACC")}
+                if self.local_rank == 0:
+                    print("Corrupted %-14s | mean AUC %.4f, mean ACC %.4f | AUC by level %s" % (
+                        k, ret["mean"][k]["AUC"], ret["mean"][k]["ACC"],
+                        " ".join("%d:%.4f" % (lv, ret["corrupted"][k][lv]["AUC"]) for lv in levels if "AUC" in ret["corrupted"][k][lv])))
+        return ret
+
     def validate(self, step, batches=4):
         """The reference's validate (forgery_engine.py:320-421) without the figure / wandb plumbing: metrics over all
         ranks, best-so-far record (AUC + ACC), best_model.bin / latest_model.bin on rank 0."""

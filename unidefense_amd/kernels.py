@@ -1793,6 +1793,66 @@ def square_control(f, ist, fst, history, decisions, steps, early_stop=True):
     _call("ud_square_control", _p(f), _p(ist), _p(fst), _p(history), _p(decisions), N, int(steps), int(bool(early_stop)), _stream())
 
 
+# ---- common image corruptions (csrc/corrupt.hip): x, out contiguous fp32 [N, 3, size, size], one launch each -------------------
+CORRUPT_JPEG = {"420": 0, "444": 1}
+CORRUPT_POINT = {"contrast": 0, "saturation": 1, "gaussian_noise": 2}
+
+
+def _chk_images(x, out, lut):
+    _chk_same(x, out)
+    _chk(lut)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise ValueError(f"expected [N, 3, size, size] images, got {tuple(x.shape)}")
+    if lut.numel() != 256:
+        raise ValueError(f"the level table holds 256 values, got {tuple(lut.shape)}")
+    if x.data_ptr() == out.data_ptr():
+        raise ValueError("a corruption writes a buffer of its own: out is x")
+    return x.shape[0], x.shape[2]
+
+
+def corrupt_jpeg(x, out, lut, qtab, quality, subsampling="420"):
+    """out = JPEG(x) on 8-bit levels with the quantisation tables qtab [128] int32 (luma, chroma; made for `quality`)."""
+    N, size = _chk_images(x, out, lut)
+    _chk_i32(qtab, (128,), "qtab")
+    _call("ud_corrupt_jpeg", _p(x), _p(out), _p(lut), _p(qtab), N, size, int(quality), CORRUPT_JPEG[subsampling], _stream())
+    return out
+
+
+def corrupt_blur(x, out, lut, w):
+    """out = separable blur of x's levels with the integer taps w [k] int32 (sum 2^14), reflect-101 borders."""
+    N, size = _chk_images(x, out, lut)
+    _chk_i32(w, (w.numel(),), "w")
+    _call("ud_corrupt_blur", _p(x), _p(out), _p(lut), _p(w), N, size, w.numel(), _stream())
+    return out
+
+
+def corrupt_point(x, out, lut, kind, f8=0, s=0.0, z=None):
+    """kind "contrast" / "saturation": scale by f8 / 256 about level 128; "gaussian_noise": levels + s z, z like x."""
+    N, size = _chk_images(x, out, lut)
+    if z is not None:
+        _chk_same(x, z)
+    _call("ud_corrupt_point", _p(x), _p(out), _p(lut), _p(z), N, size, CORRUPT_POINT[kind], int(f8), float(s), _stream())
+    return out
+
+
+def corrupt_pixelate(x, out, lut, factor):
+    """every factor x factor cell of x's levels becomes its integer mean"""
+    N, size = _chk_images(x, out, lut)
+    _call("ud_corrupt_pixelate", _p(x), _p(out), _p(lut), N, size, int(factor), _stream())
+    return out
+
+
+def corrupt_blocks(x, out, lut, pos):
+    """pos [N, count, 2] int32 (row, column): every 8 x 8 block becomes level 128, clipped by the image"""
+    N, size = _chk_images(x, out, lut)
+    if pos.dim() != 3:
+        raise ValueError(f"pos must be [N, count, 2], got {tuple(pos.shape)}")
+    count = pos.shape[1]
+    _chk_i32(pos, (N, count, 2), "pos")
+    _call("ud_corrupt_blocks", _p(x), _p(out), _p(lut), _p(pos) if count else None, N, size, count, _stream())
+    return out
+
+
 def conv_gather_wgrad(a, x, g):
     """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)]."""
     _chk(a, x)

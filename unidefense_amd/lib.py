@@ -191,6 +191,11 @@ _SIGNATURES = {
     "ud_sfmn_apply": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _F, _F, _P],
     "ud_square_propose": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _I, _P],
     "ud_square_control": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "ud_corrupt_jpeg": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "ud_corrupt_blur": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "ud_corrupt_point": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "ud_corrupt_pixelate": [_P, _P, _P, _I, _I, _I, _P],
+    "ud_corrupt_blocks": [_P, _P, _P, _P, _I, _I, _I, _P],
     "ud_absdiff_bwd": [_P, _P, _P, _P, _P, _L, _P],
     "ud_outer": [_P, _P, _P, _L, _I, _P],
     "ud_gather2d": [_P, _P, _P, _P, _L, _I, _I, _P],

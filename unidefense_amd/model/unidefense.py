@@ -261,6 +261,13 @@ class RunnerMethods:
         from ..attack import square_runner
         return square_runner(self, batch, size, **kwargs)
 
+    def corruption_runner(self, batch, size, kind, **kwargs):
+        """A common corruption (JPEG, blur, noise, pixelation, contrast, saturation, blocks, or a chain of them) in front of the
+        graph-replayed eval forward for [batch, 3, size, size] inputs (unidefense_amd/corrupt.py: CorruptionRunner; kwargs:
+        level, param, precision, subsampling)."""
+        from ..corrupt import corruption_runner
+        return corruption_runner(self, batch, size, kind, **kwargs)
+
 
 class UniDefenseModelEb4(RunnerMethods, nn.Module):
     """UniDefense model with EfficientNet backbone (reference: model/unidefense.py:28-256)."""
