@@ -741,6 +741,50 @@ int ud_corrupt_pixelate(const float* x, float* out, const float* lut, int N, int
 int ud_corrupt_blocks(const float* x, float* out, const float* lut, const int* pos, int N, int size, int count,
                       ud_stream_t stream);
 
+/* ---- affine warps and the worst-case spatial search (csrc/warp.hip; unidefense_amd/spatial.py: warp, SpatialRunner) --------
+ * ud_warp_affine: x, out fp32 [N][3][size][size], out != x; lut [256] fp32, the corruptions' level table; mat [rows][6] int32
+ *   and row [N] int32 on the device: sample n uses mat[clamp(row[n], 0, rows - 1)].  The clamp is part of the contract: both
+ *   tables are device data that the host cannot see at launch, and the kernel stays in bounds for any content of either.
+ *   ONE launch, defined in exact integers (int64 where written), restated in numpy by tests/test_spatial_cpu.py bit for bit:
+ *     levels       u = clamp(floor((x + 1) 127.5 + 0.5), 0, 255), fp32 without contraction; a NaN is level 0
+ *     coordinates  for the output pixel at row r, column c: X = 2c + 1 - size, Y = 2r + 1 - size (centred half pixels); with
+ *                  (m00, m01, o0, m10, m11, o1) the sample's row of mat:
+ *                    px = (m00 X + m01 Y + o0 + ((size - 1) << 16)) >> 1,  py = (m10 X + m11 Y + o1 + ((size - 1) << 16)) >> 1
+ *                  in int64 with arithmetic shift: the source column and row in Q16 pixels
+ *     taps         x0 = px >> 16, fx = (px >> 8) & 255, y0 and fy likewise; the four taps (y0 | y0 + 1, x0 | x0 + 1), each index
+ *                  through the border rule on its own:
+ *                    UD_WARP_REFLECT  reflect-101: j = i mod 2 (size - 1) (mathematical mod, any distance), j = 2 (size - 1) - j
+ *                                     where j >= size; size == 1: index 0
+ *                    UD_WARP_EDGE     clamp to 0 .. size - 1
+ *                    UD_WARP_FILL     a tap whose row or column lies outside has level 128
+ *     interpolation v = ((256 - fx)(256 - fy) u00 + fx (256 - fy) u01 + (256 - fx) fy u10 + fx fy u11 + 32768) >> 16: fits int32,
+ *                  needs no clamp
+ *     output       out = lut[v]
+ *   The host makes a row of mat from the inverse of p_out = scale R(angle) diag(flip ? -1 : 1, 1) p_src + shift in float64:
+ *   m = floor(A^-1 65536 + 0.5), o = floor(2 (-A^-1 shift) 65536 + 0.5) (spatial.affine_q16).
+ * ud_spatial_control: the per-sample state of a search over K candidates, one thread per sample, so that one query (warp,
+ *   forward, f, control) is a static launch sequence inside a captured graph:
+ *     ist [3][N] int32 : rows UD_SPATIAL_I_K (the sample's counter), _BEST_K (the candidate with the lowest f), _ROW (the row of
+ *                        mat [K N][6] the next warp reads for the sample: ud_warp_affine's `row` is this row of ist)
+ *     fst [1][N] fp32  : row UD_SPATIAL_F_BEST (the lowest f so far)
+ *     history [K][N] fp32 : row k = f of candidate k
+ *   closing == 0, with k = ist[K][n] in [0, K): history[k][n] = f[n]; where k == 0 or f[n] < f_best[n] (strict: a tie keeps the
+ *   lowest k, a NaN never wins) f_best[n] = f[n], best_k[n] = k; row[n] = min(k + 1, K - 1) N + n; ist[K][n] = k + 1.  k outside
+ *   [0, K) writes nothing.  The caller zeroes the state and sets row[n] = n to start a run.
+ *   closing != 0: only row[n] = clamp(best_k[n], 0, K - 1) N + n (f, fst, history may be NULL).
+ * UD_EINVAL before any HIP call: a NULL pointer, out == x, N < 1 or > 65535, size < 1 or > 32768, rows < 1, an unknown border;
+ * K < 1, N < 1, K N > 2^31 - 1. */
+#define UD_WARP_REFLECT 0
+#define UD_WARP_EDGE 1
+#define UD_WARP_FILL 2
+#define UD_SPATIAL_I_K 0
+#define UD_SPATIAL_I_BEST_K 1
+#define UD_SPATIAL_I_ROW 2
+#define UD_SPATIAL_F_BEST 0
+int ud_warp_affine(const float* x, float* out, const float* lut, const int* mat, const int* row, int N, int size, int rows,
+                   int border, ud_stream_t stream);
+int ud_spatial_control(const float* f, int* ist, float* fst, float* history, int K, int N, int closing, ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

@@ -10,19 +10,11 @@
 // fp32 operations with contraction off — so tests/test_corrupt_cpu.py restates every kernel in numpy and the GPU tests compare
 // bit for bit.  Ordinary vector loads and stores only, no atomics, nothing shared between workgroups: a replay gives the same bits.
 #include "attack_common.h"
+#include "levels.h"
 
 namespace {
 
-// ---- (a) and the colour transforms ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ int level_of(float x) {
-#pragma clang fp contract(off)
-    const float t = (x + 1.0f) * 127.5f;
-    if (!(t == t)) return 0;                       // NaN: level 0, on purpose
-    float v = floorf(t + 0.5f);
-    v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);   // +-inf clamp like any other value
-    return (int)v;
-}
-
+// ---- (a): level_of (levels.h), and the colour transforms ----------------------------------------------------------------------
 // a value already in level units (noise): round half up, clamp, NaN -> 0
 __device__ __forceinline__ int level_round(float v) {
 #pragma clang fp contract(off)

@@ -425,6 +425,58 @@ class TrainEngine(AbstractEngine):
                         " ".join("%d:%.4f" % (lv, ret["corrupted"][k][lv]["AUC"]) for lv in levels if "AUC" in ret["corrupted"][k][lv])))
         return ret
 
+    def test_spatial(self, batches=4, spatial=None):
+        """test() on clean inputs and on each sample's worst spatial candidate (unidefense_amd/spatial.py): every test batch is
+        scored as _score does (inference_graph / inference_precision keep their meaning), searched with the true labels by the
+        model's SpatialRunner and scored again the same way on its x_adv.  spatial (default config['config']['spatial'], then the
+        runner's defaults): the runner's keyword arguments, e.g. {"max_angle": 10.0, "max_shift": 0.05, "grid": (7, 5, 3)}; an
+        optional "seed" seeds the CPU generator of a random search.  Returns {"clean": what test() returns, "adv": the same keys on
+        x_adv, "attack": the resolved arguments plus "best" (CPU [n, 5]: each sample's (angle, dx, dy, scale, flip)) and "fooled"
+        (the fraction with best_loss <= 0 among the samples with loss0 > 0; NaN where there are none)}.  Scores, best and the
+        two losses are gathered over the ranks as in _score."""
+        from .metrics import gather_scores
+        spatial = spatial if spatial is not None else self.config["config"].get("spatial")
+        spatial = dict(spatial) if spatial else {}
+        seed = spatial.pop("seed", None)
+        generator = None if seed is None else torch.Generator().manual_seed(int(seed))
+        self._select_gemm_path()
+        self.model.eval()
+        graphed = bool(self.config["config"].get("inference_graph", False))
+        precision = self.config["config"].get("inference_precision", "fp32")
+
+        @torch.no_grad()
+        def score(x):
+            if graphed:
+                out = self.model_without_ddp.inference_runner(x.shape[0], x.shape[-1], precision)(x)
+            else:
+                out = self.model(x)
+            return torch.softmax(out["cls_out"], 1)[:, 0]
+
+        clean, adv, labels, best, best_loss, loss0, runner = [], [], [], [], [], [], None
+        for step in range(1, batches + 1):
+            xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
+            x, y = torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
+            try:
+                runner = self.model_without_ddp.spatial_runner(x.shape[0], x.shape[-1], **spatial)
+            except TypeError as e:                       # an unknown key is a bad dict, like a bad value
+                raise ValueError(f"spatial takes SpatialRunner's keyword arguments and 'seed': {e}") from None
+            clean.append(score(x))
+            adv.append(score(runner(x, y, generator)))
+            labels.append(y)
+            best.append(runner.best.to(self.device))
+            best_loss.append(runner.best_loss.clone())
+            loss0.append(runner.loss0.clone())
+        labels = torch.cat(labels)
+        best = torch.stack([gather_scores(torch.cat(best)[:, i].contiguous(), labels)[0] for i in range(5)], 1).cpu()
+        best_loss, _ = gather_scores(torch.cat(best_loss), labels)
+        loss0, _ = gather_scores(torch.cat(loss0), labels)
+        held = loss0 > 0
+        args = dict(runner.args)
+        args.update(best=best, fooled=float((best_loss[held] <= 0).double().mean()) if bool(held.any()) else float("nan"))
+        return {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"),
+                "adv": self._metrics(*gather_scores(torch.cat(adv), labels), "Test(spatial)"),
+                "attack": args}
+
     def validate(self, step, batches=4):
         """The reference's validate (forgery_engine.py:320-421) without the figure / wandb plumbing: metrics over all
         ranks, best-so-far record (AUC + ACC), best_model.bin / latest_model.bin on rank 0."""

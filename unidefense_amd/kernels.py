@@ -1853,6 +1853,42 @@ def corrupt_blocks(x, out, lut, pos):
     return out
 
 
+# ---- affine warps and the spatial search's state (csrc/warp.hip) ---------------------------------------------------------------
+WARP_BORDER = {"reflect": 0, "edge": 1, "fill": 2}
+SPATIAL_I = {"k": 0, "best_k": 1, "row": 2}
+SPATIAL_F = {"f_best": 0}
+
+
+def spatial_state(N, device):
+    """(ist, fst): zeroed control state for N samples"""
+    return _state(N, device, SPATIAL_I, SPATIAL_F)
+
+
+def warp_affine(x, out, lut, mat, row, border="reflect"):
+    """out = x's levels warped by the Q16 affine maps mat [rows, 6] int32, sample n by mat[clamp(row[n], 0, rows - 1)] (row [N]
+    int32), bilinear in integers with the border rule "reflect" (101) / "edge" / "fill" (level 128); one launch."""
+    N, size = _chk_images(x, out, lut)
+    if mat.dim() != 2 or mat.shape[0] < 1:
+        raise ValueError(f"mat must be [rows, 6] with rows >= 1, got {tuple(mat.shape)}")
+    _chk_i32(mat, (mat.shape[0], 6), "mat")
+    _chk_i32(row, (N,), "row")
+    if border not in WARP_BORDER:
+        raise ValueError(f"border must be one of {tuple(WARP_BORDER)}, got {border!r}")
+    _call("ud_warp_affine", _p(x), _p(out), _p(lut), _p(mat), _p(row), N, size, mat.shape[0], WARP_BORDER[border], _stream())
+    return out
+
+
+def spatial_control(f, ist, fst, history, closing=False):
+    """One step of the per-sample search state on f [N] fp32 with k = ist's counter: history[k] = f, f_best / best_k follow a
+    strictly lower f, row = min(k + 1, K - 1) N + n for the next warp (K = history's rows); closing: only row = best_k N + n."""
+    _chk(f, history)
+    N = f.numel()
+    _chk_state(ist, fst, N, SPATIAL_I, SPATIAL_F)
+    if history.dim() != 2 or history.shape[0] < 1 or history.shape[1] != N:
+        raise ValueError(f"history must be [K, {N}] with K >= 1, got {tuple(history.shape)}")
+    _call("ud_spatial_control", _p(f), _p(ist), _p(fst), _p(history), history.shape[0], N, int(bool(closing)), _stream())
+
+
 def conv_gather_wgrad(a, x, g):
     """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)]."""
     _chk(a, x)

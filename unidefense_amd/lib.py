@@ -196,6 +196,8 @@ _SIGNATURES = {
     "ud_corrupt_point": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "ud_corrupt_pixelate": [_P, _P, _P, _I, _I, _I, _P],
     "ud_corrupt_blocks": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "ud_warp_affine": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "ud_spatial_control": [_P, _P, _P, _P, _I, _I, _I, _P],
     "ud_absdiff_bwd": [_P, _P, _P, _P, _P, _L, _P],
     "ud_outer": [_P, _P, _P, _L, _I, _P],
     "ud_gather2d": [_P, _P, _P, _P, _L, _I, _I, _P],

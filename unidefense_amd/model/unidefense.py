@@ -268,6 +268,13 @@ class RunnerMethods:
         from ..corrupt import corruption_runner
         return corruption_runner(self, batch, size, kind, **kwargs)
 
+    def spatial_runner(self, batch, size, **kwargs):
+        """The graph-replayed worst case over rotations, shifts, scales and mirrors (black-box, forward only) for [batch, 3, size,
+        size] inputs (unidefense_amd/spatial.py: SpatialRunner; kwargs: max_angle, max_shift, scales, flip, search, grid, k,
+        border, objective, precision)."""
+        from ..spatial import spatial_runner
+        return spatial_runner(self, batch, size, **kwargs)
+
 
 class UniDefenseModelEb4(RunnerMethods, nn.Module):
     """UniDefense model with EfficientNet backbone (reference: model/unidefense.py:28-256)."""
