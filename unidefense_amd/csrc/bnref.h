@@ -7,41 +7,185 @@ namespace {
 
 constexpr int NT = UD_COL_NT;
 
-// rows in flight per thread: a half quad is an 8-byte access, so twice the rows keep the same bytes in flight
-template <typename T> constexpr int kRowUnroll = sizeof(T) == 2 ? 8 : 4;
+// rows in flight per thread of the streaming loops (for_rows), both storage types: the element-wise geometry (geom_ew) hands a
+// thread 4 rows, and 8 rows x 2 tensors of converted half quads do not fit 128 VGPRs without spilling
+constexpr int kRowGroup = 4;
 
 __device__ __forceinline__ void atomic_add_f64(double* p, double v) { unsafeAtomicAdd(p, v); }
 
 struct Bn4 { f32x4 mu, is, ga, be; };
 
-// Coefficients of channel quad c4 from the fp64 sums; the designated thread of a kernel (update == true for exactly
-// one thread per channel quad per launch) also moves the running statistics (nn.BatchNorm2d training forward).  The eval form
-// (sum == NULL) takes the running statistics as the moments and never writes them.
-__device__ __forceinline__ Bn4 bn_load(const ud_bn_ref& b, int g, int C4, int c4, bool update) {
-    Bn4 o;
-    const long i0 = ((long)(b.G == 1 ? 0 : g) * C4 + c4) * 4;
+// the row bodies handed to for_rows must vanish into its unrolled groups
+#define UD_LAMBDA_INLINE __attribute__((always_inline))
+
+// a * b rounded on its own, never contracted into a neighbouring add: where the one-row loops had a branch between a product
+// and the sum that follows it, the grouped loops have straight-line code, and results are to stay bit for bit what they were
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ f32x4 mul_rn(const f32x4& a, const f32x4& b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ f32x4 mul_rn(const f32x4& a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+// bn_load in two parts, so that a consumer has the coefficient loads AND its first rows in flight together: bn_issue decides the
+// form once (kernel-uniform) and issues the quad's loads back to back — no wait, no branch between them (the fp64 accumulators
+// are caller-owned: 8-byte accesses); bn_finish turns them into coefficients, the first use of the loaded values.
+struct BnRaw {
+    double s[4], ss[4];          // training form: the fp64 sums
+    float rm[4], rv[4];          // eval form: the running statistics
+    f32x4 ga, be;
+};
+
+__device__ __forceinline__ BnRaw bn_issue(const ud_bn_ref& b, int g, int C4, int c4) {
+    BnRaw r;
+    if (b.sum) {
+        const long i0 = ((long)(b.G == 1 ? 0 : g) * C4 + c4) * 4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r.s[e] = b.sum[i0 + e];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r.ss[e] = b.sumsq[i0 + e];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r.rm[e] = r.rv[e] = 0.f;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r.rm[e] = b.running_mean[c4 * 4 + e];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r.rv[e] = b.running_var[c4 * 4 + e];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r.s[e] = r.ss[e] = 0.0;
+    }
+    r.ga = reinterpret_cast<const f32x4*>(b.gamma)[c4];
+    r.be = reinterpret_cast<const f32x4*>(b.beta)[c4];
+    return r;
+}
+
+// (mean, biased variance) of the quad: ud_bn_moments' two forms
+__device__ __forceinline__ void bn_moments4(const ud_bn_ref& b, const BnRaw& r, double (&m)[4], double (&v)[4]) {
+    const bool train = b.sum != nullptr;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        double m, v;
-        ud_bn_moments(b, i0 + e, c4 * 4 + e, m, v);
-        o.mu[e] = (float)m;
-        o.is[e] = rsqrtf((float)(v + (double)b.eps));
-        if (update && b.sum && b.running_mean) {
-            const int c = c4 * 4 + e;
-            b.running_mean[c] = (1.f - b.momentum) * b.running_mean[c] + b.momentum * (float)m;
-            b.running_var[c] = (1.f - b.momentum) * b.running_var[c] + b.momentum * (float)(v * b.unbias);
-        }
+        const double mt = r.s[e] * b.inv_count;
+        double vt = r.ss[e] * b.inv_count - mt * mt;
+        if (vt < 0.0) vt = 0.0;
+        m[e] = train ? mt : (double)r.rm[e];
+        v[e] = train ? vt : (double)r.rv[e];
     }
-    o.ga = reinterpret_cast<const f32x4*>(b.gamma)[c4];
-    o.be = reinterpret_cast<const f32x4*>(b.beta)[c4];
+}
+
+__device__ __forceinline__ Bn4 bn_finish(const ud_bn_ref& b, const BnRaw& r) {
+    Bn4 o;
+    double m[4], v[4];
+    bn_moments4(b, r, m, v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        o.mu[e] = (float)m[e];
+        o.is[e] = rsqrtf((float)(v[e] + (double)b.eps));
+    }
+    o.ga = r.ga;
+    o.be = r.be;
     return o;
 }
 
+// The designated thread of a kernel (exactly one per channel quad per launch) moves the running statistics (nn.BatchNorm2d
+// training forward) — behind its row loop, off the path in front of it: the sums again (one thread per quad, L2 hits) and the
+// eight running values in one trip, then the eight stores.  The eval form (sum == NULL) takes the running statistics as the
+// moments and never writes them.
+__device__ __forceinline__ void bn_update_running(const ud_bn_ref& b, int g, int C4, int c4) {
+    if (!(b.sum && b.running_mean)) return;
+    const BnRaw r = bn_issue(b, g, C4, c4);
+    float rm[4], rv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) rm[e] = b.running_mean[c4 * 4 + e];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) rv[e] = b.running_var[c4 * 4 + e];
+    double m[4], v[4];
+    bn_moments4(b, r, m, v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        rm[e] = mul_rn(1.f - b.momentum, rm[e]) + mul_rn(b.momentum, (float)m[e]);
+        rv[e] = mul_rn(1.f - b.momentum, rv[e]) + mul_rn(b.momentum, (float)(v[e] * b.unbias));
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) b.running_mean[c4 * 4 + e] = rm[e];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) b.running_var[c4 * 4 + e] = rv[e];
+}
+
+// Coefficients of channel quad c4 in one call, for consumers that stage tiles rather than stream rows (csrc/dwtile.hip);
+// update == true for exactly one thread per channel quad per launch.
+__device__ __forceinline__ Bn4 bn_load(const ud_bn_ref& b, int g, int C4, int c4, bool update) {
+    const Bn4 o = bn_finish(b, bn_issue(b, g, C4, c4));
+    if (update) bn_update_running(b, g, C4, c4);
+    return o;
+}
+
+// ACT is a template parameter in the streaming loops: a test of the run-time `act` per element makes every element its own basic
+// block, and the next row's load is then not hoisted across it (one row in flight per thread)
+template <int ACT>
+__device__ __forceinline__ f32x4 bn_apply(const f32x4& a, const Bn4& b) {
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = ud_act_fast(b.ga[e] * ((a[e] - b.mu[e]) * b.is[e]) + b.be[e], ACT);
+    return o;
+}
 __device__ __forceinline__ f32x4 bn_apply(const f32x4& a, const Bn4& b, int act) {
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = ud_act_fast(b.ga[e] * ((a[e] - b.mu[e]) * b.is[e]) + b.be[e], act);
     return o;
+}
+
+// f(ActC<A>{}) with A = act as a compile-time constant (ud_act_fast's reading of act: 1 swish, 2 ReLU, anything else identity):
+// the loop versioning of the streaming kernels
+template <int A> struct ActC { static constexpr int value = A; };
+template <typename F>
+__device__ __forceinline__ void act_switch(int act, F&& f) {
+    if (act == 1) f(ActC<1>{});
+    else if (act == 2) f(ActC<2>{});
+    else f(ActC<0>{});
+}
+
+// This thread's rows r, r + rs, ... < r_end, quad index idx (+ step per row), NIN tensors read per row: groups of kRowGroup
+// rows are LOADED back to back, then computed in ascending row order (body(idx, r, v[NIN])); the tail runs row by row.  `fin`
+// runs once, behind the first group's loads — the place to wait for the prologue's loads (bn_finish, the gate's sigmoid), so that
+// coefficients and first rows share one round trip.
+template <typename T, int NIN, typename Fin, typename Body>
+__device__ __forceinline__ void for_rows(int r, int r_end, int rs, long idx, long step, const In4<T> (&in)[NIN], Fin&& fin,
+                                         Body&& body) {
+    constexpr int U = kRowGroup;
+    f32x4 v[U][NIN];
+    auto load = [&]() UD_LAMBDA_INLINE {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int t = 0; t < NIN; ++t) v[u][t] = in[t][idx + u * step];
+    };
+    auto compute = [&]() UD_LAMBDA_INLINE {
+#pragma unroll
+        for (int u = 0; u < U; ++u) body(idx + u * step, r + u * rs, v[u]);
+        r += U * rs;
+        idx += U * step;
+    };
+    const bool full = r + (U - 1) * rs < r_end;
+    if (full) load();
+    fin();
+    if (full) compute();
+    while (r + (U - 1) * rs < r_end) {
+        load();
+        compute();
+    }
+    for (; r < r_end; r += rs, idx += step) {
+        f32x4 t[NIN];
+#pragma unroll
+        for (int k = 0; k < NIN; ++k) t[k] = in[k][idx];
+        body(idx, r, t);
+    }
 }
 
 __device__ __forceinline__ float gate_factor(const float* alpha, int mode) {

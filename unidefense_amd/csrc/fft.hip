@@ -319,11 +319,12 @@ __global__ __launch_bounds__(NT) void rfft2_kernel(const T* __restrict__ x, T* _
         float mu = 0.f, is = 1.f, ga = 1.f, be = 0.f;
         if (EX && has_bn) {
             double m, vv;
+            // gamma / beta issued with the sums: one round trip, not two
+            ga = bn.gamma[chl];
+            be = bn.beta[chl];
             ud_bn_moments(bn, chl, chl, m, vv);          // (the eval form: the running statistics, never written)
             mu = (float)m;
             is = (float)(1.0 / sqrt(vv + (double)bn.eps));
-            ga = bn.gamma[chl];
-            be = bn.beta[chl];
             if (n == 0 && q == 0 && cok && bn.sum && bn.running_mean) {          // one thread per channel
                 bn.running_mean[ch] = (1.f - bn.momentum) * bn.running_mean[ch] + bn.momentum * (float)m;
                 bn.running_var[ch] = (1.f - bn.momentum) * bn.running_var[ch] + bn.momentum * (float)(vv * bn.unbias);
@@ -669,11 +670,12 @@ __global__ __launch_bounds__(NT, 4) void irfft2_dwbwd_kernel(const T* __restrict
     float mu, is, ga, be;
     {
         double m, vv;
+        // gamma / beta issued with the sums: one round trip, not two
+        ga = bn.gamma[chl];
+        be = bn.beta[chl];
         ud_bn_moments(bn, chl, chl, m, vv);          // (the eval form: the running statistics, never written)
         mu = (float)m;
         is = (float)(1.0 / sqrt(vv + (double)bn.eps));
-        ga = bn.gamma[chl];
-        be = bn.beta[chl];
     }
     __syncthreads();                                    // the transform's planes are free: stage a and dd, [h][w][c]
     float* A = lds;
@@ -890,11 +892,12 @@ __global__ __launch_bounds__(NT2) void rows_fwd_kernel(const T* __restrict__ x, 
     float mu = 0.f, is = 1.f, ga = 1.f, be = 0.f;
     if (EX && has_bn) {
         double m, vv;
+        // gamma / beta issued with the sums: one round trip, not two
+        ga = bn.gamma[ch];
+        be = bn.beta[ch];
         ud_bn_moments(bn, ch, ch, m, vv);          // (the eval form: the running statistics, never written)
         mu = (float)m;
         is = (float)(1.0 / sqrt(vv + (double)bn.eps));
-        ga = bn.gamma[ch];
-        be = bn.beta[ch];
         if (n == 0 && h == 0 && bn.sum && bn.running_mean) {          // one thread per channel
             bn.running_mean[ch] = (1.f - bn.momentum) * bn.running_mean[ch] + bn.momentum * (float)m;
             bn.running_var[ch] = (1.f - bn.momentum) * bn.running_var[ch] + bn.momentum * (float)(vv * bn.unbias);
@@ -1168,11 +1171,12 @@ __global__ __launch_bounds__(NTW) void rfft2_wave_kernel(const T* __restrict__ x
     float mu = 0.f, is = 1.f, ga = 1.f, be = 0.f;
     if (EX && has_bn) {
         double m, vv;
+        // gamma / beta issued with the sums: one round trip, not two
+        ga = bn.gamma[chl];
+        be = bn.beta[chl];
         ud_bn_moments(bn, chl, chl, m, vv);          // (the eval form: the running statistics, never written)
         mu = (float)m;
         is = (float)(1.0 / sqrt(vv + (double)bn.eps));
-        ga = bn.gamma[chl];
-        be = bn.beta[chl];
         if (n == 0 && wave == 0 && hh == 0 && cok && bn.sum && bn.running_mean) {          // one thread per channel
             bn.running_mean[ch] = (1.f - bn.momentum) * bn.running_mean[ch] + bn.momentum * (float)m;
             bn.running_var[ch] = (1.f - bn.momentum) * bn.running_var[ch] + bn.momentum * (float)(vv * bn.unbias);

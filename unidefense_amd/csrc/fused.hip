@@ -105,21 +105,30 @@ __global__ __launch_bounds__(NT) void colsum_bn_kernel(RedGeom q, const T* __res
     double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float mo = 0.f;          // !DOT, amax: max |act(bn(x))| as a side output (the scale of the planes ud_se_scale_bn_planes writes)
     if (active) {
-        const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, !DOT && is_updater(ri));
-        Rows w = rows_of(q, ri, c4);
-#pragma unroll kRowUnroll<T>
-        for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) {
-            f32x4 a = bn_apply(x4[w.idx], cb, bn.act);
-            if (DOT) {
-                f32x4 d = d4[w.idx];
+        const BnRaw raw = bn_issue(bn, blockIdx.z, q.C4, c4);
+        Bn4 cb;
+        const Rows w = rows_of(q, ri, c4);
+        auto fin = [&]() UD_LAMBDA_INLINE { cb = bn_finish(bn, raw); };
+        act_switch(bn.act, [&](auto ac) UD_LAMBDA_INLINE {
+            constexpr int ACT = decltype(ac)::value;
+            if constexpr (DOT) {
+                const In4<T> in[2] = {x4, d4};
+                for_rows<T, 2>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long, int, const f32x4(&t)[2]) UD_LAMBDA_INLINE {
+                    const f32x4 a = bn_apply<ACT>(t[0], cb);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += (double)d[e] * (double)a[e];
+                    for (int e = 0; e < 4; ++e) v[e] += (double)t[1][e] * (double)a[e];
+                });
             } else {
+                const In4<T> in[1] = {x4};
+                for_rows<T, 1>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long, int, const f32x4(&t)[1]) UD_LAMBDA_INLINE {
+                    const f32x4 a = bn_apply<ACT>(t[0], cb);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += (double)a[e];
-                mo = fmaxf(mo, fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))));
+                    for (int e = 0; e < 4; ++e) v[e] += (double)a[e];
+                    mo = fmaxf(mo, fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))));
+                });
             }
-        }
+        });
+        if (!DOT && is_updater(ri)) bn_update_running(bn, blockIdx.z, q.C4, c4);
     }
     red_out<4>(q, ri, active, c4, v, out, nullptr, part, true);
     if (!DOT) ud_absmax_commit(mo, amax);
@@ -151,17 +160,24 @@ __global__ __launch_bounds__(NT) void se_scale_bn_kernel(RedGeom q, const T* __r
     if (thread_coords(q, ri, c4)) {
         const In4<T> x4{x};
         const Out4<T> y4{y};
-        const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, false);
+        const BnRaw raw = bn_issue(bn, blockIdx.z, q.C4, c4);
         f32x4 gate = reinterpret_cast<const f32x4*>(s)[(long)blockIdx.z * q.C4 + c4];
+        Bn4 cb;
+        const Rows w = rows_of(q, ri, c4);
+        const In4<T> in[1] = {x4};
+        auto fin = [&]() UD_LAMBDA_INLINE {
+            cb = bn_finish(bn, raw);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]);
-        Rows w = rows_of(q, ri, c4);
-#pragma unroll kRowUnroll<T>
-        for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) {
-            const f32x4 v = bn_apply(x4[w.idx], cb, bn.act) * gate;
-            y4.st(w.idx, v);
-            m = fmaxf(m, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-        }
+            for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]);
+        };
+        act_switch(bn.act, [&](auto ac) UD_LAMBDA_INLINE {
+            constexpr int ACT = decltype(ac)::value;
+            for_rows<T, 1>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long idx, int, const f32x4(&t)[1]) UD_LAMBDA_INLINE {
+                const f32x4 v = bn_apply<ACT>(t[0], cb) * gate;
+                y4.st(idx, v);
+                m = fmaxf(m, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+            });
+        });
     }
     ud_absmax_commit(m, amax);
 }
@@ -174,6 +190,14 @@ __global__ __launch_bounds__(NT) void se_scale_bn_planes_kernel(RedGeom q, const
                                                                 const float* __restrict__ s, uint16_t* __restrict__ planes,
                                                                 long panel, long plane, const uint32_t* __restrict__ amax_in,
                                                                 float* __restrict__ inv_scale) {
+    int ri, c4;
+    const bool active = thread_coords(q, ri, c4);
+    BnRaw raw{};
+    f32x4 gate = {0.f, 0.f, 0.f, 0.f};
+    if (active) {          // in flight together with the scale's slots
+        raw = bn_issue(bn, blockIdx.z, q.C4, c4);
+        gate = reinterpret_cast<const f32x4*>(s)[(long)blockIdx.z * q.C4 + c4];
+    }
     uint32_t mb = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) mb = max(mb, amax_in[(threadIdx.x & 63) + 64 * i]);
@@ -182,26 +206,38 @@ __global__ __launch_bounds__(NT) void se_scale_bn_planes_kernel(RedGeom q, const
     float ps, pinv;
     ud_h2_scale(mb, ps, pinv);
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *inv_scale = pinv;
-    int ri, c4;
-    if (!thread_coords(q, ri, c4)) return;
-    const In4<float> x4{x};
-    const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, false);
-    f32x4 gate = reinterpret_cast<const f32x4*>(s)[(long)blockIdx.z * q.C4 + c4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]) * ps;
-    Rows w = rows_of(q, ri, c4);
+    if (!active) return;
+    const In4<float> in[1] = {In4<float>{x}};
+    Bn4 cb;
+    const Rows w = rows_of(q, ri, c4);
     uint16_t* o = planes + (long)(c4 >> 3) * panel + (c4 & 7) * 4;
-    long row = (long)blockIdx.z * q.R + w.r;
-#pragma unroll 4
-    for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step, row += q.rpi) {
-        const f32x4 v = bn_apply(x4[w.idx], cb, bn.act) * gate;
-        uint16_t h0[4], h1[4];
+    const long row0 = (long)blockIdx.z * q.R;
+    auto fin = [&]() UD_LAMBDA_INLINE {
+        cb = bn_finish(bn, raw);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) ud_split_h2(v[e], h0[e], h1[e]);
-        typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-        *reinterpret_cast<u16x4*>(o + row * 32) = u16x4{h0[0], h0[1], h0[2], h0[3]};
-        *reinterpret_cast<u16x4*>(o + row * 32 + plane) = u16x4{h1[0], h1[1], h1[2], h1[3]};
-    }
+        for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]) * ps;
+    };
+    act_switch(bn.act, [&](auto ac) UD_LAMBDA_INLINE {
+        constexpr int ACT = decltype(ac)::value;
+        for_rows<float, 1>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long, int r, const f32x4(&t)[1]) UD_LAMBDA_INLINE {
+            // The split's residual of the quad's last two channels is taken of the EXACT product (one fma), that of the first two of
+            // the rounded one: the planes the one-row loop wrote, bit for bit, stated here instead of left to the contraction pass.
+            const f32x4 a = bn_apply<ACT>(t[0], cb);
+            const long row = row0 + r;
+            uint16_t h0[4], h1[4];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) ud_split_h2(mul_rn(a[e], gate[e]), h0[e], h1[e]);
+#pragma unroll
+            for (int e = 2; e < 4; ++e) {
+                const _Float16 top = (_Float16)mul_rn(a[e], gate[e]);
+                h0[e] = __builtin_bit_cast(uint16_t, top);
+                h1[e] = __builtin_bit_cast(uint16_t, (_Float16)mul_rn(__builtin_fmaf(a[e], gate[e], -(float)top), 2048.f));
+            }
+            typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+            *reinterpret_cast<u16x4*>(o + row * 32) = u16x4{h0[0], h0[1], h0[2], h0[3]};
+            *reinterpret_cast<u16x4*>(o + row * 32 + plane) = u16x4{h1[0], h1[1], h1[2], h1[3]};
+        });
+    });
 }
 
 // half storage (the mixed-precision mode): the gated tensor laid straight into the ONE fp16 plane ud_gemm_p3 prec 1 reads
@@ -213,21 +249,28 @@ __global__ __launch_bounds__(NT) void se_scale_bn_plane_half_kernel(RedGeom q, c
     int ri, c4;
     if (!thread_coords(q, ri, c4)) return;
     typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-    const In4<_Float16> x4{x};
-    const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, false);
+    const In4<_Float16> in[1] = {In4<_Float16>{x}};
+    const BnRaw raw = bn_issue(bn, blockIdx.z, q.C4, c4);
     f32x4 gate = reinterpret_cast<const f32x4*>(s)[(long)blockIdx.z * q.C4 + c4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]);
-    Rows w = rows_of(q, ri, c4);
+    Bn4 cb;
+    const Rows w = rows_of(q, ri, c4);
     uint16_t* o = plane + (long)(c4 >> 3) * panel + (c4 & 7) * 4;
     const int npad = (c4 == q.C4 - 1) ? 7 - (c4 & 7) : 0;
-    long row = (long)blockIdx.z * q.R + w.r;
-#pragma unroll 4
-    for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step, row += q.rpi) {
-        const f32x4 v = bn_apply(x4[w.idx], cb, bn.act) * gate;
-        Quad<_Float16>::st(reinterpret_cast<_Float16*>(o + row * 32), 0, v);
-        for (int z = 1; z <= npad; ++z) *reinterpret_cast<u16x4*>(o + row * 32 + 4 * z) = u16x4{0, 0, 0, 0};
-    }
+    const long row0 = (long)blockIdx.z * q.R;
+    auto fin = [&]() UD_LAMBDA_INLINE {
+        cb = bn_finish(bn, raw);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]);
+    };
+    act_switch(bn.act, [&](auto ac) UD_LAMBDA_INLINE {
+        constexpr int ACT = decltype(ac)::value;
+        for_rows<_Float16, 1>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long, int r, const f32x4(&t)[1]) UD_LAMBDA_INLINE {
+            const f32x4 v = bn_apply<ACT>(t[0], cb) * gate;
+            const long row = row0 + r;
+            Quad<_Float16>::st(reinterpret_cast<_Float16*>(o + row * 32), 0, v);
+            for (int z = 1; z <= npad; ++z) *reinterpret_cast<u16x4*>(o + row * 32 + 4 * z) = u16x4{0, 0, 0, 0};
+        });
+    });
 }
 
 // PL (round 6): ALSO written as the fp16 x 2 planes of the NEXT block's expand conv (ud_gemm_p3 prec 2, P32 layout over [G R] x C)
@@ -246,6 +289,14 @@ __global__ __launch_bounds__(NT) void residual_bn_kernel(RedGeom q, const T* __r
                                                          const float* __restrict__ keep, float inv_keep,
                                                          const T* __restrict__ skip, T* __restrict__ out,
                                                          uint32_t* __restrict__ amax, ResPlanes rp) {
+    int ri, c4;
+    const bool active = thread_coords(q, ri, c4);
+    BnRaw raw{};
+    float kraw = 0.f;
+    if (active) {          // in flight through the scale's scan below
+        raw = bn_issue(bn, blockIdx.z, q.C4, c4);
+        if (keep) kraw = keep[blockIdx.z];
+    }
     float ps = 1.f;
     if constexpr (PL == 1) {
         __shared__ float pl_red[NT / 64];
@@ -275,25 +326,29 @@ __global__ __launch_bounds__(NT) void residual_bn_kernel(RedGeom q, const T* __r
         ud_h2_scale(__float_as_uint((gm + sk) * 1.001f), ps, pinv);
         if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *rp.inv_scale = pinv;
     }
-    int ri, c4;
     float m = 0.f;
-    if (thread_coords(q, ri, c4)) {
-        const In4<T> x4{x}, k4{skip};
+    if (active) {
         const Out4<T> o4{out};
-        const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, is_updater(ri));
-        const float sc = keep ? keep[blockIdx.z] * inv_keep : 1.f;
-        Rows w = rows_of(q, ri, c4);
+        Bn4 cb;
+        float sc = 1.f;
+        const Rows w = rows_of(q, ri, c4);
         uint16_t* po = PL ? rp.buf + (long)(c4 >> 3) * rp.panel + (c4 & 7) * 4 : nullptr;
         const int npad = (PL && c4 == q.C4 - 1) ? 7 - (c4 & 7) : 0;
-        long prow = (long)blockIdx.z * q.R + w.r;
-#pragma unroll kRowUnroll<T>
-        for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step, prow += q.rpi) {
-            f32x4 v = bn_apply(x4[w.idx], cb, bn.act) * sc;
-            if (skip) v += k4[w.idx];
-            o4.st(w.idx, v);
+        const long prow0 = (long)blockIdx.z * q.R;
+        auto fin = [&]() UD_LAMBDA_INLINE {
+            cb = bn_finish(bn, raw);
+            if (keep) sc = kraw * inv_keep;
+        };
+        // t: the BatchNorm's input; v: the block output
+        auto row = [&](auto ac, const f32x4& t, const f32x4* k, long idx, int r) UD_LAMBDA_INLINE {
+            constexpr int ACT = decltype(ac)::value;
+            f32x4 v = mul_rn(bn_apply<ACT>(t, cb), sc);
+            if (k) v += *k;
+            o4.st(idx, v);
             m = fmaxf(m, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
             if constexpr (PL == 1) {
                 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+                const long prow = prow0 + r;
                 uint16_t h0[4], h1[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) ud_split_h2(v[e] * ps, h0[e], h1[e]);
@@ -304,7 +359,21 @@ __global__ __launch_bounds__(NT) void residual_bn_kernel(RedGeom q, const T* __r
                     *reinterpret_cast<u16x4*>(po + prow * 32 + 4 * z + rp.plane) = u16x4{0, 0, 0, 0};
                 }
             }
-        }
+        };
+        act_switch(bn.act, [&](auto ac) UD_LAMBDA_INLINE {
+            if (skip) {
+                const In4<T> in[2] = {In4<T>{x}, In4<T>{skip}};
+                for_rows<T, 2>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long idx, int r, const f32x4(&t)[2]) UD_LAMBDA_INLINE {
+                    row(ac, t[0], &t[1], idx, r);
+                });
+            } else {
+                const In4<T> in[1] = {In4<T>{x}};
+                for_rows<T, 1>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long idx, int r, const f32x4(&t)[1]) UD_LAMBDA_INLINE {
+                    row(ac, t[0], nullptr, idx, r);
+                });
+            }
+        });
+        if (is_updater(ri)) bn_update_running(bn, blockIdx.z, q.C4, c4);
     }
     ud_absmax_commit(m, amax);
 }
@@ -316,29 +385,43 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(RedGeom q, const T* __rest
                                                       T* __restrict__ y) {
     int ri, c4;
     if (!thread_coords(q, ri, c4)) return;
-    const In4<T> x4{x};
+    const In4<T> in[1] = {In4<T>{x}};
     const Out4<T> y4{y};
-    const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, is_updater(ri));
-    Rows w = rows_of(q, ri, c4);
-#pragma unroll kRowUnroll<T>
-    for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) y4.st(w.idx, bn_apply(x4[w.idx], cb, bn.act));
+    const BnRaw raw = bn_issue(bn, blockIdx.z, q.C4, c4);
+    Bn4 cb;
+    const Rows w = rows_of(q, ri, c4);
+    auto fin = [&]() UD_LAMBDA_INLINE { cb = bn_finish(bn, raw); };
+    act_switch(bn.act, [&](auto ac) UD_LAMBDA_INLINE {
+        constexpr int ACT = decltype(ac)::value;
+        for_rows<T, 1>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin,
+                       [&](long idx, int, const f32x4(&t)[1]) UD_LAMBDA_INLINE { y4.st(idx, bn_apply<ACT>(t[0], cb)); });
+    });
+    if (is_updater(ri)) bn_update_running(bn, blockIdx.z, q.C4, c4);
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // BatchNorm backward
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void dz_terms(const f32x4& a, const f32x4& d, const Bn4& cb, int act, bool is_dz, float sc,
-                                         f32x4& dz, f32x4& xh) {
+// MODE: kDz = the incoming gradient IS dz; 0 / 1 / 2 = it is dy of act(bn(x)) (times the drop-connect factor sc)
+constexpr int kDz = -1;
+template <int MODE>
+__device__ __forceinline__ void dz_terms(const f32x4& a, const f32x4& d, const Bn4& cb, float sc, f32x4& dz, f32x4& xh) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         xh[e] = (a[e] - cb.mu[e]) * cb.is[e];
         float g = d[e];
-        if (!is_dz) {
-            g *= sc;
-            if (act) g *= ud_act_grad_fast(cb.ga[e] * xh[e] + cb.be[e], act);
+        if (MODE != kDz) {          // (products rounded on their own: dz is what normbwd_sums summed)
+            g = mul_rn(g, sc);
+            if (MODE) g = mul_rn(g, ud_act_grad_fast(cb.ga[e] * xh[e] + cb.be[e], MODE));
         }
         dz[e] = g;
     }
+}
+// f(ActC<MODE>{}) of dz_terms for the run-time pair (dy_is_dz, act): as act_switch
+template <typename F>
+__device__ __forceinline__ void dz_switch(int dy_is_dz, int act, F&& f) {
+    if (dy_is_dz) f(ActC<kDz>{});
+    else act_switch(act, f);
 }
 
 template <typename T>
@@ -353,20 +436,29 @@ __global__ __launch_bounds__(NT) void normbwd_sums_kernel(RedGeom q, const T* __
     double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     f32x4 en = {0.f, 0.f, 0.f, 0.f};          // s3 != NULL: sum dz^2 (the energy bound of ud_normbwd_apply_planes' scale)
     if (active) {
-        const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, false);
-        const float sc = keep ? keep[blockIdx.z] * inv_keep : 1.f;
-        Rows w = rows_of(q, ri, c4);
-#pragma unroll kRowUnroll<T>
-        for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) {
-            f32x4 dz, xh;
-            dz_terms(x4[w.idx], d4[w.idx], cb, bn.act, dy_is_dz != 0, sc, dz, xh);
+        const BnRaw raw = bn_issue(bn, blockIdx.z, q.C4, c4);
+        const float kraw = keep ? keep[blockIdx.z] : 0.f;
+        Bn4 cb;
+        float sc = 1.f;
+        const Rows w = rows_of(q, ri, c4);
+        const In4<T> in[2] = {x4, d4};
+        auto fin = [&]() UD_LAMBDA_INLINE {
+            cb = bn_finish(bn, raw);
+            if (keep) sc = kraw * inv_keep;
+        };
+        dz_switch(dy_is_dz, bn.act, [&](auto mc) UD_LAMBDA_INLINE {
+            constexpr int MODE = decltype(mc)::value;
+            for_rows<T, 2>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long, int, const f32x4(&t)[2]) UD_LAMBDA_INLINE {
+                f32x4 dz, xh;
+                dz_terms<MODE>(t[0], t[1], cb, sc, dz, xh);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] += (double)dz[e];
-                v[4 + e] += (double)dz[e] * (double)xh[e];
-            }
-            en += dz * dz;
-        }
+                for (int e = 0; e < 4; ++e) {
+                    v[e] += (double)dz[e];
+                    v[4 + e] += (double)dz[e] * (double)xh[e];
+                }
+                en += dz * dz;
+            });
+        });
     }
     if (s3) {          // (uniform) rounded UP a little: the fp32 partial sums must never under-estimate
         double ev[8] = {(double)en[0] * 1.0001, (double)en[1] * 1.0001, (double)en[2] * 1.0001, (double)en[3] * 1.0001, 0, 0, 0, 0};
@@ -406,6 +498,19 @@ __global__ __launch_bounds__(NT) void normbwd_apply_kernel(RedGeom q, const T* _
                                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                            uint32_t* __restrict__ amax, double* __restrict__ energy,
                                                            PlanesDst pd) {
+    int ri, c4;
+    const bool active = thread_coords(q, ri, c4);
+    BnRaw raw{};
+    double t1d[4] = {0, 0, 0, 0}, t2d[4] = {0, 0, 0, 0};
+    float kraw = 0.f;
+    if (active) {          // in flight through the scale's scan below
+        raw = bn_issue(bn, blockIdx.z, q.C4, c4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t1d[e] = s1[c4 * 4 + e];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t2d[e] = s2[c4 * 4 + e];
+        if (keep) kraw = keep[blockIdx.z];
+    }
     float ps = 1.f;
     if constexpr (PL == 2) {
         if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *pd.inv_scale = 1.f;
@@ -430,48 +535,45 @@ __global__ __launch_bounds__(NT) void normbwd_apply_kernel(RedGeom q, const T* _
         ud_h2_scale(__float_as_uint(sqrtf(gm) * 1.002f), ps, pinv);          // (the 0.2 %: rsqrtf / fp32 rounding of the apply)
         if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *pd.inv_scale = pinv;
     }
-    int ri, c4;
-    const bool active = thread_coords(q, ri, c4);
     const In4<T> x4{x}, d4{dy}, fr4{freq};
     const Out4<T> o4{dx};
     double acc = 0.0;
     float mo = 0.f;
     f32x4 en = {0.f, 0.f, 0.f, 0.f};          // MIX, energy != NULL: sum of dx^2 per channel over this thread's rows
     if (active) {
-        const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, false);
-        const float sc = keep ? keep[blockIdx.z] * inv_keep : 1.f;
-        f32x4 t1, t2;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            t1[e] = (float)s1[c4 * 4 + e] * (float)bn.inv_count;
-            t2[e] = (float)s2[c4 * 4 + e] * (float)bn.inv_count;
-        }
-        if (is_updater(ri)) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (dbeta) dbeta[c4 * 4 + e] = (float)s1l[c4 * 4 + e];
-                if (dgamma) dgamma[c4 * 4 + e] = (float)s2l[c4 * 4 + e];
-            }
-        }
-        Rows w = rows_of(q, ri, c4);
+        Bn4 cb;
+        float sc = 1.f;
+        f32x4 t1, t2, k;
+        const Rows w = rows_of(q, ri, c4);
         // PL: this thread's quad of the panel; the thread of the LAST quad also zeroes the panel's pad quads
         uint16_t* po = PL ? pd.buf + (long)(c4 >> 3) * pd.panel + (c4 & 7) * 4 : nullptr;
         const int npad = (PL && c4 == q.C4 - 1) ? 7 - (c4 & 7) : 0;
-        long prow = (long)blockIdx.z * q.R + w.r;
-#pragma unroll kRowUnroll<T>
-        for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step, prow += q.rpi) {
-            f32x4 dz, xh, o;
-            dz_terms(x4[w.idx], d4[w.idx], cb, bn.act, dy_is_dz != 0, sc, dz, xh);
+        const long prow0 = (long)blockIdx.z * q.R;
+        auto fin = [&]() UD_LAMBDA_INLINE {
+            cb = bn_finish(bn, raw);
+            if (keep) sc = kraw * inv_keep;
+            k = cb.ga * cb.is;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = cb.ga[e] * cb.is[e] * (dz[e] - t1[e] - xh[e] * t2[e]);
+            for (int e = 0; e < 4; ++e) {
+                t1[e] = (float)t1d[e] * (float)bn.inv_count;
+                t2[e] = (float)t2d[e] * (float)bn.inv_count;
+            }
+        };
+        // a: x, d: the incoming gradient, f: freq - spat (MIX; ud_irfft2_mix)
+        auto row = [&](auto mc, const f32x4& a, const f32x4& d, const f32x4* f, long idx, int r) UD_LAMBDA_INLINE {
+            constexpr int MODE = decltype(mc)::value;
+            f32x4 dz, xh, o;
+            dz_terms<MODE>(a, d, cb, sc, dz, xh);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = k[e] * __builtin_fmaf(-xh[e], t2[e], dz[e] - t1[e]);          // (the rounding stated)
             if constexpr (PL == 2) {
                 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+                const long prow = prow0 + r;
                 Quad<T>::st(reinterpret_cast<T*>(po + prow * 32), 0, o);
                 for (int z = 1; z <= npad; ++z) *reinterpret_cast<u16x4*>(po + prow * 32 + 4 * z) = u16x4{0, 0, 0, 0};
-                continue;
-            }
-            if constexpr (PL == 1) {
+            } else if constexpr (PL == 1) {
                 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+                const long prow = prow0 + r;
                 uint16_t h0[4], h1[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) ud_split_h2(o[e] * ps, h0[e], h1[e]);
@@ -481,15 +583,34 @@ __global__ __launch_bounds__(NT) void normbwd_apply_kernel(RedGeom q, const T* _
                     *reinterpret_cast<u16x4*>(po + prow * 32 + 4 * z) = u16x4{0, 0, 0, 0};
                     *reinterpret_cast<u16x4*>(po + prow * 32 + 4 * z + pd.plane) = u16x4{0, 0, 0, 0};
                 }
-                continue;
-            }
-            o4.st(w.idx, o);
-            mo = fmaxf(mo, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
-            if (MIX) {
-                f32x4 f = fr4[w.idx];                    // freq - spat (ud_irfft2_mix)
+            } else {
+                o4.st(idx, o);
+                mo = fmaxf(mo, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
+                if constexpr (MIX) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc += (double)ud_rounded<T>(o[e]) * (double)f[e];
-                en += o * o;
+                    for (int e = 0; e < 4; ++e) acc += (double)ud_rounded<T>(o[e]) * (double)(*f)[e];
+                    en += o * o;
+                }
+            }
+        };
+        dz_switch(dy_is_dz, bn.act, [&](auto mc) UD_LAMBDA_INLINE {
+            if constexpr (MIX) {
+                const In4<T> in[3] = {x4, d4, fr4};
+                for_rows<T, 3>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long idx, int r, const f32x4(&t)[3]) UD_LAMBDA_INLINE {
+                    row(mc, t[0], t[1], &t[2], idx, r);
+                });
+            } else {
+                const In4<T> in[2] = {x4, d4};
+                for_rows<T, 2>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long idx, int r, const f32x4(&t)[2]) UD_LAMBDA_INLINE {
+                    row(mc, t[0], t[1], nullptr, idx, r);
+                });
+            }
+        });
+        if (is_updater(ri)) {          // behind the row loop: one more trip for one thread per quad
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (dbeta) dbeta[c4 * 4 + e] = (float)s1l[c4 * 4 + e];
+                if (dgamma) dgamma[c4 * 4 + e] = (float)s2l[c4 * 4 + e];
             }
         }
     }
@@ -541,27 +662,35 @@ __global__ __launch_bounds__(NT) void se_scale_bwd_bn_kernel(RedGeom q, const T*
     const Out4<T> o4{dzo};
     double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (active) {
-        const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, false);
+        const BnRaw raw = bn_issue(bn, blockIdx.z, q.C4, c4);
         f32x4 gate = reinterpret_cast<const f32x4*>(s)[(long)blockIdx.z * q.C4 + c4];
-        f32x4 dp = reinterpret_cast<const f32x4*>(dpool)[(long)blockIdx.z * q.C4 + c4] * inv_hw;
+        f32x4 dp = reinterpret_cast<const f32x4*>(dpool)[(long)blockIdx.z * q.C4 + c4];
+        Bn4 cb;
+        const Rows w = rows_of(q, ri, c4);
+        const In4<T> in[2] = {x4, d4};
+        auto fin = [&]() UD_LAMBDA_INLINE {
+            cb = bn_finish(bn, raw);
+            dp = dp * inv_hw;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]);
-        Rows w = rows_of(q, ri, c4);
-#pragma unroll kRowUnroll<T>
-        for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) {
-            f32x4 a = x4[w.idx], d = d4[w.idx], dz;
+            for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]);
+        };
+        act_switch(bn.act, [&](auto ac) UD_LAMBDA_INLINE {
+            constexpr int ACT = decltype(ac)::value;
+            for_rows<T, 2>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long idx, int, const f32x4(&t)[2]) UD_LAMBDA_INLINE {
+                f32x4 dz;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float xh = (a[e] - cb.mu[e]) * cb.is[e];
-                float g = d[e] * gate[e] + dp[e];
-                if (bn.act) g *= ud_act_grad_fast(cb.ga[e] * xh + cb.be[e], bn.act);
-                g = ud_rounded<T>(g);                  // the sums are those of the stored gradient
-                dz[e] = g;
-                v[e] += (double)g;
-                v[4 + e] += (double)g * (double)xh;
-            }
-            o4.st(w.idx, dz);
-        }
+                for (int e = 0; e < 4; ++e) {
+                    const float xh = (t[0][e] - cb.mu[e]) * cb.is[e];
+                    float g = t[1][e] * gate[e] + dp[e];
+                    if (ACT) g *= ud_act_grad_fast(cb.ga[e] * xh + cb.be[e], ACT);
+                    g = ud_rounded<T>(g);                  // the sums are those of the stored gradient
+                    dz[e] = g;
+                    v[e] += (double)g;
+                    v[4 + e] += (double)g * (double)xh;
+                }
+                o4.st(idx, dz);
+            });
+        });
     }
     red_out<8>(q, ri, active, c4, v, s1, s2, part, false);
 }
@@ -569,7 +698,7 @@ __global__ __launch_bounds__(NT) void se_scale_bwd_bn_kernel(RedGeom q, const T*
 // ---------------------------------------------------------------------------------------------------------
 // Backward through an EVAL-FORM BatchNorm (the frozen half backward of tape.mbconv_frozen_half): mean and variance are
 // constants, so dx = gamma invstd dz per channel — no sums, no second pass, the constant folded into the pass that makes dz.
-// Streaming, element-wise: whole rows per workgroup (geom_ew), a channel quad per access, kRowUnroll<T> rows in flight.
+// Streaming, element-wise: whole rows per workgroup (geom_ew), a channel quad per access, kRowGroup rows in flight.
 // ---------------------------------------------------------------------------------------------------------
 // dd = (dc * sigmoid(s) + dpool * inv_hw) * act'(bn(x)) * gamma invstd.   Bytes per element: reads dc, x, writes dd: 3 sizeof(T)
 template <typename T>
@@ -581,25 +710,33 @@ __global__ __launch_bounds__(NT) void se_scale_bwd_bn_eval_kernel(RedGeom q, con
     if (!thread_coords(q, ri, c4)) return;
     const In4<T> x4{x}, d4{dc};
     const Out4<T> o4{ddo};
-    const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, false);
+    const BnRaw raw = bn_issue(bn, blockIdx.z, q.C4, c4);
     f32x4 gate = reinterpret_cast<const f32x4*>(s)[(long)blockIdx.z * q.C4 + c4];
-    const f32x4 dp = reinterpret_cast<const f32x4*>(dpool)[(long)blockIdx.z * q.C4 + c4] * inv_hw;
-    const f32x4 k = cb.ga * cb.is;
+    f32x4 dp = reinterpret_cast<const f32x4*>(dpool)[(long)blockIdx.z * q.C4 + c4];
+    Bn4 cb;
+    f32x4 k;
+    const Rows w = rows_of(q, ri, c4);
+    const In4<T> in[2] = {x4, d4};
+    auto fin = [&]() UD_LAMBDA_INLINE {
+        cb = bn_finish(bn, raw);
+        dp = dp * inv_hw;
+        k = cb.ga * cb.is;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]);
-    Rows w = rows_of(q, ri, c4);
-#pragma unroll kRowUnroll<T>
-    for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) {
-        const f32x4 a = x4[w.idx], d = d4[w.idx];
-        f32x4 o;
+        for (int e = 0; e < 4; ++e) gate[e] = ud_sigmoid_fast(gate[e]);
+    };
+    act_switch(bn.act, [&](auto ac) UD_LAMBDA_INLINE {
+        constexpr int ACT = decltype(ac)::value;
+        for_rows<T, 2>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long idx, int, const f32x4(&t)[2]) UD_LAMBDA_INLINE {
+            f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float g = d[e] * gate[e] + dp[e];
-            if (bn.act) g *= ud_act_grad_fast(cb.ga[e] * ((a[e] - cb.mu[e]) * cb.is[e]) + cb.be[e], bn.act);
-            o[e] = g * k[e];
-        }
-        o4.st(w.idx, o);
-    }
+            for (int e = 0; e < 4; ++e) {
+                float g = t[1][e] * gate[e] + dp[e];
+                if (ACT) g *= ud_act_grad_fast(cb.ga[e] * ((t[0][e] - cb.mu[e]) * cb.is[e]) + cb.be[e], ACT);
+                o[e] = g * k[e];
+            }
+            o4.st(idx, o);
+        });
+    });
 }
 
 // dx = dy * gamma invstd [* act'(bn(x)) when bn.act; x is not read otherwise].   Bytes per element: 2 sizeof(T) (3 with an activation)
@@ -610,21 +747,29 @@ __global__ __launch_bounds__(NT) void bn_eval_bwd_kernel(RedGeom q, const T* __r
     if (!thread_coords(q, ri, c4)) return;
     const In4<T> x4{x}, d4{dy};
     const Out4<T> o4{dx};
-    const Bn4 cb = bn_load(bn, blockIdx.z, q.C4, c4, false);
-    const f32x4 k = cb.ga * cb.is;
-    Rows w = rows_of(q, ri, c4);
-    if (bn.act) {
-#pragma unroll kRowUnroll<T>
-        for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) {
-            const f32x4 a = x4[w.idx];
-            f32x4 o = d4[w.idx] * k;
+    const BnRaw raw = bn_issue(bn, blockIdx.z, q.C4, c4);
+    Bn4 cb;
+    f32x4 k;
+    const Rows w = rows_of(q, ri, c4);
+    auto fin = [&]() UD_LAMBDA_INLINE {
+        cb = bn_finish(bn, raw);
+        k = cb.ga * cb.is;
+    };
+    if (bn.act) {          // (the entry point admits 0, 1, 2)
+        const In4<T> in[2] = {x4, d4};
+        act_switch(bn.act, [&](auto ac) UD_LAMBDA_INLINE {
+            constexpr int ACT = decltype(ac)::value;
+            for_rows<T, 2>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long idx, int, const f32x4(&t)[2]) UD_LAMBDA_INLINE {
+                f32x4 o = t[1] * k;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] *= ud_act_grad_fast(cb.ga[e] * ((a[e] - cb.mu[e]) * cb.is[e]) + cb.be[e], bn.act);
-            o4.st(w.idx, o);
-        }
+                for (int e = 0; e < 4; ++e) o[e] *= ud_act_grad_fast(cb.ga[e] * ((t[0][e] - cb.mu[e]) * cb.is[e]) + cb.be[e], ACT);
+                o4.st(idx, o);
+            });
+        });
     } else {
-#pragma unroll kRowUnroll<T>
-        for (; w.r < w.r_end; w.r += q.rpi, w.idx += w.step) o4.st(w.idx, d4[w.idx] * k);
+        const In4<T> in[1] = {d4};
+        for_rows<T, 1>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin,
+                       [&](long idx, int, const f32x4(&t)[1]) UD_LAMBDA_INLINE { o4.st(idx, t[0] * k); });
     }
 }
 
