@@ -343,9 +343,9 @@ def test_apgd_entry_points_reject_bad_arguments():
 
 
 def test_apgd_entry_points_are_declared_exported_and_bound():
-    from tests.test_abi_cpu import _declared
+    from tests.test_abi_cpu import header
     from unidefense_amd import lib
-    names = _declared()
+    names = header().protos
     handle = ctypes.CDLL(lib.LIB_PATH)
     for n in ("ud_apgd_control", "ud_apgd_update_linf", "ud_apgd_keep", "ud_apgd_step_l2", "ud_apgd_combine_l2",
               "ud_apgd_project_l2"):

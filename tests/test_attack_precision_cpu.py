@@ -10,9 +10,9 @@ FROZEN_ENTRIES = ("ud_coldot_bn_eval", "ud_coldot_bn_eval_ws_doubles", "ud_se_sc
 
 
 def test_frozen_entry_points_are_declared_exported_and_bound():
-    from tests.test_abi_cpu import _declared
+    from tests.test_abi_cpu import header
     from unidefense_amd import lib
-    names = _declared()
+    names = header().protos
     handle = ctypes.CDLL(lib.LIB_PATH)
     for n in FROZEN_ENTRIES:
         assert n in names, f"{n} is not declared in include/unidefense_hip.h"

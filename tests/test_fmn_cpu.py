@@ -427,10 +427,10 @@ def test_fmn_entry_points_reject_bad_arguments():
 
 
 def test_fmn_entry_points_are_declared_exported_and_bound():
-    from tests.test_abi_cpu import _declared
+    from tests.test_abi_cpu import header
     from unidefense_amd import kernels as K
     from unidefense_amd import lib
-    names = _declared()
+    names = header().protos
     handle = ctypes.CDLL(lib.LIB_PATH)
     for n in ("ud_fmn_norms_ws_bytes", "ud_fmn_norm_parts", "ud_fmn_control", "ud_fmn_update", "ud_fmn_project_l2"):
         assert n in names and n in lib.EXPORTED and hasattr(handle, n), n
@@ -440,10 +440,7 @@ def test_fmn_entry_points_are_declared_exported_and_bound():
     assert K.FMN_NORM == {"linf": 0, "l2": 1} and K.FMN_PARTS == {"gss": GSS, "gabs": GABS, "dss": DSS, "dmax": DMAX}
     assert K.FMN_CHUNK == CHUNK and K.fmn_norms_ws_bytes(3, 3 * 32 * 32) == 3 * 1 * 32
     # the header's constants are the binding's
-    import os
-    import re
-    src = open(os.path.join(os.path.dirname(lib.__file__), "..", "include", "unidefense_hip.h")).read()
-    const = {k: int(v) for k, v in re.findall(r"#define (UD_FMN_[A-Z0-9_]+) (\d+)", src)}
+    const = header().consts
     assert const["UD_FMN_CHUNK"] == CHUNK and const["UD_FMN_PARTS"] == 4
     assert {k: const[f"UD_FMN_I_{k.upper()}"] for k in K.FMN_I} == K.FMN_I
     assert {k: const[f"UD_FMN_F_{k.upper()}"] for k in K.FMN_F} == K.FMN_F

@@ -562,10 +562,10 @@ def test_sfmn_entry_points_reject_bad_arguments():
 
 
 def test_sfmn_entry_points_are_declared_exported_and_bound():
-    from tests.test_abi_cpu import _declared
+    from tests.test_abi_cpu import header
     from unidefense_amd import kernels as K
     from unidefense_amd import lib
-    names = _declared()
+    names = header().protos
     handle = ctypes.CDLL(lib.LIB_PATH)
     for n in ("ud_sfmn_norms_ws_bytes", "ud_sfmn_norm_parts", "ud_sfmn_control", "ud_sfmn_select", "ud_sfmn_apply"):
         assert n in names and n in lib.EXPORTED and hasattr(handle, n), n
@@ -576,10 +576,7 @@ def test_sfmn_entry_points_are_declared_exported_and_bound():
     assert K.SFMN_CHUNK == CHUNK == K.FMN_CHUNK and K.sfmn_norms_ws_bytes(3, 3 * 32 * 32) == 3 * 1 * 32
     assert K.FMN_NORM == {"linf": 0, "l2": 1}                               # the sparse norms are no new values of FMN's
     # the header's constants are the binding's
-    import os
-    import re
-    src = open(os.path.join(os.path.dirname(lib.__file__), "..", "include", "unidefense_hip.h")).read()
-    const = {k: int(v) for k, v in re.findall(r"#define (UD_SFMN_[A-Z0-9_]+) (\d+)", src)}
+    const = header().consts
     assert const["UD_SFMN_CHUNK"] == CHUNK and const["UD_SFMN_PARTS"] == 4 and const["UD_SFMN_L0_MAX_PER"] == K.SFMN_L0_MAX_PER == 2 ** 24
     assert {k: const[f"UD_SFMN_I_{k.upper()}"] for k in K.SFMN_I} == K.SFMN_I
     assert {k: const[f"UD_SFMN_F_{k.upper()}"] for k in K.SFMN_F} == K.SFMN_F

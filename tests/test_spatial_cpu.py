@@ -274,20 +274,19 @@ def test_host_side_refusals():
 
 
 def test_entry_points_are_declared_exported_and_refuse_bad_arguments():
-    import os
-    import re
-    from tests.test_abi_cpu import _declared
+    from tests.test_abi_cpu import header
     from unidefense_amd import kernels as K
     from unidefense_amd import lib
-    names = _declared()
+    names = header().protos
     L = ctypes.CDLL(lib.LIB_PATH)
     for n in ("ud_warp_affine", "ud_spatial_control"):
         assert n in names and n in lib.EXPORTED and hasattr(L, n), n
         getattr(L, n).restype = ctypes.c_int
     for n in ("spatial_state", "warp_affine", "spatial_control"):
         assert callable(getattr(K, n)), n
-    src = open(os.path.join(os.path.dirname(lib.__file__), "..", "include", "unidefense_hip.h")).read()
-    const = {k: int(v) for k, v in re.findall(r"#define (UD_(?:WARP|SPATIAL)_[A-Z0-9_]+) (\d+)", src)}
+    const = header().consts
+    assert K.WARP_BORDER == {"reflect": 0, "edge": 1, "fill": 2}
+    assert K.SPATIAL_I == {"k": 0, "best_k": 1, "row": 2} and K.SPATIAL_F == {"f_best": 0}
     assert {k: const[f"UD_WARP_{k.upper()}"] for k in K.WARP_BORDER} == K.WARP_BORDER and tuple(K.WARP_BORDER) == SP.BORDERS
     assert {k: const[f"UD_SPATIAL_I_{k.upper()}"] for k in K.SPATIAL_I} == K.SPATIAL_I
     assert K.SPATIAL_F == {"f_best": const["UD_SPATIAL_F_BEST"]}

@@ -5,7 +5,6 @@ per-sample state machine), ref_square_propose (torch in the dtype of its inputs,
 whole attack on any per-sample objective)."""
 import ctypes
 import math
-import os
 
 import pytest
 import torch
@@ -300,18 +299,19 @@ def test_square_entry_points_reject_bad_arguments():
 
 
 def test_square_entry_points_are_declared_exported_and_bound():
-    from tests.test_abi_cpu import _declared
+    from tests.test_abi_cpu import header
     from unidefense_amd import kernels as K, lib
-    names = _declared()
+    names = sorted(header().protos)
     handle = ctypes.CDLL(lib.LIB_PATH)
     for n in ("ud_square_propose", "ud_square_control"):
         assert n in names and n in lib.EXPORTED and hasattr(handle, n), n
     assert sorted(lib.EXPORTED) == names
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "unidefense_hip.h")).read()
+    assert K.SQUARE_I == {"k": 0, "accepted": 1, "active": 2, "queries": 3} and K.SQUARE_F == {"f_best": 0}
+    const = header().consts
     for name, row in list(K.SQUARE_I.items()) + list(K.SQUARE_F.items()):      # the name maps are the header's rows
         pre = "UD_SQUARE_I_" if name in K.SQUARE_I else "UD_SQUARE_F_"
         short = name.upper().replace("F_BEST", "BEST")
-        assert f"#define {pre}{short} {row}\n" in src, (name, row)
+        assert const[f"{pre}{short}"] == row, (name, row)
 
 
 # ---- the runner: refusals that need no GPU -----------------------------------------------------------------------------------

@@ -17,6 +17,7 @@ from .devmem import Scratch, ZeroPool
 from .lib import ConvGeom, GemmDesc, GemmP3Desc
 
 _call = _lib.call
+_const, _rows = _lib.const, _lib.const_rows      # the header's #define UD_* values: one, or {lower-cased suffix: value} of a prefix
 
 # when set to a list, every ud_gemm launch is bracketed by HIP events: (start, end, flops) tuples
 GEMM_PROFILE = None
@@ -276,8 +277,8 @@ class _WeightPlaneBatch:
                 self.table = self.slots = None
                 return
             self._build()
-        _call("ud_split_planes_h2t_multi", _p(self.table), len(self.entries), _p(self.slots), self.totals[0], self.totals[1],
-              _stream())
+        _call("ud_split_planes_h2t_multi", C.cast(_p(self.table), C.POINTER(_lib.SplitItem)), len(self.entries), _p(self.slots),
+              self.totals[0], self.totals[1], _stream())
         for e in self.entries.values():
             e[2] = e[0]()._version
         self.active = True
@@ -357,7 +358,8 @@ class _WeightLayoutBatch:
                 self.table = None
                 return
             self._build()
-        _call("ud_weight_layouts_multi", _p(self.table), len(self.entries), self.blocks, _stream())
+        _call("ud_weight_layouts_multi", C.cast(_p(self.table), C.POINTER(_lib.LayoutItem)), len(self.entries), self.blocks,
+              _stream())
         for e in self.entries.values():
             e[2] = e[0]()._version
         self.active = True
@@ -1499,9 +1501,10 @@ def _state(N, device, I, F):
 
 
 # ---- Auto-PGD (csrc/apgd.hip) -------------------------------------------------------------------------------------------------
-APGD_MAX_CHECKPOINTS = 16
-APGD_I = {"k": 0, "cnt": 1, "halved": 2, "improved": 3, "reset": 4}
-APGD_F = {"f_prev": 0, "f_best": 1, "f_ckpt": 2, "eta": 3, "a": 4}
+APGD_MAX_CHECKPOINTS = _const("UD_APGD_MAX_CHECKPOINTS")
+APGD_I = _rows("UD_APGD_I_")
+APGD_F = {"f_prev": _const("UD_APGD_F_PREV"), "f_best": _const("UD_APGD_F_BEST"), "f_ckpt": _const("UD_APGD_F_CKPT"),
+          "eta": _const("UD_APGD_F_ETA"), "a": _const("UD_APGD_F_A")}
 
 
 def apgd_state(N, device):
@@ -1579,11 +1582,11 @@ def apgd_project_l2(x, x0, dss, fst, eps, lo, hi):
 
 
 # ---- Fast Minimum-Norm attack (csrc/fmn.hip) ------------------------------------------------------------------------------------
-FMN_I = {"k": 0, "found": 1, "improved": 2}
-FMN_F = {"eps": 0, "best": 1}
-FMN_NORM = {"linf": 0, "l2": 1}
-FMN_PARTS = {"gss": 0, "gabs": 1, "dss": 2, "dmax": 3}          # the doubles of one part (UD_FMN_P_*)
-FMN_CHUNK = 4096
+FMN_I = _rows("UD_FMN_I_")
+FMN_F = _rows("UD_FMN_F_")
+FMN_NORM = {"linf": _const("UD_FMN_LINF"), "l2": _const("UD_FMN_L2")}
+FMN_PARTS = _rows("UD_FMN_P_")            # the doubles of one part
+FMN_CHUNK = _const("UD_FMN_CHUNK")
 _FMN_WS = Scratch(torch.float64)          # norm parts: written by fmn_norm_parts, consumed by the fmn_control behind it
 _FMN_SS_WS = Scratch(torch.float64)       # the L2 projection's sample_sumsq partial sums, consumed by its own fold launch
 
@@ -1667,12 +1670,12 @@ def fmn_project_l2(x, x0, dss, fst, lo, hi):
 
 
 # ---- Sparse minimum-norm attack (csrc/sfmn.hip) -----------------------------------------------------------------------------------
-SFMN_I = {"k": 0, "found": 1, "improved": 2}
-SFMN_F = {"eps": 0, "best": 1}
-SFMN_NORM = {"l1": 0, "l0": 1}
-SFMN_PARTS = {"gss": 0, "gmax": 1, "dabs": 2, "dcnt": 3}        # the doubles of one part (UD_SFMN_P_*)
-SFMN_CHUNK = 4096
-SFMN_L0_MAX_PER = 1 << 24                 # an L0 count lives in an fp32 state row: exact below this
+SFMN_I = _rows("UD_SFMN_I_")
+SFMN_F = _rows("UD_SFMN_F_")
+SFMN_NORM = {"l1": _const("UD_SFMN_L1"), "l0": _const("UD_SFMN_L0")}
+SFMN_PARTS = _rows("UD_SFMN_P_")          # the doubles of one part
+SFMN_CHUNK = _const("UD_SFMN_CHUNK")
+SFMN_L0_MAX_PER = _const("UD_SFMN_L0_MAX_PER")      # an L0 count lives in an fp32 state row: exact below this (2^24)
 _SFMN_WS = Scratch(torch.float64)         # norm parts: written by sfmn_norm_parts, consumed by the sfmn_control behind it
 
 
@@ -1752,8 +1755,8 @@ def sfmn_apply(x, x_best, x0, g, ist, fac, thr, norm, lo, hi):
 
 
 # ---- Square attack (csrc/square.hip) ------------------------------------------------------------------------------------------
-SQUARE_I ={"k": 0, "accepted": 1, "active": 2, "queries": 3}
-SQUARE_F = {"f_best": 0}
+SQUARE_I = _rows("UD_SQUARE_I_")
+SQUARE_F = {"f_best": _const("UD_SQUARE_F_BEST")}
 
 
 def square_state(N, device):
@@ -1794,8 +1797,9 @@ def square_control(f, ist, fst, history, decisions, steps, early_stop=True):
 
 
 # ---- common image corruptions (csrc/corrupt.hip): x, out contiguous fp32 [N, 3, size, size], one launch each -------------------
-CORRUPT_JPEG = {"420": 0, "444": 1}
-CORRUPT_POINT = {"contrast": 0, "saturation": 1, "gaussian_noise": 2}
+CORRUPT_JPEG = {"420": _const("UD_CORRUPT_JPEG_420"), "444": _const("UD_CORRUPT_JPEG_444")}
+CORRUPT_POINT = {"contrast": _const("UD_CORRUPT_CONTRAST"), "saturation": _const("UD_CORRUPT_SATURATION"),
+                 "gaussian_noise": _const("UD_CORRUPT_NOISE")}
 
 
 def _chk_images(x, out, lut):
@@ -1854,9 +1858,9 @@ def corrupt_blocks(x, out, lut, pos):
 
 
 # ---- affine warps and the spatial search's state (csrc/warp.hip) ---------------------------------------------------------------
-WARP_BORDER = {"reflect": 0, "edge": 1, "fill": 2}
-SPATIAL_I = {"k": 0, "best_k": 1, "row": 2}
-SPATIAL_F = {"f_best": 0}
+WARP_BORDER = _rows("UD_WARP_")
+SPATIAL_I = _rows("UD_SPATIAL_I_")
+SPATIAL_F = {"f_best": _const("UD_SPATIAL_F_BEST")}
 
 
 def spatial_state(N, device):
