@@ -1,0 +1,208 @@
+"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial: one scoring forward, one batch
+source, one loop-and-gather, one metrics dictionary, and a table of test_robust's methods.  The Evaluator takes its model and
+iterator as arguments and imports nothing that loads the HIP library, so the stage rules run on the CPU against stubs
+(tests/test_evaluate_cpu.py).  What every stage keeps: its order inside a batch, who owns which generator, the sequence of
+gather_scores calls (each is a pair of collectives under data parallel), every refusal before the first launch, and no
+host-device synchronisation inside the batch loop — .cpu() / float() / bool() happen after it."""
+from functools import partial
+
+import torch
+
+from . import metrics
+
+
+class Evaluator:
+    """model: what model(x) calls (wrapped under data parallel); net: the un-wrapped model, owner of the runner accessors;
+    iterator(step, batch, size, device) -> (x_real, y_real, x_fake, y_fake); inference_graph / inference_precision: the
+    engine's two config keys; local_rank: rank 0 prints."""
+
+    def __init__(self, model, net, iterator, batch, size, device, inference_graph=False, inference_precision="fp32", local_rank=0):
+        self.model, self.net, self.iterator, self.batch, self.size, self.device = model, net, iterator, batch, size, device
+        self.graphed, self.precision, self.local_rank = bool(inference_graph), inference_precision, local_rank
+
+    @torch.no_grad()
+    def score(self, x):
+        """p(real) = softmax(cls_out)[:, 0] (forgery_engine.py:349,437)"""
+        # one hipGraph replay per batch, or the model's inference forward: no tape, running statistics
+        forward = self.net.inference_runner(x.shape[0], x.shape[-1], self.precision) if self.graphed else self.model
+        return torch.softmax(forward(x)["cls_out"], 1)[:, 0]
+
+    def batches(self, n):
+        for step in range(1, n + 1):
+            xr, yr, xf, yf = self.iterator(step, self.batch, self.size, self.device)
+            yield torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
+
+    def run(self, n, body):
+        """body(x, y) -> {name: per-sample tensor} for each of n batches -> {name: (all batches of all ranks, their labels)}.
+        One gather_scores per name, in the order body names them (engine/metrics.py: two device all_gathers each)."""
+        cols, labels = {}, []
+        for x, y in self.batches(n):
+            for name, t in body(x, y).items():
+                cols.setdefault(name, []).append(t)
+            labels.append(y)
+        labels = torch.cat(labels)
+        return {name: metrics.gather_scores(torch.cat(parts), labels) for name, parts in cols.items()}
+
+    def metrics(self, scores, labels, tag):
+        """what test() returns for gathered (scores, labels), its line printed as `tag`"""
+        sc, lb = scores.float().cpu().numpy(), labels.cpu().numpy()
+        ret = {"scores": scores.cpu(), "labels": labels.cpu(), "acc": float(((sc < 0.5).astype(int) == lb).mean())}
+        if len(set(lb.tolist())) == 2:                     # a ROC needs both classes
+            ret.update(metrics.cal_metrics(lb, sc, threshold=0.5))
+            if self.local_rank == 0:
+                print("%s | EER %.4f, HTER %.4f, TPR 5%% %.4f, AUC %.4f, ACC %.4f" % (
+                    tag, ret["EER"], ret["ACER"], ret["TPR5%"], ret["AUC"], ret["ACC"]))
+        return ret
+
+    def _result(self, cols, tag, args):
+        return {"clean": self.metrics(*cols["clean"], "Test"), "adv": self.metrics(*cols["adv"], tag), "attack": args}
+
+    def test(self, batches):
+        return self.metrics(*self.run(batches, lambda x, y: {"scores": self.score(x)})["scores"], "Test")
+
+    def test_robust(self, batches, attack):
+        if not attack:
+            raise ValueError("test_robust needs an attack: pass attack={...} or set config['config']['attack']")
+        attack = dict(attack)
+        method = attack.pop("method", "pgd")
+        if method not in ROBUST:
+            names = [repr(name) for name in ROBUST]
+            raise ValueError(f"attack method must be {', '.join(names[:-1])} or {names[-1]}, got {method!r}")
+        run = ROBUST[method](self, attack)                       # refuses what it does before any batch is drawn
+        cols = self.run(batches, run.body)
+        return self._result(cols, "Test(adv)", run.attack(cols))
+
+    def test_corrupted(self, batches, kinds, levels, seed, subsampling, corrupt=None, resolve=None):
+        """corrupt / resolve: corrupt.corrupt / corrupt.resolve unless a caller (a CPU test) brings host stand-ins"""
+        from .. import corrupt as CR
+        corrupt, resolve = corrupt or CR.corrupt, resolve or CR.resolve
+        kinds, levels = list(kinds) if kinds else list(CR.CORRUPTIONS), tuple(levels)
+        resolved = {k: {lv: resolve(k, lv)[0][1] for lv in levels} for k in kinds}        # refuses before any kernel runs
+        if subsampling not in CR.SUBSAMPLINGS:
+            raise ValueError(f"subsampling must be one of {CR.SUBSAMPLINGS}, got {subsampling!r}")
+        # one device generator per call, consumed batch-major, then in (kind, level) insertion order; one x_cor buffer for all
+        generator = None if seed is None else torch.Generator(device=self.device).manual_seed(int(seed))
+        keys, x_cor = dict.fromkeys((k, lv) for k in kinds for lv in levels), None
+
+        def body(x, y):
+            nonlocal x_cor
+            clean = self.score(x)
+            x_cor = torch.empty_like(x) if x_cor is None or x_cor.shape != x.shape else x_cor
+            return {"clean": clean, **{(k, lv): self.score(corrupt(x, k, lv, generator=generator, subsampling=subsampling, out=x_cor))
+                                       for k, lv in keys}}
+
+        cols = self.run(batches, body)
+        ret = {"clean": self.metrics(*cols["clean"], "Test"), "corrupted": {}, "mean": {}, "corruptions": resolved}
+        for k in kinds:
+            ret["corrupted"][k] = {lv: self.metrics(*cols[(k, lv)], "Test(%s %d)" % (k, lv)) for lv in levels}
+            both = [r for r in ret["corrupted"][k].values() if "AUC" in r]
+            if both:
+                ret["mean"][k] = {m: float(sum(r[m] for r in both) / len(both)) for m in ("AUC", "ACC")}
+                if self.local_rank == 0:
+                    print("Corrupted %-14s | mean AUC %.4f, mean ACC %.4f | AUC by level %s" % (
+                        k, ret["mean"][k]["AUC"], ret["mean"][k]["ACC"],
+                        " ".join("%d:%.4f" % (lv, ret["corrupted"][k][lv]["AUC"]) for lv in levels if "AUC" in ret["corrupted"][k][lv])))
+        return ret
+
+    def test_spatial(self, batches, spatial):
+        spatial = dict(spatial) if spatial else {}
+        seed = spatial.pop("seed", None)
+        generator = None if seed is None else torch.Generator().manual_seed(int(seed))     # one CPU generator per call
+        runner = None
+
+        def body(x, y):
+            nonlocal runner
+            try:                                         # the runner first, then the clean score; only the accessor is wrapped
+                runner = self.net.spatial_runner(x.shape[0], x.shape[-1], **spatial)
+            except TypeError as e:                       # an unknown key is a bad dict, like a bad value
+                raise ValueError(f"spatial takes SpatialRunner's keyword arguments and 'seed': {e}") from None
+            clean = self.score(x)
+            adv = self.score(runner(x, y, generator))
+            best = runner.best.to(self.device)           # gathered in this order: best's five columns, the two losses, the scores
+            return {**{i: best[:, i] for i in range(5)}, "best_loss": runner.best_loss.clone(), "loss0": runner.loss0.clone(),
+                    "clean": clean, "adv": adv}
+
+        cols = self.run(batches, body)
+        held = cols["loss0"][0] > 0
+        args = dict(runner.args, best=torch.stack([cols[i][0] for i in range(5)], 1).cpu(),
+                    fooled=float((cols["best_loss"][0][held] <= 0).double().mean()) if bool(held.any()) else float("nan"))
+        return self._result(cols, "Test(spatial)", args)
+
+
+# ---- test_robust's methods: ROBUST[method](ev, attack) refuses and resolves the dict (given without "method") and is the run:
+# body(x, y) -> the batch's columns, attack(cols) -> the result's "attack" entry ------------------------------------------------
+class _Attack:
+    """One runner per batch from the model's `accessor`.  draws: where the generator seeded by the dict's "seed" lives —
+    "device" (Auto-PGD draws its restarts there), "cpu" (Square: the same draws on any machine), or None: "pgd" takes no
+    generator and never pops "seed", so a seed in a PGD dict still reaches AttackRunner and is refused there."""
+
+    def __init__(self, accessor, draws, ev, attack, seed=...):
+        if seed is ...:                                  # not an ensemble's: the dict's own, popped before the runner sees the dict
+            seed = attack.pop("seed", None) if draws else None
+        self.ev, self.accessor, self.kwargs, self.runner, self.extra = ev, accessor, attack, None, (None,) if draws else ()
+        if seed is not None:
+            self.extra = (torch.Generator(device=ev.device if draws == "device" else "cpu").manual_seed(int(seed)),)
+
+    def adv(self, x, y):
+        self.runner = getattr(self.ev.net, self.accessor)(x.shape[0], x.shape[-1], **self.kwargs)
+        return self.ev.score(self.runner(x, y, *self.extra))
+
+    def body(self, x, y):
+        clean = self.ev.score(x)                         # the clean batch is scored before the model is asked for a runner
+        return {"clean": clean, "adv": self.adv(x, y)}
+
+    def attack(self, cols=None):
+        return dict(self.runner.args)
+
+
+class _Ensemble:
+    """{name: {...} for each of the two members, "seed": ...}: both start from the clean batch, on generators seeded from the
+    one "seed"; each sample keeps the score with the lower probability of its true label."""
+
+    def __init__(self, names, ev, attack):
+        seed, self.ev, self.method = attack.pop("seed", None), ev, "+".join(names)
+        if set(attack) != set(names):
+            takes = ", ".join("%r: {...}" % name for name in names)
+            raise ValueError(f"attack method {self.method!r} takes {{{takes}, 'seed': ...}}, got the keys {sorted(attack)}")
+        self.runs = {name: ROBUST[name](ev, dict(attack[name]), seed) for name in names}
+
+    def body(self, x, y):
+        clean = self.ev.score(x)
+        s, s2 = [run.adv(x, y) for run in self.runs.values()]        # in the table's order: Auto-PGD runs and is scored before Square
+        # the score is P(class 0): the true label's probability is lower where it is lower for y == 0, higher otherwise
+        return {"clean": clean, "adv": torch.where(y == 0, torch.minimum(s, s2), torch.maximum(s, s2))}
+
+    def attack(self, cols=None):
+        return {"method": self.method, **{name: run.attack() for name, run in self.runs.items()}}
+
+
+class _MinNorm:
+    """"fmn" / "sparse_fmn" by the model's accessor, plus an optional "eps": "adv" is scored on x_adv where the attack flipped
+    the sample within eps (found and radius <= eps; eps absent: every found sample) and on the clean input elsewhere."""
+
+    def __init__(self, accessor, ev, attack):
+        self.eps = attack.pop("eps", None)
+        if self.eps is not None and not float(self.eps) >= 0.0:          # before any batch is drawn
+            raise ValueError(f"eps must be >= 0, got {self.eps!r}")
+        self.ev, self.accessor, self.kwargs, self.runner = ev, accessor, attack, None
+
+    def body(self, x, y):
+        clean = self.ev.score(x)
+        runner = self.runner = getattr(self.ev.net, self.accessor)(x.shape[0], x.shape[-1], **self.kwargs)
+        xa = runner(x, y)
+        take = runner.found.bool() if self.eps is None else runner.found.bool() & (runner.radius <= float(self.eps))
+        adv = self.ev.score(torch.where(take.reshape(-1, 1, 1, 1), xa, x))
+        # the runner reuses its buffers: radius and found are cloned per batch, and gathered ahead of the scores
+        return {"radius": runner.radius.clone(), "found": runner.found.clone(), "clean": clean, "adv": adv}
+
+    def attack(self, cols):
+        radius, found = cols["radius"][0].float().cpu(), cols["found"][0].to(torch.int32).cpu()
+        return dict(self.runner.args, eps=None if self.eps is None else float(self.eps), radius=radius, found=found,
+                    median_radius=float(radius.double().median()) if radius.numel() else float("nan"))
+
+
+ROBUST = {"pgd": partial(_Attack, "attack_runner", None), "apgd": partial(_Attack, "apgd_runner", "device"),
+          "square": partial(_Attack, "square_runner", "cpu"), "apgd+square": partial(_Ensemble, ("apgd", "square")),
+          "fmn": partial(_MinNorm, "fmn_runner"), "sparse_fmn": partial(_MinNorm, "sparse_fmn_runner")}
+
+

@@ -25,6 +25,7 @@ from ..loss import get_loss
 from ..model import load_model
 from .abstract_engine import AbstractEngine
 from .checkpoint import load_checkpoint, save_checkpoint
+from .evaluate import Evaluator
 from .optim import build_optimizer, build_scheduler
 from .parallel import wrap_data_parallel
 
@@ -202,64 +203,31 @@ class TrainEngine(AbstractEngine):
                 dist.destroy_process_group()
             raise
 
-    @torch.no_grad()
-    def _score(self, batches):
-        """p(real) = softmax(cls_out)[:, 0] of `batches` test batches (forgery_engine.py:349,437), gathered over the
-        ranks with two device all_gathers (engine/metrics.py:gather_scores replaces dist.all_gather_object, :374-375).
-        config['config']['inference_graph'] (default false): the forward replays the model's InferenceRunner graph;
-        config['config']['inference_precision'] ("fp32" default, "fp16"): that runner's precision (with inference_graph only)."""
-        from .metrics import gather_scores
+    # ---- the evaluation stages: engine/evaluate.py runs them, these methods are their config defaults and contracts ---------
+    def _evaluator(self):
+        """This engine's GEMM path and eval mode, then the Evaluator.  config['config']['inference_graph'] (default false): the scoring
+        forward replays the model's InferenceRunner graph (infer.py); 'inference_precision' ("fp32" default, "fp16"): that runner's."""
+        self._select_gemm_path()
         self.model.eval()
-        graphed = bool(self.config["config"].get("inference_graph", False))     # opt-in: unidefense_amd/infer.py
-        precision = self.config["config"].get("inference_precision", "fp32")
-        scores, labels = [], []
-        for step in range(1, batches + 1):
-            xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
-            x = torch.cat([xr, xf], 0).contiguous()
-            if graphed:
-                out = self.model_without_ddp.inference_runner(x.shape[0], x.shape[-1], precision)(x)     # one hipGraph replay per batch
-            else:
-                out = self.model(x)          # inference forward: no tape, running statistics
-            scores.append(torch.softmax(out["cls_out"], 1)[:, 0])
-            labels.append(torch.cat([yr, yf], 0))
-        return gather_scores(torch.cat(scores), torch.cat(labels))
+        cfg = self.config["config"]
+        return Evaluator(self.model, self.model_without_ddp, self.test_iterator, self.batch, self.size, self.device,
+                         cfg.get("inference_graph", False), cfg.get("inference_precision", "fp32"), self.local_rank)
 
     def test(self, batches=4):
-        """The reference's test stage (forgery_engine.py:423-452): scores -> cal_metrics (EER, HTER = ACER, TPR@5 %, AUC,
-        ACC, ...) over the frames of all ranks."""
-        from .metrics import cal_metrics
-        self._select_gemm_path()
-        scores, labels = self._score(batches)
-        sc, lb = scores.float().cpu().numpy(), labels.cpu().numpy()
-        ret = {"scores": scores.cpu(), "labels": labels.cpu(), "acc": float(((sc < 0.5).astype(int) == lb).mean())}
-        if len(set(lb.tolist())) == 2:                     # a ROC needs both classes
-            ret.update(cal_metrics(lb, sc, threshold=0.5))
-            if self.local_rank == 0:
-                print("Test | EER %.4f, HTER %.4f, TPR 5%% %.4f, AUC %.4f, ACC %.4f" % (
-                    ret["EER"], ret["ACER"], ret["TPR5%"], ret["AUC"], ret["ACC"]))
-        return ret
-
-    def _metrics(self, scores, labels, tag):
-        """what test() returns for gathered (scores, labels), its line printed as `tag`"""
-        from .metrics import cal_metrics
-        sc, lb = scores.float().cpu().numpy(), labels.cpu().numpy()
-        ret = {"scores": scores.cpu(), "labels": labels.cpu(), "acc": float(((sc < 0.5).astype(int) == lb).mean())}
-        if len(set(lb.tolist())) == 2:
-            ret.update(cal_metrics(lb, sc, threshold=0.5))
-            if self.local_rank == 0:
-                print("%s | EER %.4f, HTER %.4f, TPR 5%% %.4f, AUC %.4f, ACC %.4f" % (
-                    tag, ret["EER"], ret["ACER"], ret["TPR5%"], ret["AUC"], ret["ACC"]))
-        return ret
+        """The reference's test stage (forgery_engine.py:423-452): p(real) = softmax(cls_out)[:, 0] of `batches` test batches
+        (:349,437), gathered over the ranks with two device all_gathers (engine/metrics.py:gather_scores replaces
+        dist.all_gather_object, :374-375) -> cal_metrics (EER, HTER = ACER, TPR@5 %, AUC, ACC, ...) over the frames of all ranks."""
+        return self._evaluator().test(batches)
 
     def test_robust(self, batches=4, attack=None):
-        """test() on clean and on attacked inputs: every test batch is scored as _score does, attacked with the true labels by
+        """test() on clean and on attacked inputs: every test batch is scored as test() does, attacked with the true labels by
         the model's AttackRunner (unidefense_amd/attack.py) and scored again the same way.  attack (default
         config['config']['attack']): the runner's keyword arguments, e.g. {"norm": "linf", "eps": 4/255, "steps": 10} — eps in
         model-input units (after Normalize(0.5, 0.5) one 8-bit grey level is 2/255).  Returns {"clean": what test() returns,
         "adv": the same keys on x_adv, "attack": the resolved arguments, precision and grad_scale included}.  The attack dict's
         "precision": "fp16" (UDEB4; optional "grad_scale") runs the attack's frozen pass in half storage; inference_graph /
         inference_precision keep their meaning for the two scoring forwards.  Data parallel: each rank attacks its own batches on the un-wrapped model (a
-        frozen pass has no collective of its own) and the scores are gathered over the ranks as in _score.
+        frozen pass has no collective of its own) and the scores are gathered over the ranks as in test().
         "method": "apgd" in the attack dict selects Auto-PGD (the model's APGDRunner: norm, eps, steps, restarts, rho, alpha, ...;
         an optional "seed" seeds the generator of its random restarts); "pgd", the default, is the fixed-step AttackRunner.
         "method": "square" selects the black-box Square attack (the model's SquareRunner: eps, steps, p_init, restarts, ...; an
@@ -272,210 +240,29 @@ class TrainEngine(AbstractEngine):
         (CPU tensor) and "median_radius", gathered over the ranks in the scores' order (robust_curve(radius, grid) gives the
         robust accuracy at every eps from this one run).  "method": "sparse_fmn" is the same path on the model's SparseFMNRunner
         (norm "l1": radius and eps are sums of |x_adv - x|; "l0": numbers of changed elements)."""
-        from .metrics import gather_scores
-        attack = attack if attack is not None else self.config["config"].get("attack")
-        if not attack:
-            raise ValueError("test_robust needs an attack: pass attack={...} or set config['config']['attack']")
-        self._select_gemm_path()
-        self.model.eval()
-        graphed = bool(self.config["config"].get("inference_graph", False))
-        precision = self.config["config"].get("inference_precision", "fp32")
-
-        @torch.no_grad()
-        def score(x):
-            if graphed:
-                out = self.model_without_ddp.inference_runner(x.shape[0], x.shape[-1], precision)(x)
-            else:
-                out = self.model(x)
-            return torch.softmax(out["cls_out"], 1)[:, 0]
-
-        attack = dict(attack)
-        method = attack.pop("method", "pgd")
-        if method not in ("pgd", "apgd", "square", "apgd+square", "fmn", "sparse_fmn"):
-            raise ValueError(f"attack method must be 'pgd', 'apgd', 'square', 'apgd+square', 'fmn' or 'sparse_fmn', got {method!r}")
-        if method == "fmn":
-            return self._test_robust_fmn(batches, attack, score, self.model_without_ddp.fmn_runner)
-        if method == "sparse_fmn":
-            return self._test_robust_fmn(batches, attack, score, self.model_without_ddp.sparse_fmn_runner)
-        generator = square_generator = None
-        square = None
-        if method != "pgd":                                  # "seed" makes the random restarts / the draws reproducible
-            seed = attack.pop("seed", None)
-            if seed is not None and method != "square":      # Auto-PGD (APGDRunner) draws its restarts on the device
-                generator = torch.Generator(device=self.device).manual_seed(int(seed))
-            if seed is not None and method != "apgd":        # Square (SquareRunner) draws on the CPU: the same on any machine
-                square_generator = torch.Generator().manual_seed(int(seed))
-        if method == "apgd+square":
-            unknown = set(attack) - {"apgd", "square"}
-            if unknown or "apgd" not in attack or "square" not in attack:
-                raise ValueError(f"attack method 'apgd+square' takes {{'apgd': {{...}}, 'square': {{...}}, 'seed': ...}}, got the keys "
-                                 f"{sorted(attack)}")
-            attack, square = dict(attack["apgd"]), dict(attack["square"])
-        elif method == "square":
-            attack, square = None, attack
-
-        clean, adv, labels, runner, square_runner = [], [], [], None, None
-        for step in range(1, batches + 1):
-            xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
-            x, y = torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
-            clean.append(score(x))
-            if method in ("apgd", "apgd+square"):
-                runner = self.model_without_ddp.apgd_runner(x.shape[0], x.shape[-1], **attack)
-                s = score(runner(x, y, generator))
-            elif method == "pgd":
-                runner = self.model_without_ddp.attack_runner(x.shape[0], x.shape[-1], **attack)
-                s = score(runner(x, y))
-            if square is not None:
-                square_runner = self.model_without_ddp.square_runner(x.shape[0], x.shape[-1], **square)
-                s2 = score(square_runner(x, y, square_generator))
-                # the score is P(class 0): the true label's probability is lower where it is lower for y == 0, higher otherwise
-                s = s2 if method == "square" else torch.where(y == 0, torch.minimum(s, s2), torch.maximum(s, s2))
-            adv.append(s)
-            labels.append(y)
-        labels = torch.cat(labels)
-        if method == "apgd+square":
-            args = {"method": method, "apgd": dict(runner.args), "square": dict(square_runner.args)}
-        else:
-            args = dict((square_runner if method == "square" else runner).args)
-        return {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"),
-                "adv": self._metrics(*gather_scores(torch.cat(adv), labels), "Test(adv)"),
-                "attack": args}
-
-    def _test_robust_fmn(self, batches, attack, score, runner_of):
-        """test_robust's "method": "fmn" and "sparse_fmn": attack is the dict without "method", score the scoring forward,
-        runner_of the model's accessor of the minimum-norm runner (fmn_runner / sparse_fmn_runner)"""
-        from .metrics import gather_scores
-        eps = attack.pop("eps", None)
-        if eps is not None and not float(eps) >= 0.0:
-            raise ValueError(f"eps must be >= 0, got {eps!r}")
-        clean, adv, labels, radius, found, runner = [], [], [], [], [], None
-        for step in range(1, batches + 1):
-            xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
-            x, y = torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
-            clean.append(score(x))
-            runner = runner_of(x.shape[0], x.shape[-1], **attack)
-            xa = runner(x, y)
-            take = runner.found.bool() if eps is None else runner.found.bool() & (runner.radius <= float(eps))
-            adv.append(score(torch.where(take.reshape(-1, 1, 1, 1), xa, x)))
-            labels.append(y)
-            radius.append(runner.radius.clone())
-            found.append(runner.found.clone())
-        labels = torch.cat(labels)
-        radius, _ = gather_scores(torch.cat(radius), labels)
-        found, _ = gather_scores(torch.cat(found), labels)
-        radius, found = radius.float().cpu(), found.to(torch.int32).cpu()
-        args = dict(runner.args)
-        args.update(eps=None if eps is None else float(eps), radius=radius, found=found,
-                    median_radius=float(radius.double().median()) if radius.numel() else float("nan"))
-        return {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"),
-                "adv": self._metrics(*gather_scores(torch.cat(adv), labels), "Test(adv)"),
-                "attack": args}
+        return self._evaluator().test_robust(batches, attack if attack is not None else self.config["config"].get("attack"))
 
     def test_corrupted(self, batches=4, corruptions=None, levels=(1, 2, 3, 4, 5), seed=None, subsampling="420"):
-        """test() on clean and on commonly corrupted inputs (unidefense_amd/corrupt.py): every test batch is scored as _score
+        """test() on clean and on commonly corrupted inputs (unidefense_amd/corrupt.py): every test batch is scored as test()
         does (inference_graph / inference_precision keep their meaning), then once per (kind, level) on corrupt(x, kind, level) —
         one extra launch in front of the same scoring forward.  corruptions (default config['config']['corruptions'], then all
         seven): names of corrupt.CORRUPTIONS; levels: severities 1..5; seed: seeds the device generator of the noise fields and
         block positions; subsampling: JPEG's chroma format.  Returns {"clean": what test() returns, "corrupted": {kind: {level:
         the same keys}}, "mean": {kind: {"AUC", "ACC"}} averaged over the levels (where both classes are present),
-        "corruptions": {kind: {level: the resolved parameter}}}.  Scores are gathered over the ranks as in _score."""
-        from .. import corrupt as CR
-        from .metrics import gather_scores
+        "corruptions": {kind: {level: the resolved parameter}}}.  Scores are gathered over the ranks as in test()."""
         kinds = corruptions if corruptions is not None else self.config["config"].get("corruptions")
-        kinds = list(kinds) if kinds else list(CR.CORRUPTIONS)
-        levels = tuple(levels)
-        resolved = {k: {lv: CR.resolve(k, lv)[0][1] for lv in levels} for k in kinds}        # refuses before any kernel runs
-        if subsampling not in CR.SUBSAMPLINGS:
-            raise ValueError(f"subsampling must be one of {CR.SUBSAMPLINGS}, got {subsampling!r}")
-        self._select_gemm_path()
-        self.model.eval()
-        graphed = bool(self.config["config"].get("inference_graph", False))
-        precision = self.config["config"].get("inference_precision", "fp32")
-        generator = None if seed is None else torch.Generator(device=self.device).manual_seed(int(seed))
-
-        @torch.no_grad()
-        def score(x):
-            if graphed:
-                out = self.model_without_ddp.inference_runner(x.shape[0], x.shape[-1], precision)(x)
-            else:
-                out = self.model(x)
-            return torch.softmax(out["cls_out"], 1)[:, 0]
-
-        clean, labels, cor, x_cor = [], [], {(k, lv): [] for k in kinds for lv in levels}, None
-        for step in range(1, batches + 1):
-            xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
-            x = torch.cat([xr, xf], 0).contiguous()
-            clean.append(score(x))
-            labels.append(torch.cat([yr, yf], 0))
-            x_cor = torch.empty_like(x) if x_cor is None or x_cor.shape != x.shape else x_cor
-            for key in cor:
-                cor[key].append(score(CR.corrupt(x, key[0], key[1], generator=generator, subsampling=subsampling, out=x_cor)))
-        labels = torch.cat(labels)
-        ret = {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"), "corrupted": {}, "mean": {},
-               "corruptions": resolved}
-        for k in kinds:
-            ret["corrupted"][k] = {lv: self._metrics(*gather_scores(torch.cat(cor[(k, lv)]), labels), "Test(%s %d)" % (k, lv))
-                                   for lv in levels}
-            both = [r for r in ret["corrupted"][k].values() if "AUC" in r]
-            if both:
-                ret["mean"][k] = {m: float(sum(r[m] for r in both) / len(both)) for m in ("AUC", "ACC")}
-                if self.local_rank == 0:
-                    print("Corrupted %-14s | mean AUC %.4f, mean ACC %.4f | AUC by level %s" % (
-                        k, ret["mean"][k]["AUC"], ret["mean"][k]["ACC"],
-                        " ".join("%d:%.4f" % (lv, ret["corrupted"][k][lv]["AUC"]) for lv in levels if "AUC" in ret["corrupted"][k][lv])))
-        return ret
+        return self._evaluator().test_corrupted(batches, kinds, levels, seed, subsampling)
 
     def test_spatial(self, batches=4, spatial=None):
         """test() on clean inputs and on each sample's worst spatial candidate (unidefense_amd/spatial.py): every test batch is
-        scored as _score does (inference_graph / inference_precision keep their meaning), searched with the true labels by the
+        scored as test() does (inference_graph / inference_precision keep their meaning), searched with the true labels by the
         model's SpatialRunner and scored again the same way on its x_adv.  spatial (default config['config']['spatial'], then the
         runner's defaults): the runner's keyword arguments, e.g. {"max_angle": 10.0, "max_shift": 0.05, "grid": (7, 5, 3)}; an
         optional "seed" seeds the CPU generator of a random search.  Returns {"clean": what test() returns, "adv": the same keys on
         x_adv, "attack": the resolved arguments plus "best" (CPU [n, 5]: each sample's (angle, dx, dy, scale, flip)) and "fooled"
         (the fraction with best_loss <= 0 among the samples with loss0 > 0; NaN where there are none)}.  Scores, best and the
-        two losses are gathered over the ranks as in _score."""
-        from .metrics import gather_scores
-        spatial = spatial if spatial is not None else self.config["config"].get("spatial")
-        spatial = dict(spatial) if spatial else {}
-        seed = spatial.pop("seed", None)
-        generator = None if seed is None else torch.Generator().manual_seed(int(seed))
-        self._select_gemm_path()
-        self.model.eval()
-        graphed = bool(self.config["config"].get("inference_graph", False))
-        precision = self.config["config"].get("inference_precision", "fp32")
-
-        @torch.no_grad()
-        def score(x):
-            if graphed:
-                out = self.model_without_ddp.inference_runner(x.shape[0], x.shape[-1], precision)(x)
-            else:
-                out = self.model(x)
-            return torch.softmax(out["cls_out"], 1)[:, 0]
-
-        clean, adv, labels, best, best_loss, loss0, runner = [], [], [], [], [], [], None
-        for step in range(1, batches + 1):
-            xr, yr, xf, yf = self.test_iterator(step, self.batch, self.size, self.device)
-            x, y = torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
-            try:
-                runner = self.model_without_ddp.spatial_runner(x.shape[0], x.shape[-1], **spatial)
-            except TypeError as e:                       # an unknown key is a bad dict, like a bad value
-                raise ValueError(f"spatial takes SpatialRunner's keyword arguments and 'seed': {e}") from None
-            clean.append(score(x))
-            adv.append(score(runner(x, y, generator)))
-            labels.append(y)
-            best.append(runner.best.to(self.device))
-            best_loss.append(runner.best_loss.clone())
-            loss0.append(runner.loss0.clone())
-        labels = torch.cat(labels)
-        best = torch.stack([gather_scores(torch.cat(best)[:, i].contiguous(), labels)[0] for i in range(5)], 1).cpu()
-        best_loss, _ = gather_scores(torch.cat(best_loss), labels)
-        loss0, _ = gather_scores(torch.cat(loss0), labels)
-        held = loss0 > 0
-        args = dict(runner.args)
-        args.update(best=best, fooled=float((best_loss[held] <= 0).double().mean()) if bool(held.any()) else float("nan"))
-        return {"clean": self._metrics(*gather_scores(torch.cat(clean), labels), "Test"),
-                "adv": self._metrics(*gather_scores(torch.cat(adv), labels), "Test(spatial)"),
-                "attack": args}
+        two losses are gathered over the ranks as in test()."""
+        return self._evaluator().test_spatial(batches, spatial if spatial is not None else self.config["config"].get("spatial"))
 
     def validate(self, step, batches=4):
         """The reference's validate (forgery_engine.py:320-421) without the figure / wandb plumbing: metrics over all
