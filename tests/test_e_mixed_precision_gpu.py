@@ -90,7 +90,7 @@ def fp32_and_yardstick():
 def test_fp16_mode_deviates_like_one_rounding_of_the_parameters(storage, fp32_and_yardstick):
     """BASELINE configs[4] at its own batch (64 per GPU).  storage = "fp32": fp16 MFMA operands, fp32 accumulation, fp32
     activations; "half": additionally the MBConv trunk keeps activations and activation gradients in fp16 (every kernel of
-    tape.mbconv_fused instantiated for _Float16, half-operand GEMM loaders) — the full mode.
+    mbconv.mbconv_fused instantiated for _Float16, half-operand GEMM loaders) — the full mode.
     The reference has no such mode, so the bar is the step's own conditioning: each deviation from the fp32 step (outputs in
     relative L2; median / 90 % / 99 % / max of the per-tensor relative L2 of the ~480 well-defined parameter gradients) must
     stay within 4 x what ONE fp16 rounding of the parameters and inputs does to the exact step (observed: 0.8 x with fp32
@@ -293,9 +293,10 @@ def test_adjoint_transform_does_the_depthwise_backward_in_half_storage(N, S, Cc,
 
 
 def _run_stage_hip(m, stage, h_pix, rng_cpu, dout_pix, dev):
-    """blocks of one backbone stage on the fused training path (tape.mbconv_fused), forward + backward, outside the model's
+    """blocks of one backbone stage on the fused training path (mbconv.mbconv_fused), forward + backward, outside the model's
     _run: returns (out, d input, {parameter name: gradient})"""
     from unidefense_amd import kernels as K
+    from unidefense_amd import mbconv as MB
     from unidefense_amd import tape as T
     K.begin_forward(m)
     try:
@@ -306,8 +307,7 @@ def _run_stage_hip(m, stage, h_pix, rng_cpu, dout_pix, dev):
         ws = [blk._depthwise_conv.weight for blk in m.backbone._blocks]
         wts = K.dw_weights_tapmajor(ws)
         T.DW_WT = {id(w): (w, w._version, wts[id(w)]) for w in ws}
-        rng["_fused"] = {"wt": wts, "dp": T.DataParallelCtx(None, None)}
-        out = m._blocks(tape, h_pix, stage, rng)
+        out = m._blocks(tape, h_pix, stage, rng, MB.TrunkMode(MB.FUSED, wts, T.DataParallelCtx(None, None)))
     finally:
         K.end_forward()
     got = {}

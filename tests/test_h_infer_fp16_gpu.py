@@ -1,5 +1,5 @@
 """GPU: the fp16 inference runner (InferenceRunner(model, batch, size, "fp16"), UDEB4): the eval forward with the MBConv trunk in
-half storage (tape.mbconv_eval_half) captured as one hipGraph.
+half storage (mbconv.mbconv_eval_half) captured as one hipGraph.
 
 Bars: a reduced-precision mode is held to the float64 oracle by the rule tests/test_e_mixed_precision_gpu.py uses for training —
 each output's relative L2 deviation within max(4 x the deviation that ONE fp16 rounding of the parameters and the input causes in
@@ -313,12 +313,13 @@ def test_mb_eval_dw_h_refuses_training_form_bn():
 @pytest.mark.parametrize("node", [False, True], ids=["composed", "node"])
 @pytest.mark.parametrize("stage", [1, 2, 3, 4, 5, 6])
 def test_fp16_eval_stage_local_vs_float64_oracle(stage, node):
-    """every backbone stage's blocks on the fp16 eval path (tape.mbconv_eval_half, with the model's node threshold) fed the float64
+    """every backbone stage's blocks on the fp16 eval path (mbconv.mbconv_eval_half, with the model's node threshold) fed the float64
     oracle's own eval-mode input of that stage rounded once to fp16, against oracle/eb4.py:mbconv(training=False) in float64 on the
     same rounded input: relative L2 of the output <= 3e-3.  node: the expanding non-SF blocks on ud_mb_eval_dw_h (the model's
     threshold keeps them on the composed half kernels, which measured faster)"""
     dev = _dev()
     from unidefense_amd import kernels as K
+    from unidefense_amd import mbconv as MB
     from unidefense_amd import tape as T
     ou.fit_cpu_threads()
     x = param_fill.make_input(4, 256, 38)
@@ -340,7 +341,7 @@ def test_fp16_eval_stage_local_vs_float64_oracle(stage, node):
             ws = [blk._depthwise_conv.weight for blk in m.backbone._blocks]
             wts = K.dw_weights_tapmajor(ws)
             T.DW_WT = {id(w): (w, w._version, wts[id(w)]) for w in ws}
-            out = m._blocks(None, pix(h64).to(dev).half(), stage, {"_eval16": wts, "drop_connect": {}})
+            out = m._blocks(None, pix(h64).to(dev).half(), stage, {"drop_connect": {}}, MB.TrunkMode(MB.HALF, wts))
         finally:
             K.end_forward()
         torch.cuda.synchronize()

@@ -1,6 +1,6 @@
 """GPU: the fp16 input-gradient / attack runners (InputGradRunner / AttackRunner with precision="fp16", UDEB4) and the frozen half
 backward under them: the entry points that REQUIRE the eval form of ud_bn_ref (ud_coldot_bn_eval, ud_se_scale_bwd_bn_eval,
-ud_bn_eval_bwd, ud_dwtile_dgrad_eval, ud_sfmix_pool_bwd) and the tape node tape.mbconv_frozen_half.
+ud_bn_eval_bwd, ud_dwtile_dgrad_eval, ud_sfmix_pool_bwd) and the tape node mbconv.mbconv_frozen_half.
 
 Bars.  Kernels: the project's own for these kernel families (tests/test_b_fused_kernels_gpu.py) — relative L2 2e-5 in fp32 storage,
 1e-3 in half storage (one fp16 rounding of the result) — against float64 restatements written here with torch autograd on
@@ -267,15 +267,16 @@ def test_frozen_entry_points_refuse_a_training_form_bn_on_the_device():
     torch.cuda.synchronize()
 
 
-# ---- 2. stage-local: tape.mbconv_frozen_half against the float64 oracle -------------------------------------------------------
+# ---- 2. stage-local: mbconv.mbconv_frozen_half against the float64 oracle -------------------------------------------------------
 @pytest.mark.parametrize("stage", [0, 1, 2, 3, 4, 5, 6])
 def test_frozen_half_stage_local_vs_float64_oracle(stage):
-    """every backbone stage's blocks on tape.mbconv_frozen_half alone, forward and backward, fed the float64 oracle's own eval-mode
+    """every backbone stage's blocks on mbconv.mbconv_frozen_half alone, forward and backward, fed the float64 oracle's own eval-mode
     input of that stage rounded once to fp16 (stage 0: the raw stem output, its BatchNorm + swish applied on load) and a seeded
     output gradient, against oracle/eb4.py:mbconv(training=False) autograd in float64 on the same tensors.
     Observed (MI355X): see DESIGN 3l."""
     dev = _dev()
     from unidefense_amd import kernels as K
+    from unidefense_amd import mbconv as MB
     from unidefense_amd import tape as T
     x = param_fill.make_input(4, 256, 38)
     sd = ou.oracle_state(0.0, 0.3, dtype=torch.float64)
@@ -308,8 +309,8 @@ def test_frozen_half_stage_local_vs_float64_oracle(stage):
             ws = [blk._depthwise_conv.weight for blk in m.backbone._blocks]
             wts = K.dw_weights_tapmajor(ws)
             T.DW_WT = {id(w): (w, w._version, wts[id(w)]) for w in ws}
-            lazy = T.LazyInput(K.EvalBN(m.backbone._bn0, 1), lambda dh: got.update(dx=dh)) if stage == 0 else None
-            out = m._blocks(tape, h_pix, stage, {"_eval16": wts, "drop_connect": {}}, lazy)
+            lazy = MB.LazyInput(K.EvalBN(m.backbone._bn0, 1), lambda dh: got.update(dx=dh)) if stage == 0 else None
+            out = m._blocks(tape, h_pix, stage, {"drop_connect": {}}, MB.TrunkMode(MB.HALF, wts), lazy)
         finally:
             K.end_forward()
         assert len(tape.nodes) == hi - lo                                   # one node per block: no block left the frozen half path
@@ -330,12 +331,12 @@ def test_frozen_half_stage_local_vs_float64_oracle(stage):
 
 def test_frozen_half_node_refuses_a_tape_with_weight_gradients():
     dev = _dev()
-    from unidefense_amd import tape as T
+    from unidefense_amd import mbconv as MB, tape as T
     m = _shared(dev)
     tape = T.Tape()                                                           # wgrad_on True: a training tape
     x = torch.zeros(1, 8, 8, m.backbone._blocks[30].spec.cin, device=dev, dtype=torch.float16)
     with pytest.raises(RuntimeError, match="FROZEN"):
-        T.mbconv_frozen_half(tape, x, m.backbone._blocks[30], None)
+        MB.mbconv_frozen_half(tape, x, m.backbone._blocks[30], None)
 
 
 # ---- 3. whole model against the float64 oracle --------------------------------------------------------------------------------
@@ -371,7 +372,7 @@ def _flat(out):
 @pytest.mark.parametrize("size,n,seed", [(256, 1, 7), (256, 2, 7), (380, 1, 7)])
 def test_fp16_input_grad_runner_vs_float64_oracle(size, n, seed):
     """Observed (MI355X): see DESIGN 3l."""
-    from unidefense_amd import lib, tape as T
+    from unidefense_amd import lib, mbconv as MB
     from unidefense_amd.attack import InputGradRunner
     from unidefense_amd.infer import InferenceRunner
     dev = _dev()
@@ -393,11 +394,11 @@ def test_fp16_input_grad_runner_vs_float64_oracle(size, n, seed):
         v = float(t.float().abs().max())
         if not v <= peak.get("v", -1.0):
             peak.update(v=v, where=name)
-    T.HALF_GRAD_PROBE = probe
+    MB.HALF_GRAD_PROBE = probe
     try:
         eager = r(xd, yd).clone()                                            # the eager warm-up: the probe may synchronise
     finally:
-        T.HALF_GRAD_PROBE = None
+        MB.HALF_GRAD_PROBE = None
     reps = [r(xd, yd).clone() for _ in range(3)]
     out16 = {k: v.clone() for k, v in _flat(r.out).items()}
     torch.cuda.synchronize()

@@ -1,4 +1,4 @@
-"""GPU, SELF-comparison (runs last: nothing here is an oracle test): the fused MBConv path (tape.mbconv_fused: deferred
+"""GPU, SELF-comparison (runs last: nothing here is an oracle test): the fused MBConv path (mbconv.mbconv_fused: deferred
 BatchNorm, csrc/fused.hip) against the operator-by-operator path it replaces (tape.conv1x1 / batchnorm_act / sfconv_dw /
 squeeze_excite / residual — each tested against torch in float64 by tests/test_a_kernels_gpu.py and against the reference's
 goldens by tests/test_c_model_gpu.py).  Reference: model/efficientnet/model.py:94-135, exp.py:46-65.
@@ -134,19 +134,19 @@ def test_skip_gradient_accumulated_in_place_equals_separate_add():
 
 @pytest.mark.parametrize("half", [False, True], ids=["fp32", "half"])
 def test_tiled_depthwise_policy_equals_strip_kernels(half):
-    """tape._dw_tile_policy routes some depthwise convs of the fused node to the LDS-tiled kernels (csrc/dwtile.hip); with
+    """mbconv._dw_tile_policy routes some depthwise convs of the fused node to the LDS-tiled kernels (csrc/dwtile.hip); with
     the policy off every one of them runs on the strip kernels.  Same step either way: fp32 storage to fp32 rounding; half
     storage to a few fp16 roundings (the tiled forward reads swish(bn0(e)) unrounded, the strip kernel reads the fp16 copy
     rfft2_ex / bn_apply stored)."""
-    from unidefense_amd import tape as T
+    from unidefense_amd import mbconv as MB
     from unidefense_amd.loss import LOSSES
     from unidefense_amd.model import load_model
     dev = _dev()
     n = 8
 
     def run(tiled):
-        saved = T._DW_TILED
-        T._DW_TILED = tiled
+        saved = MB._DW_TILED
+        MB._DW_TILED = tiled
         try:
             m = load_model("UDEB4")(extractor="efficientnet-b4", num_classes=2, drop_rate=0.5)
             param_fill.fill_module_(m, sf_coef=0.0, fuse_coef=0.3)
@@ -166,7 +166,7 @@ def test_tiled_depthwise_policy_equals_strip_kernels(half):
             return ({k: out[k].detach().double() for k in ("cls_out", "rec")},
                     {k: p.grad.detach().double() / 64.0 for k, p in m.named_parameters() if p.grad is not None})
         finally:
-            T._DW_TILED = saved
+            MB._DW_TILED = saved
             LOSSES["aw_triplet"].n_real = None
     o0, g0 = run(False)
     o1, g1 = run(True)

@@ -1,12 +1,12 @@
 """Round 5: the depthwise conv's data + weight gradient as ONE kernel (kernels.dwtile_bwd, csrc/dwtile.hip: dw_tile_bwd_kernel)
-against the pair of kernels the step launched until round 4 (the choice of tape._dw_tile_policy per shape: tiled or strip), on
+against the pair of kernels the step launched until round 4 (the choice of mbconv._dw_tile_policy per shape: tiled or strip), on
 the stride-1 depthwise shapes of UDEB4 at bs 32 (--half: half storage, bs 64).  Graph-replayed launches, us per call."""
 import sys
 import torch
 
 sys.path.insert(0, ".")
 from unidefense_amd import kernels as K          # noqa: E402
-from unidefense_amd import tape as T             # noqa: E402
+from unidefense_amd import mbconv as MB          # noqa: E402
 from tools.bench_dwtile import timed             # noqa: E402  (prints its own table when imported as a script only)
 
 half = "--half" in sys.argv
@@ -32,7 +32,7 @@ for name, H, Cc, k, plain, nobn in SHAPES:
     K.colstats(x.view(M, Cc), acc)
     bn = None if nobn else K.DeferredBN(acc, Cc, M, gamma, beta, 1e-3, 1)
     a = x if nobn else K.bn_apply(x, bn, 1, M)
-    t_fwd, t_wg, t_bwd = T._dw_tile_policy(not plain, k, 1, H, half)
+    t_fwd, t_wg, t_bwd = MB._dw_tile_policy(not plain, k, 1, H, half)
 
     def wg():
         if t_wg:

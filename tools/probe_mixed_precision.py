@@ -1,7 +1,7 @@
 import sys, torch, numpy as np
 sys.path.insert(0, ".")
 from tests.test_e_mixed_precision_gpu import _step
-from unidefense_amd import tape as T
+from unidefense_amd import mbconv as MB
 dev = torch.device("cuda:0")
 for n in (16, 64):
     o32, g32 = _step(dev, 0, n=n)
@@ -14,7 +14,7 @@ for n in (16, 64):
           "grad relL2 50/90/99/max: %.3g %.3g %.3g %.3g" % (np.percentile(r, 50), np.percentile(r, 90), np.percentile(r, 99), r.max()))
     for storage in ("fp32", "half"):
         for tiled in (False, True):
-            T._DW_TILED = tiled
+            MB._DW_TILED = tiled
             o16, g16 = _step(dev, 3, n=n, half_storage=storage == "half")
             rms = {k: float((o16[k] - o32[k]).norm() / o32[k].norm().clamp_min(1e-30)) for k in o32}
             rel = []
@@ -26,4 +26,4 @@ for n in (16, 64):
             r = np.array(rel)
             print(f"n={n} storage={storage} tiled={tiled}: out rms", {k: f"{v:.2e}" for k, v in rms.items()},
                   "grad relL2 50/90/99/max: %.3g %.3g %.3g %.3g" % (np.percentile(r, 50), np.percentile(r, 90), np.percentile(r, 99), r.max()))
-    T._DW_TILED = True
+    MB._DW_TILED = True

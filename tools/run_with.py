@@ -1,5 +1,5 @@
 """A/B helper: set module-level knobs of the package, then run a script in this process.
-usage: python tools/run_with.py kernels._P3_RASTER=0 tape._DW_TILED=False -- bench.py --steps 10
+usage: python tools/run_with.py kernels._P3_RASTER=0 mbconv._DW_TILED=False -- bench.py --steps 10
 (the compile-time constants that used to be UD_* environment variables are plain module attributes now)"""
 import ast
 import importlib

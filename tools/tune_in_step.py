@@ -179,9 +179,9 @@ def main():
 
     if args.knobs:
         from unidefense_amd import lib as _lib
-        from unidefense_amd import tape as T
+        from unidefense_amd import mbconv as MB
         seen_tile, seen_fused = [], []
-        o_tile, o_fused = T._dw_tile_policy, T._dw_bwd_fused_policy
+        o_tile, o_fused = MB._dw_tile_policy, MB._dw_bwd_fused_policy
 
         def log_tile(sf, k, stride, H, half):
             key = (bool(sf), k, stride, H, bool(half))
@@ -194,12 +194,12 @@ def main():
             if key not in seen_fused and stride == 1:
                 seen_fused.append(key)
             return o_fused(sf, k, stride, H, half)
-        T._dw_tile_policy, T._dw_bwd_fused_policy = log_tile, log_fused
+        MB._dw_tile_policy, MB._dw_bwd_fused_policy = log_tile, log_fused
         with torch.cuda.stream(side):
             step()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        T._dw_tile_policy, T._dw_bwd_fused_policy = o_tile, o_fused
+        MB._dw_tile_policy, MB._dw_bwd_fused_policy = o_tile, o_fused
         state = {"base": min(measure(), measure())}
         print(f"# policy search; baseline {state['base']:.3f} ms; {len(seen_tile)} depthwise block classes", flush=True)
         kept = []
@@ -208,14 +208,14 @@ def main():
             for pos, name in enumerate(("forward", "weight gradient", "data gradient")):
                 new = tuple((not v) if i == pos else v for i, v in enumerate(cur))
                 if trial(f"dw_tile{key} {name}: {cur[pos]} -> {new[pos]}",
-                         lambda: T._DW_TILE_OVERRIDE.__setitem__(key, new), lambda: T._DW_TILE_OVERRIDE.pop(key, None), state):
-                    kept.append(("tape._DW_TILE_OVERRIDE", key, new))
+                         lambda: MB._DW_TILE_OVERRIDE.__setitem__(key, new), lambda: MB._DW_TILE_OVERRIDE.pop(key, None), state):
+                    kept.append(("mbconv._DW_TILE_OVERRIDE", key, new))
                     cur = new
         for key in seen_fused:
             cur = bool(o_fused(*key))
             if trial(f"dw_bwd_fused{key}: {cur} -> {not cur}",
-                     lambda: T._DW_BWD_FUSED_OVERRIDE.__setitem__(key, not cur), lambda: T._DW_BWD_FUSED_OVERRIDE.pop(key, None), state):
-                kept.append(("tape._DW_BWD_FUSED_OVERRIDE", key, not cur))
+                     lambda: MB._DW_BWD_FUSED_OVERRIDE.__setitem__(key, not cur), lambda: MB._DW_BWD_FUSED_OVERRIDE.pop(key, None), state):
+                kept.append(("mbconv._DW_BWD_FUSED_OVERRIDE", key, not cur))
         for kind in ("rfft", "rfft_ex", "irfft", "irfft_mix"):
             for S in (32, 64):
                 item = (kind, S, args.dtype == "f16")

@@ -16,7 +16,7 @@ AttackRunner's graph holds ONE iteration — forward on the static leaf x_adv, o
 place by csrc/attack.hip (L-infinity: one launch; L2: norm, step, norm, projection) — and a call replays it `steps` times.
 
 precision="fp16" (UDEB4 only; runner-scoped like InferenceRunner's): the MBConv trunk's forward AND backward in half storage —
-every block is one tape node (tape.mbconv_frozen_half) whose forward is the fp16 InferenceRunner's (runner.out is bitwise that
+every block is one tape node (mbconv.mbconv_frozen_half) whose forward is the fp16 InferenceRunner's (runner.out is bitwise that
 runner's output) and whose backward goes through the eval-form BatchNorms as per-channel constants (csrc: ud_bn_eval_bwd,
 ud_coldot_bn_eval, ud_se_scale_bwd_bn_eval, ud_dwtile_dgrad_eval; the training-form backward entry points keep refusing the eval
 form).  The stem's data gradient, decoder, attention, head and objective stay fp32.  The objective is multiplied by grad_scale (a

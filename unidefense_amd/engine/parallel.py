@@ -11,7 +11,7 @@ The path shards over the batch only.  Exchanges per backward:
     end and returns views of the reduced flat buffers (no copy back).  The mean over ranks comes for free: the
     incoming loss gradient is scaled by 1/world before the tape runs (everything downstream is linear in it,
     including the SyncBN sums).
-  * SyncBatchNorm statistics, enabled by ``sync_bn=True``.  Fused MBConv path (tape.mbconv_fused): the fp64
+  * SyncBatchNorm statistics, enabled by ``sync_bn=True``.  Fused MBConv path (mbconv.mbconv_fused): the fp64
     accumulators (sum x, sum x^2) of a BatchNorm are summed over the ranks IN PLACE between the kernel that fills them
     and the kernels that consume them (tape.DataParallelCtx.reduce), likewise (sum dz, sum dz*xhat) in the backward —
     2C doubles each way.  Every rank must hold the SAME number of rows (the count is rows * world; engine/data.py pads the

@@ -7,14 +7,14 @@ call copies the input in and replays.  K.begin_forward runs inside the graph and
 buffers in place, so a runner captured before an optimizer step (or a load_state_dict, or a change of running statistics)
 gives the updated model's output afterwards without being rebuilt.
 
-UDEB4's block group 1 takes the eval-mode node (model.unidefense._mbconv_eval: the expand conv inside the depthwise pass,
+UDEB4's block group 1 takes the eval-mode node (mbconv.mbconv_eval: the expand conv inside the depthwise pass,
 csrc/evalblk.hip) during the runner's warm-up and capture; every other layer, and the ResNet variants as a whole, are captured
 as their eager eval forward.
 
 precision="fp16" (UDEB4 only): the MBConv trunk in half storage with the storage boundaries of the fp16 training mode — the stem
 conv's output rounded once to half, the 32 blocks' activations fp16 in memory (fp32 arithmetic in registers, fp16 MFMA 1x1
 convs with fp32 accumulation), the decoder, attention, head and losses fp32 — on eval-form BatchNorms with no batch statistics
-(tape.mbconv_eval_half).  Selected by a runner-scoped flag; the eager eval forward and the fp32 runner do not change.
+(mbconv.mbconv_eval_half).  Selected by a runner-scoped flag; the eager eval forward and the fp32 runner do not change.
 """
 import contextlib
 

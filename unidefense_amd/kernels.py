@@ -3261,7 +3261,7 @@ def se_scale_bwd_bn(dc, x, bn, s, dpool, inv_hw, G, R, sacc):
     return dz
 
 
-# ---- the frozen backward (tape.mbconv_frozen_half): through EVAL-FORM BatchNorms (EvalBN), data gradients only ----
+# ---- the frozen backward (mbconv.mbconv_frozen_half): through EVAL-FORM BatchNorms (EvalBN), data gradients only ----
 def coldot_bn_eval(dy, x, bn, G, R, out):
     """out[g][c] += sum_r dy * act(bn(x)) for an EvalBN (the SE gate's gradient); deterministic (no atomics across workgroups)"""
     h = _act(dy, x)

@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from .. import kernels as K
 from ..config import cfg
+from .. import mbconv as MB
 from .. import tape as T
 from .arch import DELIMITER_DICT, build_arch
 
@@ -100,7 +101,7 @@ _OUT_KEYS = ("cls_out", "rec", "factorization", "triplet0", "triplet1", "triplet
              "spatial", "freq")
 
 
-# training mode: MBConv blocks as fused tape nodes with deferred BatchNorms (tape.mbconv_fused); cfg.fused_mbconv = False
+# training mode: MBConv blocks as fused tape nodes with deferred BatchNorms (mbconv.mbconv_fused); cfg.fused_mbconv = False
 # runs the operator-by-operator path (same results: tests/test_z_fused_selfcheck_gpu.py compares the two)
 def _fused_mbconv():
     return cfg.fused_mbconv
@@ -218,13 +219,13 @@ class RunnerMethods:
 
     def inference_runner(self, batch, size, precision="fp32"):
         """The graph-captured eval forward for [batch, 3, size, size] inputs (InferenceRunner); precision "fp16": the MBConv
-        trunk in half storage (tape.mbconv_eval_half)."""
+        trunk in half storage (mbconv.mbconv_eval_half)."""
         from ..infer import inference_runner
         return inference_runner(self, batch, size, precision)
 
     def input_grad_runner(self, batch, size, objective="cross_entropy", precision="fp32", grad_scale=None):
         """The graph-replayed gradient of objective(model(x), y) with respect to x for [batch, 3, size, size] inputs
-        (InputGradRunner).  precision "fp16": the MBConv trunk's forward and backward in half storage (tape.mbconv_frozen_half),
+        (InputGradRunner).  precision "fp16": the MBConv trunk's forward and backward in half storage (mbconv.mbconv_frozen_half),
         the objective scaled by grad_scale (default 1024) and the result unscaled."""
         from ..attack import input_grad_runner
         return input_grad_runner(self, batch, size, objective, precision, grad_scale)
@@ -434,72 +435,38 @@ class UniDefenseModelEb4(RunnerMethods, nn.Module):
     # 17.00 with it on group 1 (Ci 24 / 32), 17.20 also on group 7 (Ci 272 / 448); 380^2 bs 96 42.95 / 43.12 / 43.89
     EVAL_NODE_H_MAX_CIN = 0          # measured slower than the composed half kernels on both groups: off
 
-    @classmethod
-    def _eval_block_ok(cls, blk):
-        sp = blk.spec
-        return (sp.expand != 1 and sp.sf_norm is None and sp.cin <= cls.EVAL_NODE_MAX_CIN
-                and K.mb_eval_dw_ok(sp.cin, sp.cexp, sp.k, sp.stride))
-
-    def _mbconv_eval(self, x, blk):
-        """MBConvBlock.forward in eval mode on the eval-form BatchNorms (kernels.EvalBN): ud_mb_eval_dw makes d and the SE
-        squeeze from the thin input (the expanded tensor is never written), then the SE gate, the project conv and BN2 +
-        the residual — ud_pj_fwd_fused (gate and BN1 applied on load) + ud_residual_bn where the project pair is built for it,
-        ud_se_scale_fwd + the GEMM + ud_residual_bn elsewhere."""
-        sp = blk.spec
-        N, H, W, Ci = x.shape
-        k, s = sp.k, sp.stride
-        pl, pr, pt, pb = sp.pad
-        Ho = (H + pt + pb - k) // s + 1
-        Wo = (W + pl + pr - k) // s + 1
-        CE, Co, HW = sp.cexp, sp.cout, Ho * Wo
-        w = blk._depthwise_conv.weight
-        ent = T.DW_WT.get(id(w))
-        wt = ent[2] if (ent is not None and ent[0] is w) else w.view(CE, k * k).t().contiguous()
-        bn1 = K.EvalBN(blk._bn1, 1)
-        w2 = blk._project_conv.weight.view(Co, CE)
-        pj = K.project_fwd_fused_ok(x, w2, HW)
-        d, pool = K.mb_eval_dw(x, blk._expand_conv.weight.view(CE, Ci), K.EvalBN(blk._bn0, 1), wt, bn1, k, s, pt, pl, Ho, Wo,
-                               out_act=not pj)
-        s1 = K.fc_fwd(pool, blk._se_reduce.weight.view(sp.cse, CE), blk._se_reduce.bias, 0)
-        s2 = K.fc_fwd(s1, blk._se_expand.weight.view(CE, sp.cse), blk._se_expand.bias, 1)
-        if pj:
-            p, _ = K.project_fwd_fused(d, bn1, s2, w2, N, HW)
-        else:
-            p = K.gemm_nt(K.se_scale_fwd(d, s2).view(N * HW, CE), w2)
-        return K.residual_bn(p.view(N, Ho, Wo, Co), K.EvalBN(blk._bn2, 0), None, 1.0, x if sp.skip else None, N, HW)
-
-    def _blocks(self, tape, x, stage, rng, lazy_in=None):
-        """forward_backbone_block (model/unidefense.py:159-172)."""
+    def _blocks(self, tape, x, stage, rng, mode, lazy_in=None):
+        """forward_backbone_block (model/unidefense.py:159-172).  mode: the mbconv.TrunkMode _run chose; a block its node does not
+        take runs on the operators (_mbconv)."""
         start = self.delimiter[stage - 1] if stage > 0 else 0
         end = self.delimiter[stage]
         nblk = len(self.backbone._blocks)
         rate0 = self.arch["drop_connect_rate"]
-        fused = rng.get("_fused")
         for idx in range(start, end):
             rate = rate0 * float(idx) / nblk if rate0 else 0.0
             keep = rng["drop_connect"].get(idx) if (self.training and rate) else None
             blk = self.backbone._blocks[idx]
-            if fused is not None and (blk.spec.sf_norm is None or K.fft_kernel_size(x.shape[1])):
-                # training mode: one tape node per block, BatchNorms deferred into their consumers (tape.mbconv_fused); an SF block
-                # on a map side fft.hip has no in-register transform for (95 at 380 x 380) takes the operator path below
+            wt = mode.wt[id(blk._depthwise_conv.weight)]
+            # an SF block on a map side fft.hip has no in-register transform for (95 at 380 x 380) is not for the fused / half nodes
+            sf_ok = blk.spec.sf_norm is None or K.fft_kernel_size(x.shape[1])
+            if mode.kind == MB.FUSED and sf_ok:
+                # training mode: one tape node per block, BatchNorms deferred into their consumers (mbconv.mbconv_fused)
                 pend = self.__dict__.setdefault("_nbt_pending", [])
                 pend.extend(b.num_batches_tracked for b in (getattr(blk, "_bn0", None), blk._bn1, blk._bn2)
                             if b is not None and b.num_batches_tracked is not None)
                 nxt = self.backbone._blocks[idx + 1] if idx + 1 < end else None          # (within the stage: its input IS this output)
-                x = T.mbconv_fused(tape, x, blk, keep, 1.0 - rate, fused["wt"][id(blk._depthwise_conv.weight)],
-                                   fused["dp"], lazy_in if idx == 0 else None, next_blk=nxt)
-            elif rng.get("_eval16") is not None and (blk.spec.sf_norm is None or K.fft_kernel_size(x.shape[1])):
-                # the fp16 runners' forward: half storage, eval-form BatchNorms, no statistics (an SF block on a map side
-                # with no in-register transform — 95 at 380 x 380 — takes the operator path below, in fp32 between two casts)
-                wt = rng["_eval16"][id(blk._depthwise_conv.weight)]
-                if tape is not None:
-                    # an fp16 gradient runner (unidefense_amd/attack.py): the same forward as ONE tape node with the frozen half backward
-                    x = T.mbconv_frozen_half(tape, x, blk, wt, lazy_in if idx == start else None)
-                else:
-                    x = T.mbconv_eval_half(x, blk, wt, lazy_in if idx == start else None, self.EVAL_NODE_H_MAX_CIN)
-            elif tape is None and not self.training and self.__dict__.get("_eval_fused") and self._eval_block_ok(blk):
+                x = MB.mbconv_fused(tape, x, blk, keep, 1.0 - rate, wt, mode.dp, lazy_in if idx == 0 else None, next_blk=nxt)
+            elif mode.kind == MB.HALF and sf_ok and tape is not None:
+                # an fp16 gradient runner (unidefense_amd/attack.py): the fp16 runners' forward (below) as ONE tape node with the
+                # frozen half backward
+                x = MB.mbconv_frozen_half(tape, x, blk, wt, lazy_in if idx == start else None)
+            elif mode.kind == MB.HALF and sf_ok:
+                # the fp16 runners' forward: half storage, eval-form BatchNorms, no statistics (the SF block left out above
+                # takes the operator path below, in fp32 between two casts)
+                x = MB.mbconv_eval_half(x, blk, wt, lazy_in if idx == start else None, self.EVAL_NODE_H_MAX_CIN)
+            elif mode.kind == MB.EVAL_NODE and MB.eval_block_ok(blk, type(self).EVAL_NODE_MAX_CIN):
                 # eval-mode node of an InferenceRunner's forward (unidefense_amd/infer.py): expand conv inside the depthwise pass
-                x = self._mbconv_eval(x, blk)
+                x = MB.mbconv_eval(x, blk, wt)
             else:
                 dt = x.dtype                                   # the operator path computes in fp32 storage
                 if dt != torch.float32:
@@ -601,9 +568,8 @@ class UniDefenseModelEb4(RunnerMethods, nn.Module):
         arch = self.arch
         bb = self.backbone
         st = arch["stem"]
-        pl, pr, pt, pb = st["pad"]
-        Ho = (H + pt + pb - 3) // 2 + 1
-        Wo = (W + pl + pr - 3) // 2 + 1
+        pl, pt = st["pad"][0], st["pad"][2]
+        Ho, Wo = T.conv_out_hw(H, W, 3, 2, st["pad"])
         rng = self._prepare_rng(rng, N, x.device)
         ws = [blk._depthwise_conv.weight for blk in bb._blocks]
         wts = K.dw_weights_tapmajor(ws)                                  # all depthwise weights to tap-major, one launch
@@ -622,33 +588,36 @@ class UniDefenseModelEb4(RunnerMethods, nn.Module):
         f32 = torch.float32
         if fused:
             dp = T.DataParallelCtx(self._sync_group(bb._bn0), getattr(self, "_bn_exchange", None))
-            rng["_fused"] = {"wt": wts, "dp": dp}
+            mode = MB.TrunkMode(MB.FUSED, wts, dp)
             if bb._bn0.num_batches_tracked is not None:
                 self.__dict__.setdefault("_nbt_pending", []).append(bb._bn0.num_batches_tracked)
-            h, lazy = T.stem_fused(tape, x_pix, bb._conv_stem.weight, bb._bn0, 2, pt, pl, Ho, Wo, dp,
+            h, lazy = MB.stem_fused(tape, x_pix, bb._conv_stem.weight, bb._bn0, 2, pt, pl, Ho, Wo, dp,
                                    torch.float16 if st16 else f32, x_planes=x_in)
-            x_b0 = self._blocks(tape, h, 0, rng, lazy)
+            x_b0 = self._blocks(tape, h, 0, rng, mode, lazy)
         elif ev16:
             # the stem conv's output rounded once to half; its eval BatchNorm + swish applied on load by block 0's depthwise conv
-            rng["_eval16"] = wts
+            mode = MB.TrunkMode(MB.HALF, wts)
             stem_bn = K.EvalBN(bb._bn0, 1)
             if tape is None:
                 h = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False).to(torch.float16)
-                x_b0 = self._blocks(tape, h, 0, rng, stem_bn)
+                x_b0 = self._blocks(tape, h, 0, rng, mode, stem_bn)
             else:
                 # recorded first, replayed last: block 0's depthwise pass hands back the gradient of the raw half stem output (already
                 # through the stem's eval BatchNorm + swish), the cast makes it fp32 and ud_stem_dgrad completes x.grad
                 h32 = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False, x_planes=x_in)
                 h = T.cast(tape, h32, torch.float16)
-                x_b0 = self._blocks(tape, h, 0, rng, T.LazyInput(stem_bn, lambda dh, h=h: tape.add_grad(h, dh)))
+                x_b0 = self._blocks(tape, h, 0, rng, mode, MB.LazyInput(stem_bn, lambda dh, h=h: tape.add_grad(h, dh)))
         else:
+            # an InferenceRunner's fp32 forward (unidefense_amd/infer.py) takes the eval node where it pays; else the operators
+            node = tape is None and not self.training and self.__dict__.get("_eval_fused")
+            mode = MB.TrunkMode(MB.EVAL_NODE if node else MB.OPERATORS, wts)
             h = T.conv_dense(tape, x_pix, bb._conv_stem.weight, 2, pt, pl, Ho, Wo, need_dx=False, x_planes=x_in)
             h = self._bn(tape, h, bb._bn0, 1)
-            x_b0 = self._blocks(tape, h, 0, rng)
-        x_b1 = self._blocks(tape, x_b0, 1, rng)
-        x_b2 = self._blocks(tape, x_b1, 2, rng)
-        x_b3 = self._blocks(tape, x_b2, 3, rng)
-        x_b4h = self._blocks(tape, x_b3, 4, rng)
+            x_b0 = self._blocks(tape, h, 0, rng, mode)
+        x_b1 = self._blocks(tape, x_b0, 1, rng, mode)
+        x_b2 = self._blocks(tape, x_b1, 2, rng, mode)
+        x_b3 = self._blocks(tape, x_b2, 3, rng, mode)
+        x_b4h = self._blocks(tape, x_b3, 4, rng, mode)
         x_b4 = T.cast(tape, x_b4h, f32)
 
         d_in = x_b4
@@ -666,9 +635,9 @@ class UniDefenseModelEb4(RunnerMethods, nn.Module):
         rec = T.bilinear(tape, dec3, H, W)
         spatial, freq = T.rec_losses(tape, rec, x, self.freq_norm)
 
-        x_b5 = T.cast(tape, self._blocks(tape, x_b4h, 5, rng), f32)
+        x_b5 = T.cast(tape, self._blocks(tape, x_b4h, 5, rng, mode), f32)
         att, freq_mask, spat_mask = self._attention(tape, dec3, x, x_b5, rng)
-        x_b6 = T.cast(tape, self._blocks(tape, T.cast(tape, att, torch.float16) if st16 else att, 6, rng), f32)
+        x_b6 = T.cast(tape, self._blocks(tape, T.cast(tape, att, torch.float16) if st16 else att, 6, rng, mode), f32)
 
         h = T.conv1x1(tape, x_b6, bb._conv_head.weight)
         h = self._bn(tape, h, bb._bn1, 1)

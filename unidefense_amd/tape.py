@@ -309,75 +309,13 @@ def linear(tape, x, w, b):
 # ---------------------------------------------------------------------------------------------
 # depthwise conv, FFT, SFConv
 # ---------------------------------------------------------------------------------------------
-# Stride-1 depthwise convs of the fused MBConv node on the LDS-tiled kernels of csrc/dwtile.hip (the deferred BatchNorm is
-# applied while the halo tile is staged: swish(bn0(e)) is never materialised) WHERE THEY WIN — measured per shape against
-# the strip kernels with tools/bench_dwtile.py on an MI355X (profiles/r03/dwtile_f32_bs32.txt, dwtile_f16_bs64.txt):
-#   half storage  : everywhere, by 1.3 - 3x (forward 109 -> 53, data gradient 260 -> 86, weight gradient 284 -> 106 us ...:
-#                   the strip kernels' per-tap 8-byte window loads and conversions);
-#   fp32 forward  : every block (one launch replaces bn_apply + conv + colstats of the plain blocks: 118 -> 74, 63 -> 43,
-#                   121 -> 52, 37 -> 23 us; SF blocks 43 -> 33, 31 -> 23 us) but the 5x5 / 8x8 maps (16 vs 14 us);
-#   fp32 data grad: 5x5 at 16x16 and 32x32 (70 -> 49, 45 -> 36 us) and 3x3 at 32x32 ... 64x64 (101 -> 94 us); the strip kernel
-#                   keeps the 8x8 and 128x128 maps;
-#   fp32 weight grad: the plain blocks (63 -> 54, 66 -> 55 us at 128^2 / 64^2; they have no materialised activation any
-#                   more); the SF blocks keep the strip kernel (36 vs 45, 23 vs 29 us) on the activation rfft2_ex writes.
-_DW_TILED = True
-
-
-# per-shape overrides of the two depthwise policies below, {(sf, k, stride, H, half): value}: measured IN the replayed step by
-# tools/tune_in_step.py --knobs (the rules come from per-kernel timings); empty = the rules
-_DW_TILE_OVERRIDE = {}
-_DW_BWD_FUSED_OVERRIDE = {}
-
-
-def _dw_tile_policy(sf, k, stride, H, half):
-    """(forward, weight gradient, data gradient) on the tiled kernels?"""
-    ov = _DW_TILE_OVERRIDE.get((bool(sf), k, stride, H, bool(half)))
-    if ov is not None and _DW_TILED:
-        return ov
-    return _dw_tile_rule(sf, k, stride, H, half)
-
-
-def _dw_tile_rule(sf, k, stride, H, half):
-    if not _DW_TILED:
-        return False, False, False
-    if stride == 2:
-        # the four down-sampling blocks (profiles/r03/dwtile_stride2.txt).  Data gradient through the zero-stuffed tile, with
-        # the BatchNorm sums in its epilogue instead of a pass of their own: 189 -> 88, 59 -> 40, 57 -> 32 us (fp32), but not
-        # on the 128 x 128 map in half storage (630 -> 699); forward 271 -> 130 us on the plain 128 x 128 block (incl. the
-        # BatchNorm apply + statistics passes it absorbs), otherwise only on the large maps; weight gradient: half storage
-        # (515 -> 177, 208 -> 100 us) and the plain block, the strip kernel elsewhere (49 vs 63 us)
-        if half:
-            return True, True, H < 128
-        return (not sf) or H >= 64, not sf, True
-    if half:
-        return True, True, True
-    fwd = not (k == 5 and H <= 8)
-    bwd = (k == 5 and H >= 16) or (k == 3 and 32 <= H <= 64)
-    return (fwd or not sf), not sf, bwd
-
-
-# Round 5: the stride-1 blocks' depthwise data gradient and weight gradient as ONE kernel (kernels.dwtile_bwd: both halo tiles
-# staged once; the separate kernels read dy and the conv's input twice each).  Where it is used: _dw_bwd_fused_policy.
-def _dw_bwd_fused_policy(sf, k, stride, H, half):
-    """data + weight gradient of this depthwise conv in one launch (csrc/dwtile.hip: dw_tile_bwd_kernel)?  Measured per shape
-    against the pair of kernels _dw_tile_policy picks (tools/bench_dwbwd.py on an MI355X, profiles/r05/dwbwd_*.txt; us, pair ->
-    fused): fp32 bs 32: 128^2 187 -> 151 and 74 -> 61, 32^2 k5 100 -> 81, 16^2 k5 70 -> 63, 16^2 k3 47 -> 45, 8^2 k3 47 -> 45;
-    NOT the 64^2 k3 blocks (132 vs 134: two halo tiles of a 16 x 8 tile are 1.4x its pixels, twice) and NOT the 8^2 k5 blocks
-    (48 vs 60: one workgroup per CU next to the strip kernels' eight).  Half storage bs 64: 328 -> 260, 90 -> 80, 224 -> 211,
-    163 -> 156, 73 -> 71; a tie at 16^2 k5 and 8^2 k3, 72 vs 96 at 8^2 k5."""
-    if stride != 1:
-        return False
-    ov = _DW_BWD_FUSED_OVERRIDE.get((bool(sf), k, stride, H, bool(half)))
-    if ov is not None:
-        return ov
-    if H <= 8:
-        return k == 3 and not half
-    if half:
-        return True
-    return not (k == 3 and H == 64)
-
-
 DW_WT = {}            # {id(w): (w, w._version, tap-major wt)} for the forward in flight (kernels.dw_weights_tapmajor)
+
+
+def conv_out_hw(H, W, k, stride, pad):
+    """(Ho, Wo) of a k x k conv over an H x W map zero-padded by pad = (left, right, top, bottom) as in nn.ZeroPad2d"""
+    pl, pr, pt, pb = pad
+    return (H + pt + pb - k) // stride + 1, (W + pl + pr - k) // stride + 1
 
 
 def dwconv(tape, x, w, stride, pad):
@@ -385,9 +323,8 @@ def dwconv(tape, x, w, stride, pad):
     pad = (left, right, top, bottom) as in nn.ZeroPad2d."""
     N, H, W, Cc = x.shape
     k = w.shape[-1]
-    pl, pr, pt, pb = pad
-    Ho = (H + pt + pb - k) // stride + 1
-    Wo = (W + pl + pr - k) // stride + 1
+    pl, pt = pad[0], pad[2]
+    Ho, Wo = conv_out_hw(H, W, k, stride, pad)
     ent = DW_WT.get(id(w))                      # tap-major copy made for all layers at once (model._run), if any
     if ent is not None and ent[0] is w and ent[1] == w._version:
         wt = ent[2]
@@ -1024,7 +961,8 @@ def concat_channels(tape, parts):
 
 
 # ---------------------------------------------------------------------------------------------
-# Fused MBConv block: deferred BatchNorm, one tape node per block (csrc/fused.hip)
+# What the block nodes of mbconv.py (one tape node per MBConv block) share with the model: the SyncBatchNorm context
+# of the fused path and the storage-type boundary of the half-storage trunk
 # ---------------------------------------------------------------------------------------------
 # bench.py's data-parallel diagnostics: when set to {"bn": [], "ar": []}, every SyncBN sum is bracketed by HIP events on its launch
 # stream — (start, end, doubles) — and GradReducer.finish() appends (backward end, last collective waited for, bytes, collectives)
@@ -1065,19 +1003,6 @@ class DataParallelCtx:
         return loc
 
 
-class LazyInput:
-    """A block input that is still a raw conv output + deferred BatchNorm (the stem in front of block 0):
-    backward(dz, sacc) receives the gradient already pushed through the activation and the BatchNorm sums."""
-
-    def __init__(self, bn, backward):
-        self.bn, self.backward = bn, backward
-
-
-def _bn_of(mod, acc, count, act):
-    return K.DeferredBN(acc, mod.num_features, count, mod.weight, mod.bias, mod.eps, act,
-                        mod.momentum if mod.momentum is not None else 0.1, mod.running_mean, mod.running_var)
-
-
 def cast(tape, x, dtype):
     """Storage-type boundary of the half-storage trunk (fp16 activations between the fp32 stem / decoder / attention /
     head): y = x.to(dtype), the gradient converted back."""
@@ -1091,568 +1016,3 @@ def cast(tape, x, dtype):
                 tape.add_grad(x, g.reshape(x.shape).to(x.dtype))
         tape.record(bwd)
     return y
-
-
-def stem_fused(tape, x_pix, w, bn_mod, stride, pad_t, pad_l, Ho, Wo, dp, storage=torch.float32, x_planes=None):
-    """Stem conv (model/efficientnet/model.py:185-186) whose BatchNorm + swish is left to block 0's depthwise conv.
-    storage: dtype the trunk keeps its activations in (torch.float16: the raw conv output is handed on rounded).
-    x_planes: the input image as planes (its gradient is formed when it is the tape's tracked input; conv_dense)."""
-    h32 = conv_dense(tape, x_pix, w, stride, pad_t, pad_l, Ho, Wo, need_dx=False, x_planes=x_planes)
-    h = h32 if storage == torch.float32 else h32.to(storage)
-    Cc = h.shape[-1]
-    M = h.numel() // Cc
-    acc = K.zeros64(2 * Cc, h)
-    K.colstats(h.view(M, Cc), acc)
-    dp.reduce(acc)
-    bn = _bn_of(bn_mod, acc, M * dp.world, 1)
-
-    def backward(dz, sacc, is_dz):
-        loc = dp.reduce(sacc, keep_local=True)
-        dh, dg, db = K.normbwd_apply(h, dz, None, 1.0, bn, is_dz, 1, M, sacc, loc)
-        tape.add_param_grad(bn_mod.weight, dg)
-        tape.add_param_grad(bn_mod.bias, db)
-        tape.add_grad(h32, dh if dh.dtype == h32.dtype else dh.to(h32.dtype))
-    return h, LazyInput(bn, backward)
-
-
-def mbconv_fused(tape, x, blk, keep, keep_prob, wt, dp, lazy_in=None, next_blk=None):
-    """MBConvBlock.forward (model/efficientnet/model.py:94-135) in training mode as ONE tape node.
-    x [N,H,W,Cin]: the block input (for block 0: the raw stem output, lazy_in its deferred BatchNorm);
-    wt: the depthwise weight in tap-major layout [k*k][C]; keep: drop-connect keep vector [N] or None.
-
-    Forward (SF block, stride 1):  expand GEMM -> colstats -> rfft2 of swish(bn0(e)) (also writes the activated
-    tensor) -> depthwise conv | spectral GEMM -> irfft2 + SF mix + BN1 statistics -> SE pooling of swish(bn1(d)) ->
-    2 small FCs -> BN1 + swish + gate -> project GEMM -> colstats -> BN2 + drop-connect + skip.
-    Backward mirrors it with the BatchNorm backward sums accumulated by the kernel that produces the gradient."""
-    sp = blk.spec
-    N, H, W, Cin = x.shape
-    M = N * H * W
-    k, stride = sp.k, sp.stride
-    pl, pr, pt, pb = sp.pad
-    Ho = (H + pt + pb - k) // stride + 1
-    Wo = (W + pl + pr - k) // stride + 1
-    HWo, Mo = Ho * Wo, N * Ho * Wo
-    Ce, Co = sp.cexp, sp.cout
-    inv_keep = 1.0 / keep_prob
-    dwm = blk._depthwise_conv
-    sf = sp.sf_norm is not None
-    assert not (sp.skip and lazy_in is not None)
-
-    # ---- expand + BN0 (deferred)
-    if sp.expand != 1:
-        We = blk._expand_conv.weight.view(Ce, Cin)
-        x2 = x.view(M, Cin)
-        acc0 = K.zeros64(2 * Ce, x)
-        xp = getattr(x, "_ud_planes", None)          # the previous block's residual pass wrote this conv's operand planes itself
-        if xp is not None and not (xp.R == M and xp.C == Cin and K.spectral_takes_planes(M, Ce, Cin, We, want_stats=True)):
-            xp = None
-        (e, done), ectx = K.spectral_fwd(x2 if xp is None else xp, We, stats=acc0, x_absmax=getattr(x, "_ud_absmax", None))          # BN0 statistics in the GEMM epilogue where the launch is plain
-        if not done:
-            K.colstats(e, acc0)
-        e = e.view(N, H, W, Ce)
-        dp.reduce(acc0)
-        bn0 = _bn_of(blk._bn0, acc0, M * dp.world, 1)
-        src, src_bn = e, bn0
-    else:
-        e = bn0 = None
-        src, src_bn = x, (lazy_in.bn if lazy_in is not None else None)
-
-    # ---- depthwise / SF conv -> d (pre-BN1), BN1 statistics
-    acc1 = K.zeros64(2 * Ce, x)
-    spat = fr = xf = None
-    if sf:
-        S = H
-        s_f, s_i = _fft_scales(S, sp.sf_norm)
-        alpha = dwm.sf_coef
-        t_fwd, t_wg, t_bwd = _dw_tile_policy(True, k, stride, H, x.dtype == torch.float16)
-        t_fused = _dw_bwd_fused_policy(True, k, stride, H, x.dtype == torch.float16)
-        Wf = dwm.freq_conv.weight.view(2 * Ce, 2 * Ce)
-        if src_bn is not None:
-            # a strip kernel needs a = swish(bn0(e)) materialised (rfft2_ex writes it); the tiled ones apply it on load
-            bwd_in_fft = K.irfft2_dwbwd_ok(S, k, stride, sp.pad, x.dtype)          # (the backward then needs no materialised a)
-            want_a = not (t_fwd and (t_wg or t_fused or bwd_in_fft))
-            if K.rfft2_planes_ok(src, src_bn) and K.spectral_takes_planes(N * S * (S // 2 + 1), 2 * Ce, 2 * Ce, Wf):
-                # the transform writes the spectral GEMM's fp16 x 2 planes itself (scale from an a-priori bound): no split pass —
-                # and, stride 1, the depthwise conv of the plane it holds anyway: no conv kernel either
-                if K.rfft2_dw_ok(S, k, stride, sp.pad):
-                    xf, a, spat = K.rfft2_ex_planes(src, s_f, 1.0, bn=src_bn, want_act=not (t_wg or t_fused or bwd_in_fft), update=True, dw_wt=wt,
-                                                    dw_k=k)
-                else:
-                    xf, a = K.rfft2_ex_planes(src, s_f, 1.0, bn=src_bn, want_act=want_a, update=True)
-            elif K.rfft2_plane_half_ok(src) and K.spectral_takes_plane_half(N * S * (S // 2 + 1), 2 * Ce, 2 * Ce):
-                # the mixed-precision mode: the half result laid into the prec-1 plane by the transform (no layout pass)
-                if K.rfft2_dw_ok(S, k, stride, sp.pad):
-                    xf, a, spat = K.rfft2_ex_plane_half(src, s_f, 1.0, bn=src_bn, want_act=not (t_wg or t_fused or bwd_in_fft),
-                                                        update=True, dw_wt=wt, dw_k=k)
-                else:
-                    xf, a = K.rfft2_ex_plane_half(src, s_f, 1.0, bn=src_bn, want_act=want_a, update=True)
-            else:
-                xf, a = K.rfft2_ex(src, s_f, 1.0, bn=src_bn, want_act=want_a, update=True, want_absmax=True)
-        else:
-            xf, a = K.rfft2(src, s_f, 1.0, want_absmax=True), src
-        if spat is not None:
-            pass
-        elif t_fwd:
-            spat = K.dwtile_fwd(src, wt, k, pt, pl, Ho, Wo, bn=src_bn, stride=stride)
-        else:
-            spat = K.dwconv_fwd(a, wt, k, stride, pt, pl, Ho, Wo)
-        xf_shape = (N, S, S // 2 + 1, 2 * Ce)
-        if isinstance(xf, K.Planes):
-            yf, sctx = K.spectral_fwd(xf, Wf)
-        else:
-            yf, sctx = K.spectral_fwd(xf.view(-1, 2 * Ce), Wf, x_absmax=getattr(xf, "_ud_absmax", None))
-        yf = yf.view(xf_shape)
-        xf = None          # the context holds what the backward needs of it
-        if stride == 1:
-            d, fr = K.irfft2_mix(yf, s_i, spat, alpha, acc1)          # fr: freq - spat (neither branch is kept)
-            spat = None
-        else:
-            fr = K.irfft2(yf, s_i, 1.0)
-            d = K.sfmix_fwd(spat, fr, alpha, True)
-            K.colstats(d.view(Mo, Ce), acc1)
-        del yf
-    else:
-        alpha = None
-        t_fwd, t_wg, t_bwd = _dw_tile_policy(False, k, stride, H, x.dtype == torch.float16)
-        t_fused = _dw_bwd_fused_policy(False, k, stride, H, x.dtype == torch.float16)
-        if t_fwd:
-            # halo tile staged in LDS with swish(bn0(e)) applied on the way in; BN1 statistics out of the epilogue
-            a = None
-            d = K.dwtile_fwd(src, wt, k, pt, pl, Ho, Wo, bn=src_bn, stats=acc1, update=True, stride=stride)
-        else:
-            # the strip kernel (and its weight gradient) re-reads its input per tap: materialise the activation
-            a = K.bn_apply(src, src_bn, 1, M, update=True) if src_bn is not None else src
-            d = K.dwconv_fwd(a, wt, k, stride, pt, pl, Ho, Wo)
-            K.colstats(d.view(Mo, Ce), acc1)
-    dp.reduce(acc1)
-    bn1 = _bn_of(blk._bn1, acc1, Mo * dp.world, 1)
-
-    # ---- squeeze-excite on swish(bn1(d)), BN1 + swish + gate -> c
-    Cs = sp.cse
-    wr2, we2 = blk._se_reduce.weight.view(Cs, Ce), blk._se_expand.weight.view(Ce, Cs)
-    pool = K.zeros64(N * Ce, x)
-    Wp = blk._project_conv.weight.view(Co, Ce)
-    # project conv on the planes GEMM: the gated tensor c is written as its planes by se_scale_bn itself, scaled by
-    # max |swish(bn1(d))| — which the SE squeeze pass leaves behind (kernels.colsum_bn_amax)
-    c_pl = (d.dtype == torch.float32 and Ce % 32 == 0 and cfg.spectral_p2 != "off"
-            and K.spectral_takes_planes(Mo, Co, Ce, Wp, want_stats=True))
-    if c_pl:
-        c_amax = K.colsum_bn_amax(d, bn1, N, HWo, pool, update=True)
-    else:
-        K.colsum_bn(d, bn1, N, HWo, pool, update=True)
-    s1 = K.fc_fwd_d(pool, 1.0 / HWo, wr2, blk._se_reduce.bias, N)
-    s2 = K.fc_fwd(s1, we2, blk._se_expand.bias, 1)
-
-    # ---- project + BN2 + drop-connect + skip
-    acc2 = K.zeros64(2 * Co, x)
-    if not c_pl and K.project_fwd_fused_ok(d, Wp, HWo):
-        # thin project conv (the 64 x 64 blocks): gate applied on load, BatchNorm-2 statistics out of the epilogue, c never written
-        # (its backward re-makes c as well: csrc/pjbwd.hip)
-        p, pctx = K.project_fwd_fused(d, bn1, s2, Wp, N, HWo, stats=acc2)
-        done = True
-    elif c_pl:
-        c = K.se_scale_bn_planes(d, bn1, s2, N, HWo, c_amax)
-        (p, done), pctx = K.spectral_fwd(c, Wp, stats=acc2)
-    elif (d.dtype == torch.float16 and Ce % 8 == 0 and K.spectral_takes_plane_half(Mo, Co, Ce)):
-        c = K.se_scale_bn_plane_half(d, bn1, s2, N, HWo)          # the mixed-precision mode: no row-major c, no layout pass
-        (p, done), pctx = K.spectral_fwd(c, Wp, stats=acc2)
-    else:
-        c = K.se_scale_bn(d, bn1, s2, N, HWo, want_absmax=True)
-        (p, done), pctx = K.spectral_fwd(c.view(Mo, Ce), Wp, stats=acc2, x_absmax=getattr(c, "_ud_absmax", None))
-    if not done:
-        K.colstats(p, acc2)
-    dp.reduce(acc2)
-    bn2 = _bn_of(blk._bn2, acc2, Mo * dp.world, 0)
-    p4 = p.view(N, Ho, Wo, Co)
-    # the block output is the next block's expand-conv operand: written as that GEMM's planes in the same pass where it takes them
-    nxt = None
-    if next_blk is not None and next_blk.spec.expand != 1:
-        nxt = (Mo, next_blk.spec.cexp, next_blk._expand_conv.weight.view(next_blk.spec.cexp, Co))
-    out = K.residual_bn(p4, bn2, keep, inv_keep, x if sp.skip else None, N, HWo, update=True, want_absmax=True, planes_for=nxt)
-    if not _needs(tape):
-        return out
-
-    def bwd():
-        dout = tape.pop_grad(out)
-        if dout is None:
-            return
-        if not (dout.is_contiguous() and dout.shape == out.shape):
-            dout = dout.reshape(out.shape).contiguous()
-        # ---- BN2 (+ drop-connect scale) backward
-        # the project conv's backward on the planes GEMM: the apply pass writes its operand's planes itself, scaled by the bound
-        # the sums pass leaves behind (the energy of the incoming gradient: a third sum)
-        dp_pl = K.normbwd_planes_ok(p4, pctx)          # (1: fp32, the energy bound as a third sum; 2: half storage, one plane)
-        sb2 = K.zeros64((3 if dp_pl == 1 else 2) * Co, x)
-        K.normbwd_sums(p4, dout, keep, inv_keep, bn2, False, N, HWo, sb2)
-        loc2 = dp.reduce(sb2, keep_local=True)
-        if dp_pl:
-            pctx.dy, dg2, db2 = K.normbwd_apply_planes(p4, dout, keep, inv_keep, bn2, False, N, HWo, sb2, loc2)
-            dp2, dp_amax = (dout if dp_pl == 2 else pctx.w.buf), None          # (device — and, half storage, dtype — for the launch wrappers)
-        else:
-            dp_, dg2, db2 = K.normbwd_apply(p4, dout, keep, inv_keep, bn2, False, N, HWo, sb2, loc2, want_absmax=True)
-            dp2, dp_amax = dp_.view(Mo, Co), getattr(dp_, "_ud_absmax", None)
-        tape.add_param_grad(blk._bn2.weight, dg2)
-        tape.add_param_grad(blk._bn2.bias, db2)
-        # thin project conv (the 64 x 64 blocks): its data gradient dc is never written — each of the two passes over d that need it
-        # re-makes its tile from the thin dp (csrc/pjbwd.hip)
-        pj_fused = not dp_pl and pctx.plans is None and K.project_bwd_fused_ok(d, Wp, HWo)
-        assert pj_fused or pctx.x is not None, "the fused project forward kept no gated tensor: its backward must be the fused one"
-        dgate = K.zeros64(N * Ce, x)
-        if pj_fused:
-            dWp = K.project_bwd_fused_a(d, bn1, s2, dp2, Wp, N, HWo, dgate)
-        else:
-            dc, dWp = K.spectral_bwd(pctx, dp2, dy_absmax=dp_amax)          # (one launch for both where that fills the chip better)
-            dc = dc.view(N, Ho, Wo, Ce)
-            K.coldot_bn(dc, d, bn1, N, HWo, dgate)
-        tape.add_param_grad(blk._project_conv.weight, dWp)
-        # ---- squeeze-excite backward
-        dpool, dWe2, dbe2, dWr, dbr = K.se_bwd(dgate, s2, s1, we2, wr2, pool, 1.0 / HWo)
-        tape.add_param_grad(blk._se_expand.weight, dWe2)
-        tape.add_param_grad(blk._se_expand.bias, dbe2)
-        tape.add_param_grad(blk._se_reduce.weight, dWr)
-        tape.add_param_grad(blk._se_reduce.bias, dbr)
-        # ---- gate + swish + BN1 backward sums in one pass
-        sb1 = K.zeros64(2 * Ce, x)
-        if pj_fused:
-            dz1 = K.project_bwd_fused_b(d, bn1, s2, dpool, 1.0 / HWo, dp2, Wp, N, HWo, sb1)
-        else:
-            dz1 = K.se_scale_bwd_bn(dc, d, bn1, s2, dpool, 1.0 / HWo, N, HWo, sb1)
-        loc1 = dp.reduce(sb1, keep_local=True)
-        g_alpha, g_mode, da_f = None, 0, None
-        if sf:
-            if stride == 1:
-                dacc = K.zeros64(64, x)
-                dyf_pl = sctx.plans is not None and K.rfft2_planes_ok(d, None)
-                en = K.zeros64(Ce, x) if dyf_pl else None
-                dd, dg1, db1 = K.normbwd_apply_mix(d, dz1, bn1, N, HWo, sb1, fr, dacc, loc1, energy=en)
-                # adjoint of irfft2, x sigmoid(a); the same launch turns the accumulator slots into the gate's gradient
-                if dyf_pl:
-                    # ... and writes the GEMMs' planes itself: scale from the energy of dd the apply pass just summed
-                    dyf, _, dalpha = K.rfft2_ex_planes(dd, s_i, 2.0, gate_alpha=alpha, gate_mode=1, gate_acc=dacc, energy=en)
-                elif sctx.plans is not None and K.rfft2_plane_half_ok(dd):
-                    dyf, _, dalpha = K.rfft2_ex_plane_half(dd, s_i, 2.0, gate_alpha=alpha, gate_mode=1, gate_acc=dacc)
-                else:
-                    dyf, _, dalpha = K.rfft2_ex(dd, s_i, 2.0, gate_alpha=alpha, gate_mode=1, gate_acc=dacc, want_absmax=True)
-                tape.add_param_grad(alpha, dalpha)
-                g_sp, g_alpha, g_mode = dd, alpha, 2                                   # spatial branch: x (1 - sigmoid(a))
-            else:
-                dd, dg1, db1 = K.normbwd_apply(d, dz1, None, 1.0, bn1, True, N, HWo, sb1, loc1)
-                g_sp, dfr, dalpha = K.sfmix_bwd(spat, fr, alpha, dd, True)
-                tape.add_param_grad(alpha, dalpha)
-                dyf = K.rfft2(dfr, s_i, 2.0, want_absmax=True)
-            if isinstance(dyf, K.Planes):
-                sctx.dy = dyf                                          # the products' dy operand, already in planes
-                # (a tensor of the right device — and, half storage, of the results' dtype — for the launch wrappers)
-                dyf2, dyf_amax = (dd if dyf.prec == 1 else sctx.w.buf), None
-            else:
-                dyf2, dyf_amax = dyf.view(-1, 2 * Ce), getattr(dyf, "_ud_absmax", None)
-            dxf, dWf = K.spectral_bwd(sctx, dyf2, dy_absmax=dyf_amax)
-            tape.add_param_grad(dwm.freq_conv.weight, dWf)
-            dxf = dxf.view(xf_shape)
-            # 8 x 8 maps: the adjoint transform's kernel also does the depthwise conv's backward over the planes it holds
-            irdw = src_bn is not None and K.irfft2_dwbwd_ok(S, k, stride, sp.pad, x.dtype)
-            if not irdw:
-                da_f = K.irfft2(dxf, s_f, 0.5)                                         # adjoint of rfft2
-        else:
-            dd, dg1, db1 = K.normbwd_apply(d, dz1, None, 1.0, bn1, True, N, HWo, sb1, loc1)
-            g_sp = dd
-        tape.add_param_grad(blk._bn1.weight, dg1)
-        tape.add_param_grad(blk._bn1.bias, db1)
-        dz0 = dw_f = None
-        de_pl = False
-        if sf and irdw:
-            # (+ the energy of dz0 where the expand conv's backward takes its operand as planes: K.normbwd_apply_planes below)
-            de_pl = K.normbwd_planes_ok(src, ectx) if lazy_in is None else 0
-            sb0 = K.zeros64((3 if de_pl == 1 else 2) * src.shape[-1], x)
-            dz0, dw_f = K.irfft2_dwbwd(dxf, s_f, 0.5, g_sp, src, src_bn, wt, k, g_alpha, g_mode, sb0)
-            is_dz = True
-            tape.add_param_grad(dwm.weight, dw_f)
-        elif t_fused:
-            # ---- depthwise data + weight gradient in one pass over (dd, src)
-            if src_bn is not None:
-                sb0 = K.zeros64(2 * src.shape[-1], x)
-                dz0, dw_f = K.dwtile_bwd(g_sp, src, wt, k, pt, pl, bn=src_bn, gate_alpha=g_alpha, gate_mode=g_mode, add=da_f,
-                                         sacc=sb0)
-                is_dz = True
-            else:
-                add = da_f
-                if sp.skip and add is None:
-                    add, skip_done = dout, True
-                else:
-                    skip_done = not sp.skip
-                dx, dw_f = K.dwtile_bwd(g_sp, src, wt, k, pt, pl, gate_alpha=g_alpha, gate_mode=g_mode, add=add)
-            tape.add_param_grad(dwm.weight, dw_f)
-        elif t_wg:
-            tape.add_param_grad(dwm.weight, K.dwtile_bwd_weight(src, g_sp, k, pt, pl, bn=src_bn, gate_alpha=g_alpha,
-                                                                gate_mode=g_mode, stride=stride))
-        else:
-            tape.add_param_grad(dwm.weight, K.dwconv_bwd_weight_ex(a, g_sp, g_alpha, g_mode, k, stride, pt, pl))
-        # ---- depthwise data gradient (+ spectral branch), through swish(bn0(.)) when the input is deferred
-        if src_bn is not None:
-            if dz0 is not None:
-                pass                                       # the fused kernel above made dz0 and the BatchNorm sums
-            elif t_bwd:
-                sb0 = K.zeros64(2 * src.shape[-1], x)
-                dz0 = K.dwtile_bwd_data(g_sp, wt, k, pt, pl, H, W, g_alpha, g_mode, da_f, src, src_bn, sb0, stride=stride)
-                is_dz = True
-            elif stride == 1:
-                sb0 = K.zeros64(2 * src.shape[-1], x)
-                dz0 = K.dwconv_bwd_data_bn(g_sp, g_alpha, g_mode, wt, da_f, src, src_bn, k, stride, pt, pl, sb0)
-                is_dz = True
-            else:       # stride 2 (4 of 32 blocks): gather kernel, then the sums as a pass of their own
-                sb0 = K.zeros64(2 * src.shape[-1], x)
-                dz0 = K.dwconv_bwd_data(g_sp, wt, k, stride, pt, pl, H, W, add=da_f)
-                K.normbwd_sums(src, dz0, None, 1.0, src_bn, False, 1, M, sb0)
-                is_dz = False
-            if lazy_in is not None:
-                lazy_in.backward(dz0, sb0, is_dz)
-                return
-            loc0 = dp.reduce(sb0, keep_local=True)
-            if not de_pl and x.dtype == torch.float16 and sp.expand != 1 and K.normbwd_planes_ok(e, ectx) == 2:
-                de_pl = 2          # half storage: the plane needs no bound, whichever kernel produced dz0
-            if not de_pl and sp.expand != 1 and ectx.plans is None and K.expand_bwd_fused_ok(e, ectx.w, is_dz):
-                # thin expand conv (the 128 x 128 / 64 x 64 blocks): BatchNorm backward + both gradients in ONE pass over (dz0, e)
-                add = dout.view(M, Cin) if (sp.skip and tape.watch is None and getattr(dout, "_ud_owned", False)) else None
-                dx, dWe, dg0, db0 = K.expand_bwd_fused(e, dz0, bn0, sb0, loc0, ectx.x, ectx.w, add=add)
-                dx = dx.view(x.shape)
-                if sp.skip and add is None:
-                    dx = K.axpby(dx, 1.0, dout, 1.0, out=dx)
-                tape.add_param_grad(blk._bn0.weight, dg0)
-                tape.add_param_grad(blk._bn0.bias, db0)
-                tape.add_param_grad(blk._expand_conv.weight, dWe)
-                dx._ud_owned = True
-                tape.add_grad(x, dx)
-                return
-            if de_pl:
-                ectx.dy, dg0, db0 = K.normbwd_apply_planes(e, dz0, None, 1.0, bn0, is_dz, 1, M, sb0, loc0)
-                de2, de_amax = (dz0 if de_pl == 2 else ectx.w.buf), None
-            else:
-                de, dg0, db0 = K.normbwd_apply(e, dz0, None, 1.0, bn0, is_dz, 1, M, sb0, loc0, want_absmax=True)
-                de2, de_amax = de.view(M, Ce), getattr(de, "_ud_absmax", None)
-            tape.add_param_grad(blk._bn0.weight, dg0)
-            tape.add_param_grad(blk._bn0.bias, db0)
-            if sp.skip and tape.watch is None and getattr(dout, "_ud_owned", False):
-                dx, dWe = K.spectral_bwd(ectx, de2, out=dout.view(M, Cin), dy_absmax=de_amax)    # + skip gradient
-                dx = dx.view(x.shape)
-            else:
-                dx, dWe = K.spectral_bwd(ectx, de2, dy_absmax=de_amax)
-                dx = dx.view(x.shape)
-                if sp.skip:
-                    dx = K.axpby(dx, 1.0, dout, 1.0, out=dx)
-            tape.add_param_grad(blk._expand_conv.weight, dWe)
-        else:
-            if dw_f is None:
-                add = da_f
-                if sp.skip and add is None:
-                    add, skip_done = dout, True
-                else:
-                    skip_done = not sp.skip
-                if t_bwd:
-                    dx = K.dwtile_bwd_data(g_sp, wt, k, pt, pl, H, W, g_alpha, g_mode, add, stride=stride)
-                else:
-                    dx = K.dwconv_bwd_data_ex(g_sp, g_alpha, g_mode, wt, add, k, stride, pt, pl, H, W)
-            if not skip_done:
-                dx = K.axpby(dx, 1.0, dout, 1.0, out=dx)
-        dx._ud_owned = True
-        tape.add_grad(x, dx)
-    tape.record(bwd)
-    return out
-
-
-def mbconv_eval_half(x, blk, wt, lazy_bn=None, node_max_cin=0):
-    """MBConvBlock.forward in eval mode, half storage (the fp16 InferenceRunner, unidefense_amd/infer.py): the forward of
-    mbconv_fused with every BatchNorm in the eval form (kernels.EvalBN: the running buffers, read in place) and no batch
-    statistics anywhere — no accumulator is handed to a producer and ud_colstats is never launched.  No tape.
-    x [N,H,W,Cin] fp16 (for block 0: the raw stem output, lazy_bn its eval BatchNorm + swish, applied on load);
-    wt: the depthwise weight tap-major [k*k][C].  Activations are stored as fp16, computed in fp32 registers; the 1x1 convs
-    are fp16 MFMA products with fp32 accumulation, selected per GEMM descriptor by the half operands (ud_gemm_desc.half_mask),
-    the fp32 weights converted as the kernel loads them.
-    node_max_cin: an expanding non-SF block with at most this many input channels takes the half-storage eval node instead
-    (ud_mb_eval_dw_h: expand conv on fp16 MFMA + BN0 + swish + depthwise + SE squeeze in one pass; e is never written)."""
-    sp = blk.spec
-    N, H, W, Cin = x.shape
-    M = N * H * W
-    k, stride = sp.k, sp.stride
-    pl, pr, pt, pb = sp.pad
-    Ho = (H + pt + pb - k) // stride + 1
-    Wo = (W + pl + pr - k) // stride + 1
-    HWo, Mo = Ho * Wo, N * Ho * Wo
-    Ce, Co = sp.cexp, sp.cout
-    assert x.dtype == torch.float16 and not (sp.skip and lazy_bn is not None)
-    bn1 = K.EvalBN(blk._bn1, 1)
-    if (sp.expand != 1 and sp.sf_norm is None and Cin <= node_max_cin and K.mb_eval_dw_h_ok(Cin, Ce, k, stride)):
-        # d raw (BN1 + swish applied on load by se_scale_bn); pool: the mean of swish(bn1(.)) of the stored values
-        d, pmean = K.mb_eval_dw_h(x, blk._expand_conv.weight.view(Ce, Cin), K.EvalBN(blk._bn0, 1), wt, bn1, k, stride, pt, pl, Ho,
-                                  Wo, out_act=False)
-        s1 = K.fc_fwd(pmean, blk._se_reduce.weight.view(sp.cse, Ce), blk._se_reduce.bias, 0)
-        return _eval_half_tail(x, blk, d, bn1, s1, N, HWo, Mo)
-    if sp.expand != 1:
-        e = K.gemm_nt(x.view(M, Cin), blk._expand_conv.weight.view(Ce, Cin))
-        src, src_bn = e.view(N, H, W, Ce), K.EvalBN(blk._bn0, 1)
-    else:
-        src, src_bn = x, lazy_bn
-    # depthwise conv of act(bn0(e)) from LDS halo tiles (the activation applied on load); SF blocks: the transform of the
-    # same activated tensor, the spectral 1x1 conv, and the inverse transform mixed with the spatial branch
-    spat = K.dwtile_fwd(src, wt, k, pt, pl, Ho, Wo, bn=src_bn, stride=stride)
-    if sp.sf_norm is not None:
-        S = H
-        s_f, s_i = _fft_scales(S, sp.sf_norm)
-        dwm = blk._depthwise_conv
-        xf, _ = K.rfft2_ex(src, s_f, 1.0, bn=src_bn)
-        yf = K.gemm_nt(xf.view(-1, 2 * Ce), dwm.freq_conv.weight.view(2 * Ce, 2 * Ce)).view(xf.shape)
-        if stride == 1:
-            d, _ = K.irfft2_mix(yf, s_i, spat, dwm.sf_coef, None)
-        else:
-            d = K.sfmix_fwd(spat, K.irfft2(yf, s_i, 1.0), dwm.sf_coef, True)
-    else:
-        d = spat
-    # squeeze-excite on swish(bn1(d)), then the gated tensor -> project conv -> BN2 (+ skip)
-    pool = K.zeros64(N * Ce, x)
-    K.colsum_bn(d, bn1, N, HWo, pool)
-    s1 = K.fc_fwd_d(pool, 1.0 / HWo, blk._se_reduce.weight.view(sp.cse, Ce), blk._se_reduce.bias, N)
-    return _eval_half_tail(x, blk, d, bn1, s1, N, HWo, Mo)
-
-
-def _eval_half_tail(x, blk, d, bn1, s1, N, HWo, Mo):
-    """the rest of mbconv_eval_half after the SE squeeze's first FC: gate, project conv, BN2 (+ skip)"""
-    sp = blk.spec
-    Ce, Co = sp.cexp, sp.cout
-    Ho, Wo = d.shape[1], d.shape[2]
-    s2 = K.fc_fwd(s1, blk._se_expand.weight.view(Ce, sp.cse), blk._se_expand.bias, 1)
-    c = K.se_scale_bn(d, bn1, s2, N, HWo)
-    p = K.gemm_nt(c.view(Mo, Ce), blk._project_conv.weight.view(Co, Ce))
-    return K.residual_bn(p.view(N, Ho, Wo, Co), K.EvalBN(blk._bn2, 0), None, 1.0, x if sp.skip else None, N, HWo)
-
-
-# measurement hook of the frozen half backward: a callable (block's parameter container, name, half tensor) called for every half
-# gradient tensor the node stores (tests and DESIGN 3l record the largest scaled magnitude against fp16's 65504 with it); None: off
-HALF_GRAD_PROBE = None
-
-
-def mbconv_frozen_half(tape, x, blk, wt, lazy_in=None):
-    """MBConvBlock.forward in eval mode, half storage, as ONE tape node whose backward is the FROZEN one (the fp16 InputGradRunner /
-    AttackRunner, unidefense_amd/attack.py): data gradients only, through eval-form BatchNorms.
-
-    Forward: mbconv_eval_half's composed kernels in the same order (the outputs are bitwise the fp16 InferenceRunner's).  Kept for
-    the backward: e (raw expand output), d (raw depthwise / SF output), s1, s2 — not the gated tensor, the spectra, the two SF
-    branches or any activated tensor.
-    Backward (half storage, fp32 registers; an eval BatchNorm's backward is the per-channel constant gamma invstd, folded into the
-    kernel that makes the gradient — no sums, no apply pass, no fp64 accumulators but the SE gate's):
-      dp = gamma2 invstd2 dout (ud_bn_eval_bwd, the thin tensor) -> dc = dp @ Wp (half GEMM) -> dgate = sum_hw dc swish(bn1(d))
-      (ud_coldot_bn_eval) -> the SE FCs' data gradient (ud_se_bwd_a / _b without their weight-gradient workgroups) ->
-      dd = (dc sigmoid(s2) + dpool / HW) swish'(bn1(d)) gamma1 invstd1 (ud_se_scale_bwd_bn_eval) -> SF: the adjoint transforms
-      around the spectral data-gradient GEMM, the gate applied by ud_rfft2_ex (frequency) and the dgrad kernel (spatial) ->
-      de = (gate dwconv^T(dd) + da_f) swish'(bn0(e)) gamma0 invstd0 (ud_dwtile_dgrad_eval) -> dx = de @ We (+ the skip gradient).
-    x [N,H,W,Cin] fp16; for block 0: the raw half stem output, lazy_in = LazyInput(the stem's EvalBN, backward(dh))."""
-    if tape.wgrad_on:
-        raise RuntimeError("mbconv_frozen_half is the backward of a FROZEN model (no parameter requires a gradient): it forms no "
-                           "weight gradient; a half-storage backward with trainable parameters is the training step's")
-    sp = blk.spec
-    N, H, W, Cin = x.shape
-    M = N * H * W
-    k, stride = sp.k, sp.stride
-    pl, pr, pt, pb = sp.pad
-    Ho = (H + pt + pb - k) // stride + 1
-    Wo = (W + pl + pr - k) // stride + 1
-    HWo, Mo = Ho * Wo, N * Ho * Wo
-    Ce, Co, Cs = sp.cexp, sp.cout, sp.cse
-    assert x.dtype == torch.float16 and not (sp.skip and lazy_in is not None)
-    dwm = blk._depthwise_conv
-    sf = sp.sf_norm is not None
-    bn1 = K.EvalBN(blk._bn1, 1)
-    bn2 = K.EvalBN(blk._bn2, 0)
-    if sp.expand != 1:
-        We = blk._expand_conv.weight.view(Ce, Cin)
-        e = K.gemm_nt(x.view(M, Cin), We).view(N, H, W, Ce)
-        src, src_bn = e, K.EvalBN(blk._bn0, 1)
-    else:
-        We = None
-        src, src_bn = x, (lazy_in.bn if lazy_in is not None else None)
-    spat = K.dwtile_fwd(src, wt, k, pt, pl, Ho, Wo, bn=src_bn, stride=stride)
-    if sf:
-        S = H
-        s_f, s_i = _fft_scales(S, sp.sf_norm)
-        alpha = dwm.sf_coef
-        Wf = dwm.freq_conv.weight.view(2 * Ce, 2 * Ce)
-        xf, _ = K.rfft2_ex(src, s_f, 1.0, bn=src_bn)
-        xf_shape = xf.shape
-        yf = K.gemm_nt(xf.view(-1, 2 * Ce), Wf).view(xf_shape)
-        if stride == 1:
-            d, _ = K.irfft2_mix(yf, s_i, spat, alpha, None)
-        else:
-            d = K.sfmix_fwd(spat, K.irfft2(yf, s_i, 1.0), alpha, True)
-        del xf, yf, spat
-    else:
-        d = spat
-    pool = K.zeros64(N * Ce, x)
-    K.colsum_bn(d, bn1, N, HWo, pool)
-    wr2, we2 = blk._se_reduce.weight.view(Cs, Ce), blk._se_expand.weight.view(Ce, Cs)
-    s1 = K.fc_fwd_d(pool, 1.0 / HWo, wr2, blk._se_reduce.bias, N)
-    s2 = K.fc_fwd(s1, we2, blk._se_expand.bias, 1)
-    Wp = blk._project_conv.weight.view(Co, Ce)
-    p = K.gemm_nt(K.se_scale_bn(d, bn1, s2, N, HWo).view(Mo, Ce), Wp)
-    out = K.residual_bn(p.view(N, Ho, Wo, Co), bn2, None, 1.0, x if sp.skip else None, N, HWo)
-    del pool, p
-
-    def bwd():
-        dout = tape.pop_grad(out)
-        if dout is None:
-            return
-        if not (dout.is_contiguous() and dout.shape == out.shape):
-            dout = dout.reshape(out.shape).contiguous()
-        assert dout.dtype == torch.float16
-        # ---- BN2: the constant applied in a pass over the thin tensor; project conv's data gradient on the half GEMM
-        probe = HALF_GRAD_PROBE
-        dp = K.bn_eval_bwd(dout, None, bn2, 1, Mo)
-        dc = K.gemm_nn(dp.view(Mo, Co), Wp).view(N, Ho, Wo, Ce)
-        if probe is not None:
-            for nm, t in (("dout", dout), ("dp", dp), ("dc", dc)):
-                probe(blk, nm, t)
-        # ---- SE gate, the two FCs (data gradient only), then gate + swish + BN1 in one pass over (dc, d)
-        dgate = K.zeros64(N * Ce, x)
-        K.coldot_bn_eval(dc, d, bn1, N, HWo, dgate)
-        dpool = K.se_bwd(dgate, s2, s1, we2, wr2, None, 1.0 / HWo, need_w=False)[0]
-        dd = K.se_scale_bwd_bn_eval(dc, d, bn1, s2, dpool, 1.0 / HWo, N, HWo)
-        del dc
-        if probe is not None:
-            probe(blk, "dd", dd)
-        # ---- SF: frequency branch sigmoid(a) dd through the adjoint transforms and the spectral data-gradient GEMM (stride 2:
-        # through the 2 x 2 mean first); spatial branch (1 - sigmoid(a)) dd by the dgrad kernel's gate mode 2; the gate is frozen
-        g_alpha, g_mode, da_f = None, 0, None
-        if sf:
-            dfr = dd if stride == 1 else K.sfmix_pool_bwd(dd)
-            dyf, _ = K.rfft2_ex(dfr, s_i, 2.0, gate_alpha=alpha, gate_mode=1)
-            dxf = K.gemm_nn(dyf.view(-1, 2 * Ce), Wf).view(xf_shape)
-            da_f = K.irfft2(dxf, s_f, 0.5)
-            if probe is not None:
-                for nm, t in (("dyf", dyf), ("dxf", dxf), ("da_f", da_f)):
-                    probe(blk, nm, t)
-            del dfr, dyf, dxf
-            g_alpha, g_mode = alpha, 2
-        # ---- depthwise data gradient through BN0 (block 0: the stem's BatchNorm) + swish in one tiled pass, then the expand conv
-        if src_bn is not None:
-            de = K.dwtile_dgrad_eval(dd, wt, k, pt, pl, src, src_bn, g_alpha, g_mode, da_f, stride)
-            if probe is not None:
-                probe(blk, "de", de)
-            if lazy_in is not None:
-                lazy_in.backward(de)
-                return
-            if sp.skip and tape.watch is None and getattr(dout, "_ud_owned", False):
-                dx = K.gemm_nn(de.view(M, Ce), We, out=dout.view(M, Cin), accumulate=True).view(x.shape)      # + the skip gradient
-            else:
-                dx = K.gemm_nn(de.view(M, Ce), We).view(x.shape)
-                if sp.skip:
-                    dx = K.axpby(dx, 1.0, dout, 1.0, out=dx)
-        else:
-            add, skip_done = da_f, not sp.skip
-            if sp.skip and add is None:
-                add, skip_done = dout, True
-            dx = K.dwtile_bwd_data(dd, wt, k, pt, pl, H, W, g_alpha, g_mode, add, stride=stride)
-            if not skip_done:
-                dx = K.axpby(dx, 1.0, dout, 1.0, out=dx)
-        if probe is not None:
-            probe(blk, "dx", dx)
-        dx._ud_owned = True
-        tape.add_grad(x, dx)
-    tape.record(bwd)
-    return out
