@@ -785,6 +785,35 @@ int ud_warp_affine(const float* x, float* out, const float* lut, const int* mat,
                    int border, ud_stream_t stream);
 int ud_spatial_control(const float* f, int* ist, float* fst, float* history, int K, int N, int closing, ud_stream_t stream);
 
+/* ---- universal perturbation (csrc/universal.hip; unidefense_amd/universal.py: UniversalRunner) -----------------------------
+ * ONE pattern delta [per] fp32 shared by all N samples of contiguous fp32 [N][per] batches; an iteration is a static launch
+ * sequence inside a captured graph: forward + d/dx, control, reduce, update.
+ * ud_uap_control: one thread per sample.  ist [1][N] int32, row UD_UAP_I_K: the sample's iteration counter (the caller zeroes it
+ *   to start a run).  With k = ist[K][n] in [0, steps): history[k][n] = f[n] (fp32 [steps][N]);
+ *   w[n] = (f[n] < beta) && (source < 0 || y[n] == source) as 0 / 1 (int32 [N]; y int64 [N]; a NaN f gives 0; beta = +inf counts
+ *   everyone); counted[k][n] = w[n] (int32 [steps][N]); ist[K][n] = k + 1.  k outside [0, steps) writes nothing.
+ * ud_uap_reduce: gsum[e] = sum over n with w[n] != 0 of g[n][e], added in ascending n from 0.f, one fp32 add per term and no
+ *   fused multiply-add: a float32 loop on the host reproduces it to the bit.  An excluded sample's row is not read (its NaN
+ *   does not leak); a counted sample's NaN stays.  No sample counted: gsum = 0.  One thread per element, float4 per thread where
+ *   per % 4 == 0 and g, gsum are 16-byte aligned; no workspace.
+ * ud_uap_update_linf: one pass: delta[e] <- clamp(delta[e] + step sign(gsum[e]), -eps, eps), then for every n
+ *   x_adv[n][e] = clamp(x[n][e] + delta[e], lo, hi); one fp32 rounding per operation in this order (bitwise the torch fp32
+ *   expression), sign(0) = 0, a NaN in gsum becomes a NaN in delta at that element.
+ * ud_uap_apply: dss != NULL (one double, |delta|^2 from ud_sample_sumsq(delta, NULL, 1, per)): delta is first scaled in place
+ *   by min(1, eps / max(sqrt(dss[0]), 1e-12)), product formed in double and rounded once; a factor of exactly 1 leaves it
+ *   untouched.  Then x_adv[n][e] = clamp(x[n][e] + delta[e], lo, hi) for every n; dss == NULL: only that, delta is not written.
+ *   x_adv may be x itself (no other overlap).  The L2 step on delta itself is ud_sample_sumsq(gsum) + ud_attack_step_l2(delta, gsum, gss, 1, per, step).
+ * UD_EINVAL before any HIP call: a NULL pointer (but dss), N < 1 or > 65535, per < 1, steps < 1, steps N > 2^31 - 1, a NaN beta
+ * or step, eps < 0 or NaN, lo > hi or NaN. */
+#define UD_UAP_I_K 0
+int ud_uap_control(const float* f, const long long* y, int* w, int* ist, float* history, int* counted, int N, int steps,
+                   float beta, int source, ud_stream_t stream);
+int ud_uap_reduce(const float* g, const int* w, float* gsum, int N, long per, ud_stream_t stream);
+int ud_uap_update_linf(float* delta, const float* gsum, const float* x, float* x_adv, int N, long per, float step, float eps,
+                       float lo, float hi, ud_stream_t stream);
+int ud_uap_apply(float* delta, const double* dss, const float* x, float* x_adv, int N, long per, float eps, float lo, float hi,
+                 ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

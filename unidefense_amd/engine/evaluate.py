@@ -1,7 +1,7 @@
-"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial: one scoring forward, one batch
-source, one loop-and-gather, one metrics dictionary, and a table of test_robust's methods.  The Evaluator takes its model and
-iterator as arguments and imports nothing that loads the HIP library, so the stage rules run on the CPU against stubs
-(tests/test_evaluate_cpu.py).  What every stage keeps: its order inside a batch, who owns which generator, the sequence of
+"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal: one scoring
+forward, one batch source, one loop-and-gather, one metrics dictionary, and a table of test_robust's methods.  The Evaluator
+takes its model and iterator as arguments and imports nothing that loads the HIP library, so the stage rules run on the CPU
+against stubs (tests/test_evaluate_cpu.py, tests/test_universal_cpu.py).  What every stage keeps: its order inside a batch, who owns which generator, the sequence of
 gather_scores calls (each is a pair of collectives under data parallel), every refusal before the first launch, and no
 host-device synchronisation inside the batch loop — .cpu() / float() / bool() happen after it."""
 from functools import partial
@@ -27,16 +27,17 @@ class Evaluator:
         forward = self.net.inference_runner(x.shape[0], x.shape[-1], self.precision) if self.graphed else self.model
         return torch.softmax(forward(x)["cls_out"], 1)[:, 0]
 
-    def batches(self, n):
-        for step in range(1, n + 1):
+    def batches(self, n, first=1):
+        for step in range(first, first + n):
             xr, yr, xf, yf = self.iterator(step, self.batch, self.size, self.device)
             yield torch.cat([xr, xf], 0).contiguous(), torch.cat([yr, yf], 0)
 
-    def run(self, n, body):
-        """body(x, y) -> {name: per-sample tensor} for each of n batches -> {name: (all batches of all ranks, their labels)}.
-        One gather_scores per name, in the order body names them (engine/metrics.py: two device all_gathers each)."""
+    def run(self, n, body, first=1):
+        """body(x, y) -> {name: per-sample tensor} for each of n batches (the iterator's steps first .. first + n - 1) -> {name:
+        (all batches of all ranks, their labels)}.  One gather_scores per name, in the order body names them (engine/metrics.py:
+        two device all_gathers each)."""
         cols, labels = {}, []
-        for x, y in self.batches(n):
+        for x, y in self.batches(n, first):
             for name, t in body(x, y).items():
                 cols.setdefault(name, []).append(t)
             labels.append(y)
@@ -127,6 +128,53 @@ class Evaluator:
         args = dict(runner.args, best=torch.stack([cols[i][0] for i in range(5)], 1).cpu(),
                     fooled=float((cols["best_loss"][0][held] <= 0).double().mean()) if bool(held.any()) else float("nan"))
         return self._result(cols, "Test(spatial)", args)
+
+    def test_universal(self, batches, fit_batches, epochs, universal):
+        universal = dict(universal) if universal else {}
+        seed = universal.pop("seed", None)
+        for name, v in (("batches", batches), ("fit_batches", fit_batches), ("epochs", epochs)):
+            if not v >= 1 or int(v) != v:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            universal.setdefault("reduce", dist.all_reduce)      # every rank sums gsum in place: the same delta everywhere
+        try:                                             # ONE runner holds the pattern; every refusal before the first batch
+            runner = self.net.universal_runner(2 * self.batch, self.size, **universal)
+        except TypeError as e:                           # an unknown key is a bad dict, like a bad value
+            raise ValueError(f"universal takes UniversalRunner's keyword arguments and 'seed': {e}") from None
+        generator = None if seed is None else torch.Generator().manual_seed(int(seed))     # one CPU generator per call
+        runner.reset()
+        counted = []
+        for _ in range(int(epochs)):                     # the fit: the iterator's steps 1 .. fit_batches, epochs times over
+            for x, y in self.batches(int(fit_batches)):
+                runner(x, y)
+                counted.append(runner.counted.sum(1))
+        # the control, drawn once: a pattern of the same norm that was fitted on nothing
+        args = runner.args
+        delta, (lo, hi) = runner.delta, args["clip"]
+        if args["norm"] == "linf":
+            sign = torch.randint(0, 2, tuple(delta.shape), generator=generator).to(torch.float32) * 2.0 - 1.0
+            control = sign.to(delta.device) * args["eps"]
+        else:
+            z = torch.randn(tuple(delta.shape), generator=generator, dtype=torch.float32).to(delta.device)
+            control = z * (delta.norm() / z.norm().clamp_min(1e-12))
+
+        def body(x, y):                                  # the held-out steps, scored three ways, gathered in this order
+            return {"clean": self.score(x), "adv": self.score(runner.apply(x)),
+                    "control": self.score((x + control).clamp_(lo, hi))}
+
+        cols = self.run(int(batches), body, first=int(fit_batches) + 1)
+        labels = cols["clean"][1]
+        right = (cols["clean"][0] < 0.5).long() == labels
+
+        def fooled(name):
+            wrong = (cols[name][0] < 0.5).long() != labels
+            return float(wrong[right].double().mean()) if bool(right.any()) else float("nan")
+
+        d = delta.detach().cpu()
+        args = dict(args, delta=d, linf=float(d.abs().max()), l2=float(d.double().norm()), fooled=fooled("adv"),
+                    fooled_control=fooled("control"), fit_counted=[int(c) for c in torch.cat(counted).cpu()])
+        return dict(self._result(cols, "Test(universal)", args), control=self.metrics(*cols["control"], "Test(control)"))
 
 
 # ---- test_robust's methods: ROBUST[method](ev, attack) refuses and resolves the dict (given without "method") and is the run:

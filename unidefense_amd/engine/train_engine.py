@@ -264,6 +264,22 @@ class TrainEngine(AbstractEngine):
         two losses are gathered over the ranks as in test()."""
         return self._evaluator().test_spatial(batches, spatial if spatial is not None else self.config["config"].get("spatial"))
 
+    def test_universal(self, batches=4, fit_batches=4, epochs=2, universal=None):
+        """What ONE pattern of size eps costs on data it was not fitted on (unidefense_amd/universal.py): the model's
+        UniversalRunner is reset and fitted on the test iterator's steps 1 .. fit_batches, `epochs` times over, with the true
+        labels; the held-out steps fit_batches + 1 .. fit_batches + batches are then scored as test() does (inference_graph /
+        inference_precision keep their meaning) three ways: clean, with the pattern (runner.apply), and with a control pattern
+        of the same norm fitted on nothing (linf: random +-eps; l2: a Gaussian scaled to |delta|_2), drawn once from a CPU
+        generator.  universal (default config['config']['universal']): the runner's keyword arguments, e.g. {"norm": "linf",
+        "eps": 4/255, "steps": 1}; an optional "seed" seeds the control's generator.  Returns {"clean", "adv", "control": what
+        test() returns, "attack": the resolved arguments plus "delta" (CPU [3, size, size]), "linf", "l2", "fooled" (the fraction
+        of the held-out samples classified correctly clean that the pattern flips; NaN where there are none), "fooled_control"
+        and "fit_counted" (the samples that steered each fit iteration, this rank's)}.  Under data parallel every rank's
+        gradient sum is all-reduced inside the iteration, so all ranks hold the same pattern; scores are gathered as in
+        test(), in the order clean, adv, control."""
+        universal = universal if universal is not None else self.config["config"].get("universal")
+        return self._evaluator().test_universal(batches, fit_batches, epochs, universal)
+
     def validate(self, step, batches=4):
         """The reference's validate (forgery_engine.py:320-421) without the figure / wandb plumbing: metrics over all
         ranks, best-so-far record (AUC + ACC), best_model.bin / latest_model.bin on rank 0."""

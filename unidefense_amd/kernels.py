@@ -1893,6 +1893,72 @@ def spatial_control(f, ist, fst, history, closing=False):
     _call("ud_spatial_control", _p(f), _p(ist), _p(fst), _p(history), history.shape[0], N, int(bool(closing)), _stream())
 
 
+# ---- universal perturbation (csrc/universal.hip): one pattern delta [per] for contiguous fp32 [N, ...] batches ----------------
+UAP_I = _rows("UD_UAP_I_")
+
+
+def uap_state(N, steps, device):
+    """(ist, w, history, counted): zeroed control state for N samples and `steps` iterations"""
+    return (torch.zeros(len(UAP_I), N, dtype=torch.int32, device=device), torch.zeros(N, dtype=torch.int32, device=device),
+            torch.zeros(steps, N, dtype=torch.float32, device=device), torch.zeros(steps, N, dtype=torch.int32, device=device))
+
+
+def _chk_pattern(delta, x, *more):
+    """delta (and `more`) hold one sample's elements of the batch x: (N, per)"""
+    _chk(delta, x, *more)
+    N = x.shape[0] if x.dim() >= 1 else 0
+    if N < 1 or x.numel() == 0 or any(t.numel() * N != x.numel() for t in (delta,) + more):
+        raise ValueError(f"a pattern holds one sample's elements: {[tuple(t.shape) for t in (delta,) + more]} for a batch "
+                         f"{tuple(x.shape)}")
+    return N, x.numel() // N
+
+
+def uap_control(f, y, w, ist, history, counted, beta, source=None):
+    """One step of the universal perturbation's per-sample control on f [N] fp32 with k = ist's counter: history[k] = f,
+    w = counted[k] = (f < beta) & (source is None or y == source), counter + 1; history and counted are [steps, N]."""
+    _chk(f, history)
+    N = f.numel()
+    if not (y.is_cuda and y.dtype == torch.int64 and y.is_contiguous() and tuple(y.shape) == (N,)):
+        raise ValueError(f"y must be a contiguous int64 CUDA tensor [{N}], got {y.dtype} {y.device} {tuple(y.shape)}")
+    if history.dim() != 2 or history.shape[0] < 1 or history.shape[1] != N:
+        raise ValueError(f"history must be [steps, {N}] with steps >= 1, got {tuple(history.shape)}")
+    _chk_i32(w, (N,), "w")
+    _chk_i32(ist, (len(UAP_I), N), "ist")
+    _chk_i32(counted, tuple(history.shape), "counted")
+    _call("ud_uap_control", _p(f), _p(y), _p(w), _p(ist), _p(history), _p(counted), N, history.shape[0], float(beta),
+          -1 if source is None else int(source), _stream())
+
+
+def uap_reduce(g, w, gsum):
+    """gsum[e] = sum over the samples n with w[n] != 0 of g[n, e], in ascending n with one fp32 add per term (bitwise a float32
+    host loop); an excluded sample is not read.  g [N, ...] fp32, w [N] int32, gsum one sample's elements."""
+    N, per = _chk_pattern(gsum, g)
+    _chk_i32(w, (N,), "w")
+    _call("ud_uap_reduce", _p(g), _p(w), _p(gsum), N, per, _stream())
+    return gsum
+
+
+def uap_update_linf(delta, gsum, x, x_adv, step, eps, lo, hi):
+    """In place: delta <- clamp(delta + step sign(gsum), -eps, eps), then x_adv[n] = clamp(x[n] + delta, lo, hi) for every n:
+    one pass, bitwise the torch fp32 expression; sign(0) = 0, a NaN in gsum becomes a NaN in delta."""
+    _chk_same(x, x_adv)
+    N, per = _chk_pattern(delta, x, gsum)
+    _call("ud_uap_update_linf", _p(delta), _p(gsum), _p(x), _p(x_adv), N, per, float(step), float(eps), float(lo), float(hi),
+          _stream())
+    return x_adv
+
+
+def uap_apply(delta, dss, x, x_adv, eps, lo, hi):
+    """x_adv[n] = clamp(x[n] + delta, lo, hi) for every n; dss (one float64, sample_sumsq of delta as [1, per]) given: delta is
+    first scaled in place by min(1, eps / max(sqrt(dss), 1e-12)) (exactly 1: untouched); dss None: delta is only read."""
+    _chk_same(x, x_adv)
+    N, per = _chk_pattern(delta, x)
+    if dss is not None:
+        _chk_f64(dss, 1)
+    _call("ud_uap_apply", _p(delta), _p(dss), _p(x), _p(x_adv), N, per, float(eps), float(lo), float(hi), _stream())
+    return x_adv
+
+
 def conv_gather_wgrad(a, x, g):
     """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)]."""
     _chk(a, x)

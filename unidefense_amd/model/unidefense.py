@@ -276,6 +276,13 @@ class RunnerMethods:
         from ..spatial import spatial_runner
         return spatial_runner(self, batch, size, **kwargs)
 
+    def universal_runner(self, batch, size, **kwargs):
+        """The graph-replayed universal perturbation — one pattern of size eps for every image, held by the runner across calls
+        — for [batch, 3, size, size] inputs (unidefense_amd/universal.py: UniversalRunner; kwargs: norm, eps, steps, step, beta,
+        source, clip, precision, grad_scale, reduce)."""
+        from ..universal import universal_runner
+        return universal_runner(self, batch, size, **kwargs)
+
 
 class UniDefenseModelEb4(RunnerMethods, nn.Module):
     """UniDefense model with EfficientNet backbone (reference: model/unidefense.py:28-256)."""
