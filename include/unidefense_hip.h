@@ -1033,6 +1033,31 @@ int ud_se_bwd_b(const double* ds1_acc, const float* s1, const float* Wr, const d
 int ud_se_scale_bwd_bn(const void* dc, const void* x, const ud_bn_ref* bn, const float* s, const float* dpool,
     float inv_hw, void* dz, double* s1, double* s2, double* ws, int G, int R, int C, int f16, ud_stream_t
     stream);
+/* ---- the same SE / BatchNorm-1 backward WITHOUT dz ever written: the BatchNorm sums from per-sample dots ----
+ * s1 = sum dz and s2 = sum dz xhat of dz = (dc g + p) act'(bn(x)), g = sigmoid(s[n][c]), p = dpool[n][c] inv_hw, are linear in
+ * the per-sample quantities (g, p):  s1[c] = sum_n (g A1[n][c] + p B1[n][c]),  s2[c] = sum_n (g A2[n][c] + p B2[n][c])  with
+ *   A1 = sum_hw dc act'(y)   A2 = sum_hw dc act'(y) xhat   B1 = sum_hw act'(y)   B2 = sum_hw act'(y) xhat   (y = bn(x)).
+ * fp32 storage only (f16 != 0: UD_EINVAL); training-form entry points: the eval form of ud_bn_ref is UD_EINVAL.
+ * ud_coldot_bn_se        : ud_coldot_bn that also sums the four dots: out [5][G][C] fp64, zeroed by the caller, receives
+ *                          (dgate, A1, A2, B1, B2).  One launch, fp64 atomics with at most 64 adds per address; no scratch.
+ * ud_se_bwd_b_bn         : ud_se_bwd_b whose (n, c) thread also adds g A + p B of its sample into bs1[c] / bs2[c] (fp64, zeroed by
+ *                          the caller; N adds per address).  s2: the gate's pre-activation [N][C]; dots: ud_coldot_bn_se's out.
+ *                          Same dpool / dWr / dbr as ud_se_bwd_b.
+ * ud_normbwd_apply_se    : ud_normbwd_apply whose second input is dc: dz is formed on load from (dc, x, s, dpool); s / dpool
+ *                          [G][C], one sample per group.  dx, dgamma, dbeta, absmax as ud_normbwd_apply.
+ * ud_normbwd_apply_mix_se: ud_normbwd_apply_mix likewise (dalpha_acc, energy as there). */
+int ud_coldot_bn_se(const void* dy, const void* x, const ud_bn_ref* bn, int G, int R, int C, double* out, int f16,
+                    ud_stream_t stream);
+int ud_se_bwd_b_bn(const double* ds1_acc, const float* s1, const float* Wr, const double* pool, float pool_scale,
+                   float* dpool, float* dWr, float* dbr, const float* s2, const double* dots, float inv_hw, double* bs1,
+                   double* bs2, int N, int C, int Cs, ud_stream_t stream);
+int ud_normbwd_apply_se(const void* x, const void* dc, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,
+                        const double* s1, const double* s2, const double* s1_local, const double* s2_local, int G, int R,
+                        int C, void* dx, float* dgamma, float* dbeta, int f16, uint32_t* absmax, ud_stream_t stream);
+int ud_normbwd_apply_mix_se(const void* x, const void* dc, const ud_bn_ref* bn, const float* s, const float* dpool,
+                            float inv_hw, const double* s1, const double* s2, const double* s1_local,
+                            const double* s2_local, const void* diff, int G, int R, int C, void* dd, double* dalpha_acc,
+                            float* dgamma, float* dbeta, double* energy, int f16, ud_stream_t stream);
 /* ---- frozen backward: the same steps through EVAL-FORM BatchNorms (required; UD_EINVAL for the training form) ----
  * ud_coldot_bn_eval      : out[g][c] += sum_r dy * act(bn(x)) (the SE gate's gradient; out zeroed by the caller).  Deterministic:
  *                          no atomic add is shared by two workgroups — one row-chunk per sample adds once into the zeroed slot,

@@ -58,6 +58,28 @@ __device__ __forceinline__ void red_out(const RedGeom& q, int ri, bool active, i
         }
     }
 }
+// Many quantities per column (NQ = 20: five quads), per-group accumulators out[NQ / 4][G][C]: ALL row lanes fold and add — thread
+// (ri, column) totals values ri, ri + rpi, ... of its column quad over the row lanes and adds them itself, where red_out's
+// single row lane would walk rpi x NQ LDS values and issue NQ atomics back to back.  LDS value-major: conflict-free both ways.
+template <int NQ>
+__device__ __forceinline__ void red_out_spread(const RedGeom& q, int ri, bool active, int c4, double (&v)[NQ], double* out) {
+    __shared__ double sm[NQ * NT];
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) sm[i * NT + threadIdx.x] = v[i];
+    }
+    __syncthreads();
+    if (!active) return;
+    const int col = (int)threadIdx.x - ri * q.CW;
+    const long plane = (long)q.G * q.C4 * 4;
+    const long o = ((long)blockIdx.z * q.C4 + c4) * 4;
+    for (int i = ri; i < NQ; i += q.rpi) {
+        const double* s = sm + i * NT + col;
+        double t = 0.0;
+        for (int r = 0; r < q.rpi; ++r) t += s[r * q.CW];
+        atomic_add_f64(out + (i >> 2) * plane + o + (i & 3), t);
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // statistics and lazy reductions
@@ -132,6 +154,48 @@ __global__ __launch_bounds__(NT) void colsum_bn_kernel(RedGeom q, const T* __res
     }
     red_out<4>(q, ri, active, c4, v, out, nullptr, part, true);
     if (!DOT) ud_absmax_commit(mo, amax);
+}
+
+// colsum_bn_kernel<T, true> with five quantities per (group, channel): besides the SE gate's dot, the four per-sample sums the
+// BatchNorm-1 backward sums are linear in — with y = bn(x), xhat and act' as se_scale_bwd_bn_kernel forms them,
+//   out[0] = sum_r dy act(y)      out[1] = A1 = sum_r dy act'(y)      out[2] = A2 = sum_r dy act'(y) xhat
+//                                 out[3] = B1 = sum_r act'(y)         out[4] = B2 = sum_r act'(y) xhat
+// (out: [5][G][C], plane stride G * C).  The term dy act'(y) is rounded to fp32 once, as the gradient it stands for is.
+template <typename T>
+__global__ __launch_bounds__(NT) void coldot_bn_se_kernel(RedGeom q, const T* __restrict__ x, const T* __restrict__ dy,
+                                                          ud_bn_ref bn, double* __restrict__ out) {
+    int ri, c4;
+    const bool active = thread_coords(q, ri, c4);
+    const In4<T> x4{x}, d4{dy};
+    double v[20];
+#pragma unroll
+    for (int i = 0; i < 20; ++i) v[i] = 0.0;
+    if (active) {
+        const BnRaw raw = bn_issue(bn, blockIdx.z, q.C4, c4);
+        Bn4 cb;
+        const Rows w = rows_of(q, ri, c4);
+        auto fin = [&]() UD_LAMBDA_INLINE { cb = bn_finish(bn, raw); };
+        act_switch(bn.act, [&](auto ac) UD_LAMBDA_INLINE {
+            constexpr int ACT = decltype(ac)::value;
+            const In4<T> in[2] = {x4, d4};
+            for_rows<T, 2>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long, int, const f32x4(&t)[2]) UD_LAMBDA_INLINE {
+                const f32x4 a = bn_apply<ACT>(t[0], cb);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float xh = (t[0][e] - cb.mu[e]) * cb.is[e];
+                    const float ap = ACT ? ud_act_grad_fast(cb.ga[e] * xh + cb.be[e], ACT) : 1.f;
+                    const double dyd = (double)t[1][e], xhd = (double)xh, apd = (double)ap;
+                    const double u = (double)mul_rn(t[1][e], ap);
+                    v[e] += dyd * (double)a[e];
+                    v[4 + e] += u;
+                    v[8 + e] += u * xhd;
+                    v[12 + e] += apd;
+                    v[16 + e] += apd * xhd;
+                }
+            });
+        });
+    }
+    red_out_spread<20>(q, ri, active, c4, v, out);
 }
 
 // y[n][o] = sum_i (xsum[n][i] * xscale) W[o][i] + b[o]; one wave per output
@@ -403,25 +467,39 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(RedGeom q, const T* __rest
 // BatchNorm backward
 // ---------------------------------------------------------------------------------------------------------
 // MODE: kDz = the incoming gradient IS dz; 0 / 1 / 2 = it is dy of act(bn(x)) (times the drop-connect factor sc)
+// kSe + act (act = 0 / 1 / 2): the incoming gradient is dc, the gradient of the SE-gated tensor, and dz is formed from it on the
+// fly as se_scale_bwd_bn_kernel forms it — dz = (dc g + p) act'(bn(x)), g = sigmoid(s[z][c]), p = dpool[z][c] inv_hw (SeGate)
 constexpr int kDz = -1;
+constexpr int kSe = 8;
+struct SeGate { f32x4 g, p; };
 template <int MODE>
-__device__ __forceinline__ void dz_terms(const f32x4& a, const f32x4& d, const Bn4& cb, float sc, f32x4& dz, f32x4& xh) {
+__device__ __forceinline__ void dz_terms(const f32x4& a, const f32x4& d, const Bn4& cb, float sc, f32x4& dz, f32x4& xh,
+                                         const SeGate& se = SeGate{}) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         xh[e] = (a[e] - cb.mu[e]) * cb.is[e];
         float g = d[e];
-        if (MODE != kDz) {          // (products rounded on their own: dz is what normbwd_sums summed)
+        if constexpr (MODE >= kSe) {
+            g = g * se.g[e] + se.p[e];
+            if (MODE - kSe) g *= ud_act_grad_fast(cb.ga[e] * xh[e] + cb.be[e], MODE - kSe);
+        } else if (MODE != kDz) {          // (products rounded on their own: dz is what normbwd_sums summed)
             g = mul_rn(g, sc);
             if (MODE) g = mul_rn(g, ud_act_grad_fast(cb.ga[e] * xh[e] + cb.be[e], MODE));
         }
         dz[e] = g;
     }
 }
-// f(ActC<MODE>{}) of dz_terms for the run-time pair (dy_is_dz, act): as act_switch
-template <typename F>
+// f(ActC<MODE>{}) of dz_terms for the run-time pair (dy_is_dz, act): as act_switch; SE: the gate modes kSe + act
+template <bool SE = false, typename F>
 __device__ __forceinline__ void dz_switch(int dy_is_dz, int act, F&& f) {
-    if (dy_is_dz) f(ActC<kDz>{});
-    else act_switch(act, f);
+    if constexpr (SE) {
+        if (act == 1) f(ActC<kSe + 1>{});
+        else if (act == 2) f(ActC<kSe + 2>{});
+        else f(ActC<kSe>{});
+    } else {
+        if (dy_is_dz) f(ActC<kDz>{});
+        else act_switch(act, f);
+    }
 }
 
 template <typename T>
@@ -487,7 +565,14 @@ struct PlanesDst {
 // MIX: also the SF-mix gradient: acc += dd * diff, diff = freq - spat as written by ud_irfft2_mix
 // PL = 2 (the mixed-precision mode, half storage): the half result itself laid into the P32 plane ud_gemm_p3 prec 1 reads (scale 1) —
 // the row-major tensor had no other reader than the layout pass.
-template <typename T, bool MIX, int PL = 0>
+// SE: dy is dc and dz is formed on the fly from the SE gate (dz_terms' kSe modes; se: s and dpool [G][C], one sample per group):
+// the BatchNorm-1 apply of the SE backward whose sums came from per-sample dots — dz is never stored
+struct SeSrc {
+    const float* s;
+    const float* dpool;
+    float inv_hw;
+};
+template <typename T, bool MIX, int PL = 0, bool SE = false>
 __global__ __launch_bounds__(NT) void normbwd_apply_kernel(RedGeom q, const T* __restrict__ x,
                                                            const T* __restrict__ dy, const float* __restrict__ keep,
                                                            float inv_keep, ud_bn_ref bn, int dy_is_dz,
@@ -497,14 +582,19 @@ __global__ __launch_bounds__(NT) void normbwd_apply_kernel(RedGeom q, const T* _
                                                            T* __restrict__ dx, double* __restrict__ dalpha_acc,
                                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                            uint32_t* __restrict__ amax, double* __restrict__ energy,
-                                                           PlanesDst pd) {
+                                                           PlanesDst pd, SeSrc se) {
     int ri, c4;
     const bool active = thread_coords(q, ri, c4);
     BnRaw raw{};
     double t1d[4] = {0, 0, 0, 0}, t2d[4] = {0, 0, 0, 0};
     float kraw = 0.f;
+    SeGate sg{};
     if (active) {          // in flight through the scale's scan below
         raw = bn_issue(bn, blockIdx.z, q.C4, c4);
+        if constexpr (SE) {
+            sg.g = reinterpret_cast<const f32x4*>(se.s)[(long)blockIdx.z * q.C4 + c4];
+            sg.p = reinterpret_cast<const f32x4*>(se.dpool)[(long)blockIdx.z * q.C4 + c4];
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) t1d[e] = s1[c4 * 4 + e];
 #pragma unroll
@@ -553,6 +643,11 @@ __global__ __launch_bounds__(NT) void normbwd_apply_kernel(RedGeom q, const T* _
             cb = bn_finish(bn, raw);
             if (keep) sc = kraw * inv_keep;
             k = cb.ga * cb.is;
+            if constexpr (SE) {
+                sg.p = sg.p * se.inv_hw;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sg.g[e] = ud_sigmoid_fast(sg.g[e]);
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 t1[e] = (float)t1d[e] * (float)bn.inv_count;
@@ -563,7 +658,7 @@ __global__ __launch_bounds__(NT) void normbwd_apply_kernel(RedGeom q, const T* _
         auto row = [&](auto mc, const f32x4& a, const f32x4& d, const f32x4* f, long idx, int r) UD_LAMBDA_INLINE {
             constexpr int MODE = decltype(mc)::value;
             f32x4 dz, xh, o;
-            dz_terms<MODE>(a, d, cb, sc, dz, xh);
+            dz_terms<MODE>(a, d, cb, sc, dz, xh, sg);
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = k[e] * __builtin_fmaf(-xh[e], t2[e], dz[e] - t1[e]);          // (the rounding stated)
             if constexpr (PL == 2) {
@@ -593,7 +688,7 @@ __global__ __launch_bounds__(NT) void normbwd_apply_kernel(RedGeom q, const T* _
                 }
             }
         };
-        dz_switch(dy_is_dz, bn.act, [&](auto mc) UD_LAMBDA_INLINE {
+        dz_switch<SE>(dy_is_dz, bn.act, [&](auto mc) UD_LAMBDA_INLINE {
             if constexpr (MIX) {
                 const In4<T> in[3] = {x4, d4, fr4};
                 for_rows<T, 3>(w.r, w.r_end, q.rpi, w.idx, w.step, in, fin, [&](long idx, int r, const f32x4(&t)[3]) UD_LAMBDA_INLINE {
@@ -845,11 +940,23 @@ __global__ __launch_bounds__(NT) void se_bwd_a_kernel(const double* __restrict__
 // ds1[n][i] = ds1_acc[n][i] * swish'(s1[n][i]).  grid (x, y):
 //   y <  N : dpool[n][c] = sum_i ds1[n][i] Wr[i][c] for sample n = y, channels x * 256 ..
 //   y >= N : i = y - N: dW_r[i][c] = sum_n ds1[n][i] pool[n][c] * pool_scale;  db_r[i] = sum_n ds1[n][i]
+// BN (ud_se_bwd_b_bn): the (n, c) thread that forms dpool[n][c] also adds its sample's share of the BatchNorm-1 backward sums,
+//   bs1[c] += g A1 + p B1,  bs2[c] += g A2 + p B2,   g = sigmoid(s2[n][c]), p = dpool[n][c] inv_hw — both in fp32 exactly as the
+//   apply pass (normbwd_apply_kernel<.., SE>) will form them; (A1, A2, B1, B2) = planes 1..4 of coldot_bn_se_kernel's [5][N][C].
+//   fp64 atomics, N adds per address.
+struct SeBnFold {
+    const float* s2;
+    const double* dots;
+    float inv_hw;
+    double* bs1;
+    double* bs2;
+};
+template <bool BN>
 __global__ __launch_bounds__(NT) void se_bwd_b_kernel(const double* __restrict__ ds1_acc, const float* __restrict__ s1,
                                                       const float* __restrict__ Wr, const double* __restrict__ pool,
                                                       float pool_scale, float* __restrict__ dpool,
                                                       float* __restrict__ dWr, float* __restrict__ dbr, int N, int C,
-                                                      int Cs) {
+                                                      int Cs, SeBnFold f) {
     __shared__ float sh[NT];
     const int c = blockIdx.x * NT + threadIdx.x;
     if ((int)blockIdx.y < N) {
@@ -858,10 +965,22 @@ __global__ __launch_bounds__(NT) void se_bwd_b_kernel(const double* __restrict__
             sh[threadIdx.x] = (float)ds1_acc[(long)n * Cs + threadIdx.x] * ud_act_grad_fast(s1[(long)n * Cs + threadIdx.x], 1);
         __syncthreads();
         if (c >= C) return;
+        const long o = (long)n * C + c, plane = (long)N * C;
+        float gs = 0.f;
+        double a1 = 0.0, a2 = 0.0, b1 = 0.0, b2 = 0.0;
+        if constexpr (BN) {          // in flight through the FC loop
+            gs = f.s2[o];
+            a1 = f.dots[plane + o], a2 = f.dots[2 * plane + o], b1 = f.dots[3 * plane + o], b2 = f.dots[4 * plane + o];
+        }
         float acc = 0.f;
 #pragma unroll 8
         for (int i = 0; i < Cs; ++i) acc += sh[i] * Wr[(long)i * C + c];
-        dpool[(long)n * C + c] = acc;
+        dpool[o] = acc;
+        if constexpr (BN) {
+            const double g = (double)ud_sigmoid_fast(gs), p = (double)mul_rn(acc, f.inv_hw);
+            atomic_add_f64(f.bs1 + c, g * a1 + p * b1);
+            atomic_add_f64(f.bs2 + c, g * a2 + p * b2);
+        }
         return;
     }
     const int i = blockIdx.y - N;
@@ -1310,7 +1429,7 @@ int ud_normbwd_apply(const void* x, const void* dy, const float* keep, float inv
                                                 (hipStream_t)stream, q, (const T*)x, (const T*)dy, keep, inv_keep, *bn,
                                                 dy_is_dz, s1, s2, s1_local, s2_local, (const T*)nullptr, (T*)dx,
                                                 (double*)nullptr, dgamma, dbeta, absmax, (double*)nullptr,
-                                                PlanesDst{nullptr, 0, 0, nullptr, nullptr}));
+                                                PlanesDst{nullptr, 0, 0, nullptr, nullptr}, SeSrc{}));
     UD_LAUNCH_CHECK();
     return 0;
 }
@@ -1330,7 +1449,7 @@ int ud_normbwd_apply_planes(const float* x, const float* dy, const float* keep, 
     hipLaunchKernelGGL((normbwd_apply_kernel<float, false, 1>), red_grid(q), dim3(NT), 0, (hipStream_t)stream, q, x, dy, keep,
                        inv_keep, *bn, dy_is_dz, s1, s2, s1_local, s2_local, (const float*)nullptr, (float*)nullptr,
                        (double*)nullptr, dgamma, dbeta, (uint32_t*)nullptr, (double*)nullptr,
-                       PlanesDst{planes, panel_stride, plane_stride, inv_scale, energy});
+                       PlanesDst{planes, panel_stride, plane_stride, inv_scale, energy}, SeSrc{});
     UD_LAUNCH_CHECK();
     return 0;
 }
@@ -1347,7 +1466,7 @@ int ud_normbwd_apply_plane_half(const void* x, const void* dy, const float* keep
     hipLaunchKernelGGL((normbwd_apply_kernel<_Float16, false, 2>), red_grid(q), dim3(NT), 0, (hipStream_t)stream, q,
                        (const _Float16*)x, (const _Float16*)dy, keep, inv_keep, *bn, dy_is_dz, s1, s2, s1_local, s2_local,
                        (const _Float16*)nullptr, (_Float16*)nullptr, (double*)nullptr, dgamma, dbeta, (uint32_t*)nullptr,
-                       (double*)nullptr, PlanesDst{plane, panel_stride, 0, inv_scale, nullptr});
+                       (double*)nullptr, PlanesDst{plane, panel_stride, 0, inv_scale, nullptr}, SeSrc{});
     UD_LAUNCH_CHECK();
     return 0;
 }
@@ -1365,7 +1484,7 @@ int ud_normbwd_apply_mix(const void* x, const void* dz, const ud_bn_ref* bn, con
                                                 (hipStream_t)stream, q, (const T*)x, (const T*)dz, (const float*)nullptr,
                                                 1.f, *bn, 1, s1, s2, s1_local, s2_local, (const T*)diff, (T*)dd,
                                                 dalpha_acc, dgamma, dbeta, (uint32_t*)nullptr, energy,
-                                                PlanesDst{nullptr, 0, 0, nullptr, nullptr}));
+                                                PlanesDst{nullptr, 0, 0, nullptr, nullptr}, SeSrc{}));
     UD_LAUNCH_CHECK();
     return 0;
 }
@@ -1400,8 +1519,68 @@ int ud_se_bwd_b(const double* ds1_acc, const float* s1, const float* Wr, const d
     if (N < 1 || N > NT || C < 1 || Cs < 1 || Cs > NT || !ds1_acc || !s1 || !Wr || !dpool || (!dWr != !dbr) || (wg && !pool))
         return UD_EINVAL;
     dim3 grid((unsigned)ud_cdiv(C, NT), (unsigned)(N + (wg ? Cs : 0)));
-    hipLaunchKernelGGL(se_bwd_b_kernel, grid, dim3(NT), 0, (hipStream_t)stream, ds1_acc, s1, Wr, pool, pool_scale, dpool,
-                       dWr, dbr, N, C, Cs);
+    hipLaunchKernelGGL(se_bwd_b_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, ds1_acc, s1, Wr, pool, pool_scale, dpool,
+                       dWr, dbr, N, C, Cs, SeBnFold{});
+    UD_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the SE backward with the BatchNorm-1 sums from per-sample dots: ud_coldot_bn_se -> ud_se_bwd_a ->
+// ud_se_bwd_b_bn -> ud_normbwd_apply_se / _mix_se; dz1 is never written, ud_se_scale_bwd_bn is not launched.  fp32 storage. ----
+// Per-group accumulators see P <= 64 adds per address whatever the size (plan_reduce): always one launch, no scratch.
+int ud_coldot_bn_se(const void* dy, const void* x, const ud_bn_ref* bn, int G, int R, int C, double* out, int f16,
+                    ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
+    if (!shape_ok(G, R, C) || !x || !dy || !bn || !out || bn->G != 1 || f16) return UD_EINVAL;
+    RedPlan pl = plan_reduce(G, R, C, true, nullptr);
+    hipLaunchKernelGGL(coldot_bn_se_kernel<float>, red_grid(pl.q), dim3(NT), 0, (hipStream_t)stream, pl.q, (const float*)x,
+                       (const float*)dy, *bn, out);
+    UD_LAUNCH_CHECK();
+    return 0;
+}
+
+int ud_se_bwd_b_bn(const double* ds1_acc, const float* s1, const float* Wr, const double* pool, float pool_scale,
+                   float* dpool, float* dWr, float* dbr, const float* s2, const double* dots, float inv_hw, double* bs1,
+                   double* bs2, int N, int C, int Cs, ud_stream_t stream) {
+    const bool wg = dWr != nullptr;
+    if (N < 1 || N > NT || C < 1 || Cs < 1 || Cs > NT || !ds1_acc || !s1 || !Wr || !dpool || (!dWr != !dbr) || (wg && !pool))
+        return UD_EINVAL;
+    if (!s2 || !dots || !bs1 || !bs2) return UD_EINVAL;
+    dim3 grid((unsigned)ud_cdiv(C, NT), (unsigned)(N + (wg ? Cs : 0)));
+    hipLaunchKernelGGL(se_bwd_b_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, ds1_acc, s1, Wr, pool, pool_scale, dpool,
+                       dWr, dbr, N, C, Cs, SeBnFold{s2, dots, inv_hw, bs1, bs2});
+    UD_LAUNCH_CHECK();
+    return 0;
+}
+
+int ud_normbwd_apply_se(const void* x, const void* dc, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,
+                        const double* s1, const double* s2, const double* s1_local, const double* s2_local, int G, int R,
+                        int C, void* dx, float* dgamma, float* dbeta, int f16, uint32_t* absmax, ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
+    if (!shape_ok(G, R, C) || !x || !dc || !bn || !s || !dpool || !s1 || !s2 || !dx || bn->G != 1 || f16) return UD_EINVAL;
+    if ((dgamma || dbeta) && (!s1_local || !s2_local)) return UD_EINVAL;
+    RedGeom q = geom_ew(G, R, C);
+    hipLaunchKernelGGL((normbwd_apply_kernel<float, false, 0, true>), red_grid(q), dim3(NT), 0, (hipStream_t)stream, q,
+                       (const float*)x, (const float*)dc, (const float*)nullptr, 1.f, *bn, 0, s1, s2, s1_local, s2_local,
+                       (const float*)nullptr, (float*)dx, (double*)nullptr, dgamma, dbeta, absmax, (double*)nullptr,
+                       PlanesDst{nullptr, 0, 0, nullptr, nullptr}, SeSrc{s, dpool, inv_hw});
+    UD_LAUNCH_CHECK();
+    return 0;
+}
+
+int ud_normbwd_apply_mix_se(const void* x, const void* dc, const ud_bn_ref* bn, const float* s, const float* dpool,
+                            float inv_hw, const double* s1, const double* s2, const double* s1_local,
+                            const double* s2_local, const void* diff, int G, int R, int C, void* dd, double* dalpha_acc,
+                            float* dgamma, float* dbeta, double* energy, int f16, ud_stream_t stream) {
+    if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
+    if (!shape_ok(G, R, C) || !x || !dc || !bn || !s || !dpool || !s1 || !s2 || !dd || !diff || !dalpha_acc || bn->G != 1 || f16)
+        return UD_EINVAL;
+    if ((dgamma || dbeta) && (!s1_local || !s2_local)) return UD_EINVAL;
+    RedGeom q = make_geom_ex(G, R, C, 512, 4096, 4);      // (ud_normbwd_apply_mix's geometry)
+    hipLaunchKernelGGL((normbwd_apply_kernel<float, true, 0, true>), red_grid(q), dim3(NT), 0, (hipStream_t)stream, q,
+                       (const float*)x, (const float*)dc, (const float*)nullptr, 1.f, *bn, 0, s1, s2, s1_local, s2_local,
+                       (const float*)diff, (float*)dd, dalpha_acc, dgamma, dbeta, (uint32_t*)nullptr, energy,
+                       PlanesDst{nullptr, 0, 0, nullptr, nullptr}, SeSrc{s, dpool, inv_hw});
     UD_LAUNCH_CHECK();
     return 0;
 }

@@ -3085,6 +3085,14 @@ def coldot_bn(dy, x, bn, G, R, out):
           _stream())
 
 
+def coldot_bn_se(dy, x, bn, G, R, out):
+    """coldot_bn plus the four per-sample dots the BatchNorm backward sums are linear in: out fp64 [5 G C], zeroed by the caller,
+    receives (dgate, A1, A2, B1, B2) — se_bwd(fold=...) turns them into the sums.  fp32 storage."""
+    _chk(dy, x)
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32 and out.numel() >= 5 * G * x.shape[-1]
+    _call("ud_coldot_bn_se", _p(dy), _p(x), C.byref(bn.ref()), G, R, x.shape[-1], _pd(out), 0, _stream())
+
+
 def fc_fwd_d(xsum, xscale, W, b, N):
     _chk(W, b)
     O, I = W.shape
@@ -3287,16 +3295,49 @@ def normbwd_apply_mix(x, dz, bn, G, R, sacc, diff, dalpha_acc, sacc_local=None, 
     return dd, dg, db
 
 
+def normbwd_apply_se(x, dc, bn, s, dpool, inv_hw, G, R, sacc, sacc_local=None):
+    """normbwd_apply whose gradient input is dc, the gated tensor's gradient: dz = (dc sigmoid(s) + dpool inv_hw) act'(bn(x)) is
+    formed on load and never stored; sacc from se_bwd(fold=...).  fp32 storage.  Returns (dx, dgamma, dbeta)."""
+    _chk(x, dc, s, dpool)
+    assert x.dtype == torch.float32 and dc.dtype == torch.float32
+    Cc = x.shape[-1]
+    loc = sacc if sacc_local is None else sacc_local
+    dx = torch.empty_like(x)
+    dg = empty((Cc,), x)
+    db = empty((Cc,), x)
+    _call("ud_normbwd_apply_se", _p(x), _p(dc), C.byref(bn.ref()), _p(s), _p(dpool), float(inv_hw), _pd(sacc), _pd(sacc, Cc),
+          _pd(loc), _pd(loc, Cc), G, R, Cc, _p(dx), _p(dg), _p(db), 0, None, _stream())
+    dx._ud_absmax = None
+    return dx, dg, db
+
+
+def normbwd_apply_mix_se(x, dc, bn, s, dpool, inv_hw, G, R, sacc, diff, dalpha_acc, sacc_local=None, energy=None):
+    """normbwd_apply_mix likewise: dz formed on load from (dc, x, s, dpool).  fp32 storage.  Returns (dd, dgamma, dbeta)."""
+    _chk(x, dc, diff, s, dpool)
+    assert x.dtype == torch.float32 and dc.dtype == torch.float32 and diff.dtype == torch.float32
+    Cc = x.shape[-1]
+    loc = sacc if sacc_local is None else sacc_local
+    dd = torch.empty_like(x)
+    dg = empty((Cc,), x)
+    db = empty((Cc,), x)
+    _call("ud_normbwd_apply_mix_se", _p(x), _p(dc), C.byref(bn.ref()), _p(s), _p(dpool), float(inv_hw), _pd(sacc), _pd(sacc, Cc),
+          _pd(loc), _pd(loc, Cc), _p(diff), G, R, Cc, _p(dd), _pd(dalpha_acc), _p(dg), _p(db),
+          _pd(energy) if energy is not None else None, 0, _stream())
+    return dd, dg, db
+
+
 def gate_grad_from_acc(acc, alpha):
     out = empty((), alpha)
     _call("ud_gate_grad_from_acc", _pd(acc), _p(alpha), _p(out), _stream())
     return out
 
 
-def se_bwd(dgate, s2, s1, We, Wr, pool, pool_scale, need_w=True):
+def se_bwd(dgate, s2, s1, We, Wr, pool, pool_scale, need_w=True, fold=None):
     """Backward of the two SE FCs (model.py:119-121) in two launches.  dgate: fp64 [N, C] (gradient of the gate
     sigmoid(s2)); pool: fp64 pooled SUMS.  Returns (dpool, dWe, dbe, dWr, dbr).
-    need_w=False (a frozen backward): only dpool — the weight / bias gradient workgroups are not launched, pool is not read."""
+    need_w=False (a frozen backward): only dpool — the weight / bias gradient workgroups are not launched, pool is not read.
+    fold = (dots, inv_hw, sacc): dots the [5 N C] result of coldot_bn_se (dgate its first plane); the second launch also adds the
+    BatchNorm-1 backward sums into sacc (fp64 [2 C], zeroed): ud_se_bwd_b_bn."""
     _chk(s2, s1, We, Wr)
     N, Cc = s2.shape
     Cs = s1.shape[1]
@@ -3312,6 +3353,12 @@ def se_bwd(dgate, s2, s1, We, Wr, pool, pool_scale, need_w=True):
     dpool = empty((N, Cc), s2)
     dWr = empty((Cs, Cc), s2)
     dbr = empty((Cs,), s2)
+    if fold is not None:
+        dots, inv_hw, sacc = fold
+        assert dots.numel() >= 5 * N * Cc and sacc.numel() >= 2 * Cc
+        _call("ud_se_bwd_b_bn", _pd(ds1_acc), _p(s1), _p(Wr), _pd(pool), float(pool_scale), _p(dpool), _p(dWr), _p(dbr), _p(s2),
+              _pd(dots), float(inv_hw), _pd(sacc), _pd(sacc, Cc), N, Cc, Cs, _stream())
+        return dpool, dWe, dbe, dWr, dbr
     _call("ud_se_bwd_b", _pd(ds1_acc), _p(s1), _p(Wr), _pd(pool), float(pool_scale), _p(dpool), _p(dWr), _p(dbr), N, Cc,
           Cs, _stream())
     return dpool, dWe, dbe, dWr, dbr

@@ -89,6 +89,26 @@ def _dw_bwd_fused_policy(sf, k, stride, H, half):
     return not (k == 3 and H == 64)
 
 
+# The SE / BatchNorm-1 backward without dz1: the BatchNorm sums are linear in the per-sample gate and dpool, so the
+# dot pass sums four more per-sample dots (K.coldot_bn_se), the second SE FC launch folds them into the sums (K.se_bwd(fold=...))
+# and the apply pass forms dz1 on load from dc (K.normbwd_apply_se / _mix_se): se_scale_bwd_bn is not launched, dz1 never written.
+_SE_BN1_FOLD_OVERRIDE = {}
+
+
+def _se_bn1_fold_policy(sf, stride, Ho, Ce, half):
+    """BatchNorm-1 backward sums from per-sample dots, dz1 formed on load?  For the blocks whose project conv's data gradient dc
+    is a tensor (not pj_fused), fp32 storage.  Measured per block shape, old chain against new (tools/bench_se_bn1_fold.py on an
+    MI355X, profiles/r23/se_bn1_fold.txt; us, bs 32): plain 128^2 x 48 155 -> 93 and x 24 90 -> 56, SF stride 2 16^2 x 336 41 -> 30,
+    SF 16^2 x 672 55 -> 42 and x 960 67 -> 50, SF stride 2 8^2 x 960 32 -> 25, SF 8^2 x 1632 49 -> 43, plain 8^2 x 1632 44 -> 38 and
+    x 2688 62 -> 51: every shape of the step wins, so the rule is "on"; the override keeps the old chain reachable per shape."""
+    if half:
+        return False
+    ov = _SE_BN1_FOLD_OVERRIDE.get((bool(sf), stride, Ho, Ce))
+    if ov is not None:
+        return ov
+    return True
+
+
 # ONE geometry per (block, input shape), read by all five nodes.
 # sizes: x [N,H,W,Cin] (M pixels) -> expanded [N,H,W,Ce] -> depthwise [N,Ho,Wo,Ce] (HWo per sample, Mo pixels) -> [N,Ho,Wo,Co];
 # pt / pl: the depthwise conv's top / left zero pad.  2-D weight views: We expand [Ce,Cin] (None: no expand conv), Wsr / Wse the
@@ -405,7 +425,8 @@ def _fused_backward(b, tape):
 
 def _bwd_project(b, tape, gr):
     """BN2 (+ drop-connect scale) and the project conv -> gr.dp2 (the gradient of the project output, [Mo, Co] or the planes'
-    placeholder), gr.dc (the gated tensor's gradient; None where pj_fused), gr.dgate (the SE gate's, fp64 sums), gr.pj_fused."""
+    placeholder), gr.dc (the gated tensor's gradient; None where pj_fused), gr.dgate (the SE gate's, fp64 sums), gr.pj_fused,
+    gr.se_dots (None, or [5 N Ce] fp64: dgate and the four dots of the BN1 sums — the route of _se_bn1_fold_policy)."""
     g, x, blk, dout = b.geo, b.x, b.blk, gr.dout
     # the project conv's backward on the planes GEMM: the apply pass writes its operand's planes itself, scaled by the bound
     # the sums pass leaves behind (the energy of the incoming gradient: a third sum)
@@ -420,31 +441,51 @@ def _bwd_project(b, tape, gr):
     # re-makes its tile from the thin dp (csrc/pjbwd.hip)
     gr.pj_fused = not dp_pl and b.pctx.plans is None and K.project_bwd_fused_ok(b.d, g.Wp, g.HWo)
     assert gr.pj_fused or b.pctx.x is not None, "the fused project forward kept no gated tensor: its backward must be the fused one"
-    gr.dgate = K.zeros64(g.N * g.Ce, x)
+    gr.se_dots = None
     if gr.pj_fused:
         gr.dc = None
+        gr.dgate = K.zeros64(g.N * g.Ce, x)
         dWp = K.project_bwd_fused_a(b.d, b.bn1, b.s2, gr.dp2, g.Wp, g.N, g.HWo, gr.dgate)
     else:
         dc, dWp = K.spectral_bwd(b.pctx, gr.dp2, dy_absmax=dp_amax)          # (one launch for both where that fills the chip better)
         gr.dc = dc.view(g.N, g.Ho, g.Wo, g.Ce)
-        K.coldot_bn(gr.dc, b.d, b.bn1, g.N, g.HWo, gr.dgate)
+        if _se_bn1_fold_policy(g.sf, g.stride, g.Ho, g.Ce, b.d.dtype != torch.float32 or dc.dtype != torch.float32):
+            gr.se_dots = K.zeros64(5 * g.N * g.Ce, x)
+            gr.dgate = gr.se_dots[:g.N * g.Ce]
+            K.coldot_bn_se(gr.dc, b.d, b.bn1, g.N, g.HWo, gr.se_dots)
+        else:
+            gr.dgate = K.zeros64(g.N * g.Ce, x)
+            K.coldot_bn(gr.dc, b.d, b.bn1, g.N, g.HWo, gr.dgate)
     tape.add_param_grad(blk._project_conv.weight, dWp)
 
 
 def _bwd_se(b, tape, gr):
-    """the two SE FCs, then gate + swish + the BN1 backward sums in one pass -> gr.dz1, gr.sb1 (summed over the ranks), gr.loc1"""
+    """the two SE FCs, then gate + swish + the BN1 backward sums in one pass -> gr.dz1, gr.sb1 (summed over the ranks), gr.loc1;
+    gr.se_dots given: the sums come out of the second FC launch, gr.dz1 is None and gr.dpool is kept for the apply pass"""
     g, blk = b.geo, b.blk
-    dpool, dWe2, dbe2, dWr, dbr = K.se_bwd(gr.dgate, b.s2, b.s1, g.Wse, g.Wsr, b.pool, 1.0 / g.HWo)
+    gr.sb1 = K.zeros64(2 * g.Ce, b.x)
+    fold = (gr.se_dots, 1.0 / g.HWo, gr.sb1) if gr.se_dots is not None else None
+    dpool, dWe2, dbe2, dWr, dbr = K.se_bwd(gr.dgate, b.s2, b.s1, g.Wse, g.Wsr, b.pool, 1.0 / g.HWo, fold=fold)
     tape.add_param_grad(blk._se_expand.weight, dWe2)
     tape.add_param_grad(blk._se_expand.bias, dbe2)
     tape.add_param_grad(blk._se_reduce.weight, dWr)
     tape.add_param_grad(blk._se_reduce.bias, dbr)
-    gr.sb1 = K.zeros64(2 * g.Ce, b.x)
-    if gr.pj_fused:
+    gr.dpool = dpool
+    if fold is not None:
+        gr.dz1 = None
+    elif gr.pj_fused:
         gr.dz1 = K.project_bwd_fused_b(b.d, b.bn1, b.s2, dpool, 1.0 / g.HWo, gr.dp2, g.Wp, g.N, g.HWo, gr.sb1)
     else:
         gr.dz1 = K.se_scale_bwd_bn(gr.dc, b.d, b.bn1, b.s2, dpool, 1.0 / g.HWo, g.N, g.HWo, gr.sb1)
     gr.loc1 = b.dp.reduce(gr.sb1, keep_local=True)
+
+
+def _bn1_apply(b, gr):
+    """the BN1 backward apply from dz1 or, where dz1 was never written (gr.se_dots), from dc through the SE gate"""
+    g = b.geo
+    if gr.dz1 is None:
+        return K.normbwd_apply_se(b.d, gr.dc, b.bn1, b.s2, gr.dpool, 1.0 / g.HWo, g.N, g.HWo, gr.sb1, gr.loc1)
+    return K.normbwd_apply(b.d, gr.dz1, None, 1.0, b.bn1, True, g.N, g.HWo, gr.sb1, gr.loc1)
 
 
 def _bwd_bn1(b, tape, gr):
@@ -454,14 +495,18 @@ def _bwd_bn1(b, tape, gr):
     g, x, blk, d = b.geo, b.x, b.blk, b.d
     gr.g_alpha, gr.g_mode, gr.da_f, gr.dxf = None, 0, None, None
     if not g.sf:
-        gr.g_sp, dg1, db1 = K.normbwd_apply(d, gr.dz1, None, 1.0, b.bn1, True, g.N, g.HWo, gr.sb1, gr.loc1)
+        gr.g_sp, dg1, db1 = _bn1_apply(b, gr)
     else:
         alpha, sctx = g.alpha, b.sctx
         if g.stride == 1:
             dacc = K.zeros64(64, x)
             dyf_pl = sctx.plans is not None and K.rfft2_planes_ok(d, None)
             en = K.zeros64(g.Ce, x) if dyf_pl else None
-            dd, dg1, db1 = K.normbwd_apply_mix(d, gr.dz1, b.bn1, g.N, g.HWo, gr.sb1, b.fr, dacc, gr.loc1, energy=en)
+            if gr.dz1 is None:
+                dd, dg1, db1 = K.normbwd_apply_mix_se(d, gr.dc, b.bn1, b.s2, gr.dpool, 1.0 / g.HWo, g.N, g.HWo, gr.sb1, b.fr, dacc,
+                                                      gr.loc1, energy=en)
+            else:
+                dd, dg1, db1 = K.normbwd_apply_mix(d, gr.dz1, b.bn1, g.N, g.HWo, gr.sb1, b.fr, dacc, gr.loc1, energy=en)
             # adjoint of irfft2, x sigmoid(a); the same launch turns the accumulator slots into the gate's gradient
             # (_PLANES: ... and writes the GEMMs' planes itself: scale from the energy of dd the apply pass just summed)
             form = _PLANES if dyf_pl else _PLANE_HALF if (sctx.plans is not None and K.rfft2_plane_half_ok(dd)) else _ROWS
@@ -470,7 +515,7 @@ def _bwd_bn1(b, tape, gr):
             tape.add_param_grad(alpha, dalpha)
             gr.g_sp, gr.g_alpha, gr.g_mode = dd, alpha, 2                                   # spatial branch: x (1 - sigmoid(a))
         else:
-            dd, dg1, db1 = K.normbwd_apply(d, gr.dz1, None, 1.0, b.bn1, True, g.N, g.HWo, gr.sb1, gr.loc1)
+            dd, dg1, db1 = _bn1_apply(b, gr)
             gr.g_sp, dfr, dalpha = K.sfmix_bwd(b.spat, b.fr, alpha, dd, True)
             tape.add_param_grad(alpha, dalpha)
             dyf = K.rfft2(dfr, g.s_i, 2.0, want_absmax=True)
