@@ -814,6 +814,35 @@ int ud_uap_update_linf(float* delta, const float* gsum, const float* x, float* x
 int ud_uap_apply(float* delta, const double* dss, const float* x, float* x_adv, int N, long per, float eps, float lo, float hi,
                  ud_stream_t stream);
 
+/* ---- randomized smoothing (csrc/smooth.hip; unidefense_amd/smooth.py: CertifyRunner) ----------------------------------------
+ * One draw of a certificate is a static launch sequence inside a captured graph: noise, forward, vote.
+ * ud_smooth_noise: out[n][e] = x[n][e] + scale noise(n, e) for contiguous fp32 [N][per]; out may be x itself (no other overlap).
+ *   The noise is a pure function of (seed, ids[n], draw_n, e), draw_n = (uint32)(draw0 + (k ? k[n] : 0)); ids int64 [N] (the
+ *   sample's stream id), k int32 [N] or NULL (the sample's own draw counter), seed: 64 bits.  Philox4x32-10 (multipliers
+ *   0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) with the key (seed low word, seed high word) and the counter
+ *   (q, draw_n, id low word, id high word), q = e / 4; element 4 q + j takes output word j.  From a word w, m = w >> 8.
+ *   UD_SMOOTH_UNIFORM : t = (2 m + 1 - 2^24) 2^-24, exact in fp32, symmetric, never 0, inside (-1, 1).
+ *   UD_SMOOTH_GAUSSIAN: Box-Muller on the word pairs (w0, w1) -> elements (4 q, 4 q + 1) and (w2, w3) -> (4 q + 2, 4 q + 3):
+ *     u1 = (m_a + 1) 2^-24 in (0, 1], u2 = m_b 2^-24, r = sqrt(-2 ln u1), t = (r cos(2 pi u2), r sin(2 pi u2)), |t| <= 5.77;
+ *     logf, sqrtf and sincospif(2 u2), not the fast intrinsics.
+ *   out = x + scale t with one fp32 product and one fp32 add, not contracted (uniform: bitwise a float32 host expression).  A
+ *   NaN in x stays a NaN at its own element.  One thread per quad; a float4 per thread where per % 4 == 0 and both bases are
+ *   16-byte aligned, scalar accesses otherwise (the tail quad of another per uses its first words): the same bits either way.
+ * ud_smooth_vote: one thread per sample.  ist [1][N] int32, row UD_SMOOTH_I_K: the sample's draw counter (the caller zeroes it).
+ *   With d = ist[K][n] in [0, draws): the class is the first maximum of logits[n][0..C) (C == 1: logit > 0), Ce = max(C, 2);
+ *   votes[d][n] = the class, or -1 if any logit of the row is NaN (int32 [draws][N]); margins[d][n] = the top logit minus the
+ *   runner-up (C == 1: |logit|; an invalid row: NaN; fp32 [draws][N]); counts[d < n0 ? 0 : 1][n][class] += 1 for a valid row
+ *   (int32 [2][N][Ce]); ist[K][n] = d + 1.  d outside [0, draws) writes nothing.  No atomics: a thread touches its sample only.
+ * UD_EINVAL before any HIP call: a NULL pointer (but k), N < 1 or > 65535, per < 1 or > 2^34, an unknown mode, scale < 0 or NaN;
+ * C < 1, draws < 1, n0 outside [0, draws], draws N or 2 N Ce > 2^31 - 1. */
+#define UD_SMOOTH_I_K 0
+#define UD_SMOOTH_GAUSSIAN 0
+#define UD_SMOOTH_UNIFORM 1
+int ud_smooth_noise(const float* x, float* out, const long long* ids, const int* k, int draw0, int N, long per, int mode,
+                    float scale, long seed, ud_stream_t stream);
+int ud_smooth_vote(const float* logits, int N, int C, int* ist, int* counts, int* votes, float* margins, int draws, int n0,
+                   ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

@@ -1,4 +1,4 @@
-"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal: one scoring
+"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal / test_certified: one scoring
 forward, one batch source, one loop-and-gather, one metrics dictionary, and a table of test_robust's methods.  The Evaluator
 takes its model and iterator as arguments and imports nothing that loads the HIP library, so the stage rules run on the CPU
 against stubs (tests/test_evaluate_cpu.py, tests/test_universal_cpu.py).  What every stage keeps: its order inside a batch, who owns which generator, the sequence of
@@ -175,6 +175,50 @@ class Evaluator:
         args = dict(args, delta=d, linf=float(d.abs().max()), l2=float(d.double().norm()), fooled=fooled("adv"),
                     fooled_control=fooled("control"), fit_counted=[int(c) for c in torch.cat(counted).cpu()])
         return dict(self._result(cols, "Test(universal)", args), control=self.metrics(*cols["control"], "Test(control)"))
+
+    def test_certified(self, batches, certify):
+        from ..smooth import certified_curve
+        certify = dict(certify) if certify else {}
+        grid = certify.pop("grid", None)
+        if not batches >= 1 or int(batches) != batches:
+            raise ValueError(f"batches must be an integer >= 1, got {batches!r}")
+        try:                                             # ONE runner for every batch; every refusal before the first batch
+            runner = self.net.certify_runner(2 * self.batch, self.size, **certify)
+        except TypeError as e:                           # an unknown key is a bad dict, like a bad value
+            raise ValueError(f"certify takes CertifyRunner's keyword arguments and 'grid': {e}") from None
+        args = dict(runner.args)
+        grid = torch.linspace(0.0, 4.0 * args["sigma"], 9, dtype=torch.float64) if grid is None \
+            else torch.as_tensor(grid, dtype=torch.float64).reshape(-1)
+        if grid.numel() < 1 or not bool((torch.isfinite(grid) & (grid >= 0)).all()):
+            raise ValueError(f"grid must hold finite radii >= 0, got {grid.tolist()}")
+        dist = torch.distributed
+        rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
+        seen = 0
+
+        def body(x, y):                                  # the clean score, then the certificate; gathered radius, predicted, clean
+            nonlocal seen
+            clean = self.score(x)
+            # a stream id per sample of the whole run: the certificate does not depend on where the sample sits in its batch
+            ids = torch.arange(x.shape[0], dtype=torch.int64, device=x.device) + (seen * world + rank) * x.shape[0]
+            seen += 1
+            radius = runner(x, ids)
+            # the runner reuses its buffers: radius and predicted are cloned per batch
+            return {"radius": radius.clone(), "predicted": runner.predicted.clone(), "clean": clean}
+
+        cols = self.run(int(batches), body)
+        labels = cols["clean"][1].cpu()
+        radius, predicted = cols["radius"][0].float().cpu(), cols["predicted"][0].long().cpu()
+        right = predicted == labels
+        ret = {"args": args, "radius": radius, "predicted": predicted, "abstained": float((predicted < 0).double().mean()),
+               "accuracy": float(right.double().mean()),
+               "median_radius": float(radius[right].double().median()) if bool(right.any()) else float("nan"),
+               "grid": grid, "certified_accuracy": certified_curve(radius, predicted, labels, grid)}
+        clean = self.metrics(*cols["clean"], "Test")
+        if self.local_rank == 0:
+            print("Test(certified %s, sigma %g) | ACC %.4f, abstained %.4f, median radius %.4f | certified ACC %s" % (
+                args["norm"], args["sigma"], ret["accuracy"], ret["abstained"], ret["median_radius"],
+                " ".join("%.3g:%.4f" % (e, a) for e, a in zip(grid.tolist(), ret["certified_accuracy"].tolist()))))
+        return {"clean": clean, "certify": ret}
 
 
 # ---- test_robust's methods: ROBUST[method](ev, attack) refuses and resolves the dict (given without "method") and is the run:

@@ -280,6 +280,18 @@ class TrainEngine(AbstractEngine):
         universal = universal if universal is not None else self.config["config"].get("universal")
         return self._evaluator().test_universal(batches, fit_batches, epochs, universal)
 
+    def test_certified(self, batches=4, certify=None):
+        """A LOWER bound on robustness, where test_robust gives upper bounds (unidefense_amd/smooth.py): every test batch is scored
+        as test() does (inference_graph / inference_precision keep their meaning), then certified by the model's CertifyRunner —
+        n0 + n noisy forwards per batch, no labels.  certify (default config['config']['certify'], then the runner's defaults):
+        the runner's keyword arguments, e.g. {"sigma": 0.25, "noise": "gaussian", "n0": 100, "n": 1000, "alpha": 0.001}, plus an
+        optional "grid" of radii (default: nine points from 0 to 4 sigma).  Returns {"clean": what test() returns, "certify": the
+        resolved "args", "radius" and "predicted" (CPU, -1: abstained), "abstained" (a fraction), "accuracy" (predicted == label;
+        an abstention is wrong), "median_radius" over the correct samples, "grid" and "certified_accuracy" (per grid point the
+        fraction classified correctly and certified beyond it)}.  Sample i of rank r's batch b draws the noise stream
+        (b world + r) 2 batch + i; radius, predicted and the scores are gathered over the ranks as in test(), in this order."""
+        return self._evaluator().test_certified(batches, certify if certify is not None else self.config["config"].get("certify"))
+
     def validate(self, step, batches=4):
         """The reference's validate (forgery_engine.py:320-421) without the figure / wandb plumbing: metrics over all
         ranks, best-so-far record (AUC + ACC), best_model.bin / latest_model.bin on rank 0."""

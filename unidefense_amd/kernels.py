@@ -1959,6 +1959,59 @@ def uap_apply(delta, dss, x, x_adv, eps, lo, hi):
     return x_adv
 
 
+# ---- randomized smoothing (csrc/smooth.hip): the noise of a draw made in the kernel, the draw's votes counted on the device ------
+SMOOTH_I = _rows("UD_SMOOTH_I_")
+SMOOTH_MODE = {"gaussian": _const("UD_SMOOTH_GAUSSIAN"), "uniform": _const("UD_SMOOTH_UNIFORM")}
+
+
+def smooth_state(N, draws, C, device):
+    """(ist, counts, votes, margins): zeroed state for N samples, `draws` draws and C logits (counts has max(C, 2) classes)"""
+    return (torch.zeros(len(SMOOTH_I), N, dtype=torch.int32, device=device),
+            torch.zeros(2, N, max(int(C), 2), dtype=torch.int32, device=device),
+            torch.zeros(draws, N, dtype=torch.int32, device=device), torch.zeros(draws, N, dtype=torch.float32, device=device))
+
+
+def _seed64(seed):
+    """a Python integer's low 64 bits as the signed value the C ABI's `long` carries"""
+    s = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return s - (1 << 64) if s >> 63 else s
+
+
+def smooth_noise(x, out, ids, k, draw0, mode, scale, seed):
+    """out[n] = x[n] + scale noise(seed, ids[n], draw0 + k[n], element): x, out fp32 [N, ...] (out may be x), ids int64 [N], k
+    int32 [N] or None; mode "gaussian" / "uniform"; Philox4x32-10 in the kernel, a pure function of its four arguments."""
+    _chk_same(x, out)
+    N = x.shape[0] if x.dim() >= 1 else 0
+    if N < 1 or x.numel() == 0:
+        raise ValueError(f"expected a batch [N, ...], got {tuple(x.shape)}")
+    if not (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and tuple(ids.shape) == (N,)):
+        raise ValueError(f"ids must be a contiguous int64 CUDA tensor [{N}], got {ids.dtype} {ids.device} {tuple(ids.shape)}")
+    if k is not None:
+        _chk_i32(k, (N,), "k")
+    if mode not in SMOOTH_MODE:
+        raise ValueError(f"mode must be one of {tuple(SMOOTH_MODE)}, got {mode!r}")
+    _call("ud_smooth_noise", _p(x), _p(out), _p(ids), _p(k), int(draw0), N, x.numel() // N, SMOOTH_MODE[mode], float(scale),
+          _seed64(seed), _stream())
+    return out
+
+
+def smooth_vote(logits, ist, counts, votes, margins, n0):
+    """One draw's votes on logits [N, C] fp32 with d = ist's counter: votes[d] = the first maximum's class (-1 for a row with a
+    NaN), margins[d] = top minus runner-up, counts[d < n0 ? 0 : 1, n, class] += 1, counter + 1; votes, margins are [draws, N]."""
+    _chk(logits, margins)
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"logits must be [N, C], got {tuple(logits.shape)}")
+    N, Cn = logits.shape
+    if votes.dim() != 2 or votes.shape[0] < 1 or votes.shape[1] != N:
+        raise ValueError(f"votes must be [draws, {N}] with draws >= 1, got {tuple(votes.shape)}")
+    _chk_i32(ist, (len(SMOOTH_I), N), "ist")
+    _chk_i32(counts, (2, N, max(Cn, 2)), "counts")
+    _chk_i32(votes, tuple(votes.shape), "votes")
+    if tuple(margins.shape) != tuple(votes.shape):
+        raise ValueError(f"margins must be {list(votes.shape)}, got {tuple(margins.shape)}")
+    _call("ud_smooth_vote", _p(logits), N, Cn, _p(ist), _p(counts), _p(votes), _p(margins), votes.shape[0], int(n0), _stream())
+
+
 def conv_gather_wgrad(a, x, g):
     """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)]."""
     _chk(a, x)

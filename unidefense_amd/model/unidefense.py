@@ -283,6 +283,13 @@ class RunnerMethods:
         from ..universal import universal_runner
         return universal_runner(self, batch, size, **kwargs)
 
+    def certify_runner(self, batch, size, **kwargs):
+        """The graph-replayed randomized-smoothing certificate — per sample a radius inside which the smoothed decision provably
+        does not change — for [batch, 3, size, size] inputs (unidefense_amd/smooth.py: CertifyRunner; kwargs: sigma, noise, n0, n,
+        alpha, seed, logits, precision)."""
+        from ..smooth import certify_runner
+        return certify_runner(self, batch, size, **kwargs)
+
 
 class UniDefenseModelEb4(RunnerMethods, nn.Module):
     """UniDefense model with EfficientNet backbone (reference: model/unidefense.py:28-256)."""
