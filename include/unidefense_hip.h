@@ -843,6 +843,50 @@ int ud_smooth_noise(const float* x, float* out, const long long* ids, const int*
 int ud_smooth_vote(const float* logits, int N, int C, int* ist, int* counts, int* votes, float* margins, int draws, int n0,
                    ud_stream_t stream);
 
+/* ---- flow-field (stAdv) attack on a differentiable warp (csrc/flow.hip; unidefense_amd/flow.py: flow_warp, FlowRunner) --------
+ * x, out, g, x_adv fp32 [N][3][S][S]; w, w_best, gw fp32 [N][2][S][S], a displacement per output pixel in pixels: channel 0 the
+ * column displacement, channel 1 the row displacement.  Every kernel is one launch, one thread per pixel for the three channels,
+ * pixel-local gathers with ordinary vector loads and stores: no atomics, no workspace, a replay gives the same bits.  Every fp32
+ * operation below is rounded once, in the order written, without contraction.
+ * The cell of the output pixel (r, c):  qx = (float)c + w0 (one rounding; everything below starts from this fp32 value),
+ *   px = min(max(qx, 0), S - 1), x0 = min(floor(px), S - 2), fx = px - x0 in [0, 1] (floor and the difference are exact);
+ *   qy, py, y0, fy likewise from r and w1.  A NaN qx (qy) takes the cell 0 and fx (fy) = NaN: it is replaced BEFORE the
+ *   conversion to an integer, and the integer is clamped to [0, S - 2] once more, so every tap index lies in [0, S - 1] for ANY
+ *   content of w (NaN, +-inf, huge values).  The taps u_ab = x[ch][y0 + a][x0 + b].
+ * ud_flow_warp: out[ch] = (1 - fy) ((1 - fx) u00 + fx u01) + fy ((1 - fx) u10 + fx u11), out != x: at most FIVE roundings on a
+ *   path (1 - fx, the product, the sum, the product with 1 - fy, the sum).  A zero flow returns a finite x (a -0.0 as +0.0); a
+ *   NaN component of w gives NaN at that pixel only.
+ * ud_flow_grad: gw = sign (gx, gy) - tau t, sign = +1 (ascend) or -1 (targeted), with g = dL/dout:
+ *     gx = 0 < qx < S - 1 ? sum_ch g[ch] ((1 - fy) (u01 - u00) + fy (u11 - u10)) : 0      (strict, as torch's grid_sample)
+ *     gy = 0 < qy < S - 1 ? sum_ch g[ch] ((1 - fx) (u10 - u00) + fx (u11 - u01)) : 0
+ *   the channel sum from ch = 0 upwards (six roundings on a path), and t the gradient at p of the smoothness term
+ *   L_flow = sum over the unordered horizontal and vertical neighbour pairs (p, q) of sqrt(|w(p) - w(q)|^2 + tv_eps):
+ *     t = sum over q in (left, right, up, down) inside the image of d / sqrt(d0 d0 + d1 d1 + tv_eps), d = w(p) - w(q),
+ *   added in that order from 0 (ten roundings on a path), then tau t and the difference: TWELVE roundings on the longest path.
+ *   It reads w's neighbours: gw must not be w.
+ * ud_flow_control: one thread per sample, so that an iteration is a static launch sequence inside a captured graph.
+ *     ist [2][N] int32 : rows UD_FLOW_I_K (the sample's counter; the caller zeroes it to start a run), UD_FLOW_I_KEEP
+ *     fst [1][N] fp32  : row UD_FLOW_F_BEST (the best f so far);  history [steps + 1][N] fp32: row k = f of candidate k
+ *   With k = ist[K][n] in [0, steps]: history[k][n] = f[n]; keep = k == 0 || better(f, best) || (isnan(best) && !isnan(f)),
+ *   better strict > (maximise != 0) or < (maximise == 0): a tie keeps the earliest k, a NaN wins only at k == 0; where keep,
+ *   best = f; ist[KEEP][n] = keep; ist[K][n] = k + 1.  A k outside [0, steps] writes nothing but KEEP = 0.
+ * ud_flow_update: one pass.  Where keep[n] != 0 (ud_flow_control's KEEP row): w_best(p) = w(p), the flow that produced the f just
+ *   judged.  closing == 0: w(p) <- min(max(w(p) + step sign(gw(p)), -bound), bound) per component, sign(0) = 0, a NaN stays
+ *   (bitwise torch's fp32 clamp(w + step sign(gw), -bound, bound)), then x_adv(p) = ud_flow_warp's value at p for the new w.
+ *   closing != 0: w and gw are not touched (gw may be NULL) and x_adv(p) = ud_flow_warp's value at p for w_best.
+ *   x_adv != x, w_best != w, gw neither of them.
+ * UD_EINVAL before any HIP call: a NULL pointer, out == x, gw == w or w_best, x_adv == x, w_best == w, N < 1 or > 65535, S < 2 or > 32768,
+ * sign not +-1, tau < 0 or not finite, tv_eps <= 0 or not finite, a NaN step, bound < 0 or NaN; steps < 1, (steps + 1) N > 2^31 - 1. */
+#define UD_FLOW_I_K 0
+#define UD_FLOW_I_KEEP 1
+#define UD_FLOW_F_BEST 0
+int ud_flow_warp(const float* x, const float* w, float* out, int N, int S, ud_stream_t stream);
+int ud_flow_grad(const float* g, const float* x, const float* w, float* gw, int N, int S, int sign, float tau, float tv_eps,
+                 ud_stream_t stream);
+int ud_flow_control(const float* f, int* ist, float* fst, float* history, int steps, int N, int maximise, ud_stream_t stream);
+int ud_flow_update(float* w, float* w_best, const float* gw, const int* keep, const float* x, float* x_adv, int N, int S,
+                   float step, float bound, int closing, ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

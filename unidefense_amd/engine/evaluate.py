@@ -1,4 +1,4 @@
-"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal / test_certified: one scoring
+"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal / test_flow / test_certified: one scoring
 forward, one batch source, one loop-and-gather, one metrics dictionary, and a table of test_robust's methods.  The Evaluator
 takes its model and iterator as arguments and imports nothing that loads the HIP library, so the stage rules run on the CPU
 against stubs (tests/test_evaluate_cpu.py, tests/test_universal_cpu.py).  What every stage keeps: its order inside a batch, who owns which generator, the sequence of
@@ -175,6 +175,30 @@ class Evaluator:
         args = dict(args, delta=d, linf=float(d.abs().max()), l2=float(d.double().norm()), fooled=fooled("adv"),
                     fooled_control=fooled("control"), fit_counted=[int(c) for c in torch.cat(counted).cpu()])
         return dict(self._result(cols, "Test(universal)", args), control=self.metrics(*cols["control"], "Test(control)"))
+
+    def test_flow(self, batches, flow):
+        flow = dict(flow) if flow else {}
+        runner = None
+
+        def body(x, y):
+            nonlocal runner
+            try:                                         # the runner first, then the clean score; only the accessor is wrapped
+                runner = self.net.flow_runner(x.shape[0], x.shape[-1], **flow)
+            except TypeError as e:                       # an unknown key is a bad dict, like a bad value
+                raise ValueError(f"flow takes FlowRunner's keyword arguments: {e}") from None
+            clean = self.score(x)
+            adv = self.score(runner(x, y))
+            # the runner reuses its buffers: the flow's two sizes are cloned per batch, and gathered ahead of the scores
+            return {"flow_linf": runner.flow_linf.clone(), "flow_tv": runner.flow_tv.clone(), "clean": clean, "adv": adv}
+
+        cols = self.run(batches, body)
+        labels = cols["clean"][1]
+        right = (cols["clean"][0] < 0.5).long() == labels
+        wrong = (cols["adv"][0] < 0.5).long() != labels
+        linf, tv = cols["flow_linf"][0].double(), cols["flow_tv"][0].double()
+        args = dict(runner.args, flow_linf_mean=float(linf.mean()), flow_linf_max=float(linf.max()), flow_tv_mean=float(tv.mean()),
+                    flow_tv_max=float(tv.max()), fooled=float(wrong[right].double().mean()) if bool(right.any()) else float("nan"))
+        return self._result(cols, "Test(flow)", args)
 
     def test_certified(self, batches, certify):
         from ..smooth import certified_curve

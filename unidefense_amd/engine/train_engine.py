@@ -280,6 +280,18 @@ class TrainEngine(AbstractEngine):
         universal = universal if universal is not None else self.config["config"].get("universal")
         return self._evaluator().test_universal(batches, fit_batches, epochs, universal)
 
+    def test_flow(self, batches=4, flow=None):
+        """test() on clean inputs and on each sample's flow-field (stAdv) adversarial image (unidefense_amd/flow.py): every test
+        batch is scored as test() does (inference_graph / inference_precision keep their meaning), attacked with the true labels
+        by the model's FlowRunner — a per-pixel displacement field of at most max_flow pixels, ascended through a differentiable
+        warp — and scored again the same way on its x_adv.  flow (default config['config']['flow'], then the runner's defaults):
+        the runner's keyword arguments, e.g. {"max_flow": 2.0, "steps": 20, "tau": 0.05}.  Returns {"clean": what test() returns,
+        "adv": the same keys on x_adv, "attack": the resolved arguments plus "flow_linf_mean" / "flow_linf_max" and "flow_tv_mean"
+        / "flow_tv_max" (the best flows' largest displacement and smoothness term) and "fooled" (the fraction of the samples
+        classified correctly clean that the flow flips; NaN where there are none)}.  The flows' two sizes and the scores are
+        gathered over the ranks as in test(), in this order."""
+        return self._evaluator().test_flow(batches, flow if flow is not None else self.config["config"].get("flow"))
+
     def test_certified(self, batches=4, certify=None):
         """A LOWER bound on robustness, where test_robust gives upper bounds (unidefense_amd/smooth.py): every test batch is scored
         as test() does (inference_graph / inference_precision keep their meaning), then certified by the model's CertifyRunner —

@@ -1959,6 +1959,94 @@ def uap_apply(delta, dss, x, x_adv, eps, lo, hi):
     return x_adv
 
 
+# ---- flow-field attack (csrc/flow.hip): images fp32 [N, 3, S, S], flows fp32 [N, 2, S, S] in pixels (column, row) ---------------
+FLOW_I = _rows("UD_FLOW_I_")
+FLOW_F = {"f_best": _const("UD_FLOW_F_BEST")}
+
+
+def flow_state(N, steps, device):
+    """(ist, fst, history): zeroed control state for N samples and `steps` iterations (history [steps + 1, N])"""
+    return _state(N, device, FLOW_I, FLOW_F) + (torch.zeros(int(steps) + 1, N, dtype=torch.float32, device=device),)
+
+
+def _chk_flow(x, w, *more):
+    """x (and its likes in `more` with three channels) [N, 3, S, S], w (and its likes with two) [N, 2, S, S]: (N, S)"""
+    _chk(x, w, *more)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[0] < 1 or x.shape[2] < 2:
+        raise ValueError(f"expected [N, 3, S, S] images with N >= 1 and S >= 2, got {tuple(x.shape)}")
+    N, S = x.shape[0], x.shape[2]
+    for t in (w,) + more:
+        if tuple(t.shape) not in ((N, 2, S, S), (N, 3, S, S)):
+            raise ValueError(f"expected a flow [{N}, 2, {S}, {S}] or an image [{N}, 3, {S}, {S}], got {tuple(t.shape)}")
+    if tuple(w.shape) != (N, 2, S, S):
+        raise ValueError(f"a flow is [{N}, 2, {S}, {S}] (column and row displacement in pixels), got {tuple(w.shape)}")
+    return N, S
+
+
+def _chk_apart(**named):
+    names = list(named)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            if named[a] is not None and named[b] is not None and named[a].data_ptr() == named[b].data_ptr():
+                raise ValueError(f"{a} and {b} must be buffers of their own")
+
+
+def flow_warp(x, w, out):
+    """out(p) = x sampled bilinearly at p + w(p), coordinates clamped to the image (the header's rule); one launch, out is not x."""
+    N, S = _chk_flow(x, w, out)
+    if out.shape != x.shape:
+        raise ValueError(f"out must be like x {tuple(x.shape)}, got {tuple(out.shape)}")
+    _chk_apart(x=x, out=out)
+    _call("ud_flow_warp", _p(x), _p(w), _p(out), N, S, _stream())
+    return out
+
+
+def flow_grad(g, x, w, gw, sign=1, tau=0.0, tv_eps=1e-8):
+    """gw = sign d<g, warp(x, w)>/dw - tau d L_flow(w)/dw (sign +1 or -1; L_flow the sum over neighbour pairs of
+    sqrt(|w(p) - w(q)|^2 + tv_eps)); g like x, gw like w and not w; one launch."""
+    N, S = _chk_flow(x, w, g, gw)
+    if g.shape != x.shape or gw.shape != w.shape:
+        raise ValueError(f"g must be like x and gw like w, got {tuple(g.shape)} and {tuple(gw.shape)}")
+    _chk_apart(w=w, gw=gw)
+    if sign not in (1, -1):
+        raise ValueError(f"sign must be +1 or -1, got {sign!r}")
+    if not (math.isfinite(float(tau)) and float(tau) >= 0.0):
+        raise ValueError(f"tau must be a finite number >= 0, got {tau!r}")
+    if not (math.isfinite(float(tv_eps)) and float(tv_eps) > 0.0):
+        raise ValueError(f"tv_eps must be a finite number > 0, got {tv_eps!r}")
+    _call("ud_flow_grad", _p(g), _p(x), _p(w), _p(gw), N, S, int(sign), float(tau), float(tv_eps), _stream())
+    return gw
+
+
+def flow_control(f, ist, fst, history, maximise=True):
+    """One step of the per-sample keep-best state on f [N] fp32 with k = ist's counter in [0, steps] (history [steps + 1, N]):
+    history[k] = f; keep = k == 0, or f strictly better than f_best (maximise: greater), or f_best NaN and f not; f_best follows."""
+    _chk(f, history)
+    N = f.numel()
+    _chk_state(ist, fst, N, FLOW_I, FLOW_F)
+    if history.dim() != 2 or history.shape[0] < 2 or history.shape[1] != N:
+        raise ValueError(f"history must be [steps + 1, {N}] with steps >= 1, got {tuple(history.shape)}")
+    _call("ud_flow_control", _p(f), _p(ist), _p(fst), _p(history), history.shape[0] - 1, N, int(bool(maximise)), _stream())
+
+
+def flow_update(w, w_best, gw, keep, x, x_adv, step, bound, closing=False):
+    """One pass: w_best = w where keep[n] != 0 (keep [N] int32); then w <- clamp(w + step sign(gw), -bound, bound) (bitwise the
+    torch fp32 expression) and x_adv = flow_warp(x, w); closing: w stays (gw may be None) and x_adv = flow_warp(x, w_best)."""
+    N, S = _chk_flow(x, w, w_best, x_adv, *(() if gw is None else (gw,)))
+    if x_adv.shape != x.shape or w_best.shape != w.shape or (gw is not None and gw.shape != w.shape):
+        raise ValueError("x_adv must be like x, w_best and gw like w")
+    if gw is None and not closing:
+        raise ValueError("only the closing pass runs without gw")
+    _chk_apart(x=x, x_adv=x_adv)
+    _chk_apart(w=w, w_best=w_best, gw=gw)
+    _chk_i32(keep, (N,), "keep")
+    if math.isnan(float(step)) or not float(bound) >= 0.0:
+        raise ValueError(f"step must be a number and bound >= 0, got {step!r} and {bound!r}")
+    _call("ud_flow_update", _p(w), _p(w_best), _p(gw), _p(keep), _p(x), _p(x_adv), N, S, float(step), float(bound),
+          int(bool(closing)), _stream())
+    return x_adv
+
+
 # ---- randomized smoothing (csrc/smooth.hip): the noise of a draw made in the kernel, the draw's votes counted on the device ------
 SMOOTH_I = _rows("UD_SMOOTH_I_")
 SMOOTH_MODE = {"gaussian": _const("UD_SMOOTH_GAUSSIAN"), "uniform": _const("UD_SMOOTH_UNIFORM")}

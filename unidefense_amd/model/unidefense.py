@@ -283,6 +283,13 @@ class RunnerMethods:
         from ..universal import universal_runner
         return universal_runner(self, batch, size, **kwargs)
 
+    def flow_runner(self, batch, size, **kwargs):
+        """The graph-replayed flow-field (stAdv) attack — a per-pixel displacement field of at most max_flow pixels, ascended
+        through a differentiable warp — for [batch, 3, size, size] inputs (unidefense_amd/flow.py: FlowRunner; kwargs: max_flow,
+        steps, step, tau, tv_eps, targeted, objective, precision, grad_scale)."""
+        from ..flow import flow_runner
+        return flow_runner(self, batch, size, **kwargs)
+
     def certify_runner(self, batch, size, **kwargs):
         """The graph-replayed randomized-smoothing certificate — per sample a radius inside which the smoothed decision provably
         does not change — for [batch, 3, size, size] inputs (unidefense_amd/smooth.py: CertifyRunner; kwargs: sigma, noise, n0, n,
