@@ -113,64 +113,71 @@ def to_nchw(t):
 def test_resnet_operators():
     """conv (7x7/2, 3x3/2, 1x1/2) with data + weight gradients, BN+ReLU, max-pool, avg-pool, add+ReLU, concat."""
     dev = _dev()
-    from tests.test_a_kernels_gpu import check, rnd, run_tape
+    from tests.test_a_kernels_gpu import check_all, grads, rnd, run_tape
     from unidefense_amd import tape as T
     N = 2
     for (Ci, Co, k, s, p, H, need_dx) in ((3, 64, 7, 2, 3, 32, False), (64, 128, 3, 2, 1, 32, True),
                                           (64, 128, 1, 2, 0, 32, True), (448, 512, 3, 2, 1, 16, True)):
         x, w = rnd(N, Ci, H, H, seed=1), rnd(Co, Ci, k, k, seed=2, scale=0.1)
-        xr, wr = x.double().requires_grad_(), w.double().requires_grad_()
-        yr = F.conv2d(xr, wr, None, s, p)
-        gy = rnd(*yr.shape, seed=3)
-        yr.backward(gy.double())
+        Ho = (H + 2 * p - k) // s + 1
+        gy = rnd(N, Co, Ho, Ho, seed=3)
+
+        def ref(dt):
+            xr, wr = x.to(dt).requires_grad_(), w.to(dt).requires_grad_()
+            yr = F.conv2d(xr, wr, None, s, p)
+            return dict(zip((f"conv k{k} s{s} y", f"conv k{k} s{s} dx", f"conv k{k} s{s} dw"),
+                            [yr.detach()] + grads(yr, [xr, wr], gy)))
         outs, gin, gp = run_tape(lambda t, a, b: T.conv_dense_any(t, a, b, s, p, need_dx=need_dx), [to_pix(x).to(dev)],
                                  [w.to(dev)], lambda o: [to_pix(gy).to(dev)])
-        check(f"conv k{k} s{s} y", to_nchw(outs[0]), yr)
-        check(f"conv k{k} s{s} dw", gp[0], wr.grad)
+        got = {f"conv k{k} s{s} y": to_nchw(outs[0]), f"conv k{k} s{s} dw": gp[0]}
         if need_dx:
-            check(f"conv k{k} s{s} dx", to_nchw(gin[0]), xr.grad)
+            got[f"conv k{k} s{s} dx"] = to_nchw(gin[0])
+        check_all(got, ref)
     # BN + ReLU
     C, H = 128, 16
     x = rnd(N, C, H, H, seed=1) + 0.2
     g_, b_ = rnd(C, seed=2) * 0.1 + 1, rnd(C, seed=3) * 0.1
-    xr, gr, br = x.double().requires_grad_(), g_.double().requires_grad_(), b_.double().requires_grad_()
-    yr = F.relu(F.batch_norm(xr, None, None, gr, br, True, 0.1, 1e-5))
-    gy = rnd(*yr.shape, seed=4)
-    yr.backward(gy.double())
+    gy = rnd(N, C, H, H, seed=4)
+
+    def ref(dt):
+        xr, gr, br = x.to(dt).requires_grad_(), g_.to(dt).requires_grad_(), b_.to(dt).requires_grad_()
+        yr = F.relu(F.batch_norm(xr, None, None, gr, br, True, 0.1, 1e-5))
+        return dict(zip(("bn-relu y", "bn-relu dx", "bn-relu dgamma"), [yr.detach()] + grads(yr, [xr, gr], gy)))
     rm, rv = torch.zeros(C, device=dev), torch.ones(C, device=dev)
     outs, gin, gp = run_tape(lambda t, a, w_, bb: T.batchnorm_act(t, a, w_, bb, rm, rv, 1e-5, 0.1, True, 2),
                              [to_pix(x).to(dev)], [g_.to(dev).requires_grad_(), b_.to(dev).requires_grad_()],
                              lambda o: [to_pix(gy).to(dev)])
-    check("bn-relu y", to_nchw(outs[0]), yr)
-    check("bn-relu dx", to_nchw(gin[0]), xr.grad)
-    check("bn-relu dgamma", gp[0], gr.grad)
+    check_all({"bn-relu y": to_nchw(outs[0]), "bn-relu dx": to_nchw(gin[0]), "bn-relu dgamma": gp[0]}, ref)
     # max-pool 3/2/1, avg-pool 4, add+relu, concat
     x = rnd(N, 64, 16, 16, seed=5)
-    xr = x.double().requires_grad_()
-    yr = F.max_pool2d(xr, 3, 2, 1)
-    gy = rnd(*yr.shape, seed=6)
-    yr.backward(gy.double())
-    outs, gin, _ = run_tape(lambda t, a: T.maxpool3s2(t, a), [to_pix(x).to(dev)], [], lambda o: [to_pix(gy).to(dev)])
-    check("maxpool y", to_nchw(outs[0]), yr)
-    check("maxpool dx", to_nchw(gin[0]), xr.grad)
-    xr = x.double().requires_grad_()
-    yr = F.adaptive_avg_pool2d(xr, 4)
-    gy = rnd(*yr.shape, seed=7)
-    yr.backward(gy.double())
-    outs, gin, _ = run_tape(lambda t, a: T.avgpool(t, a, 4), [to_pix(x).to(dev)], [], lambda o: [to_pix(gy).to(dev)])
-    check("avgpool y", to_nchw(outs[0]), yr)
-    check("avgpool dx", to_nchw(gin[0]), xr.grad)
+    gy_max, gy_avg = rnd(N, 64, 8, 8, seed=6), rnd(N, 64, 4, 4, seed=7)
     a, b = rnd(N, 64, 8, 8, seed=8), rnd(N, 128, 8, 8, seed=9)
-    ar, brr = a.double().requires_grad_(), b.double().requires_grad_()
-    yr = F.relu(torch.cat([ar, brr], 1) + 0.1)
-    gy = rnd(*yr.shape, seed=10)
-    yr.backward(gy.double())
+    gy = rnd(N, 192, 8, 8, seed=10)
+
+    def ref(dt):
+        out = {}
+        xr = x.to(dt).requires_grad_()
+        yr = F.max_pool2d(xr, 3, 2, 1)
+        out.update(zip(("maxpool y", "maxpool dx"), [yr.detach()] + grads(yr, [xr], gy_max)))
+        xr = x.to(dt).requires_grad_()
+        yr = F.adaptive_avg_pool2d(xr, 4)
+        out.update(zip(("avgpool y", "avgpool dx"), [yr.detach()] + grads(yr, [xr], gy_avg)))
+        ar, brr = a.to(dt).requires_grad_(), b.to(dt).requires_grad_()
+        yr = F.relu(torch.cat([ar, brr], 1) + 0.1)
+        out.update(zip(("concat+add_relu y", "concat+add_relu da", "concat+add_relu db"),
+                       [yr.detach()] + grads(yr, [ar, brr], gy)))
+        return out
+    got = {}
+    outs, gin, _ = run_tape(lambda t, a_: T.maxpool3s2(t, a_), [to_pix(x).to(dev)], [], lambda o: [to_pix(gy_max).to(dev)])
+    got.update({"maxpool y": to_nchw(outs[0]), "maxpool dx": to_nchw(gin[0])})
+    outs, gin, _ = run_tape(lambda t, a_: T.avgpool(t, a_, 4), [to_pix(x).to(dev)], [], lambda o: [to_pix(gy_avg).to(dev)])
+    got.update({"avgpool y": to_nchw(outs[0]), "avgpool dx": to_nchw(gin[0])})
     bias = torch.full((N, 8, 8, 192), 0.1, device=dev)
     outs, gin, _ = run_tape(lambda t, p, q: T.add_relu(t, T.concat_channels(t, [p, q]), bias),
                             [to_pix(a).to(dev), to_pix(b).to(dev)], [], lambda o: [to_pix(gy).to(dev)])
-    check("concat+add_relu y", to_nchw(outs[0]), yr)
-    check("concat+add_relu da", to_nchw(gin[0]), ar.grad)
-    check("concat+add_relu db", to_nchw(gin[1]), brr.grad)
+    got.update({"concat+add_relu y": to_nchw(outs[0]), "concat+add_relu da": to_nchw(gin[0]),
+                "concat+add_relu db": to_nchw(gin[1])})
+    check_all(got, ref)
 
 
 @pytest.mark.gpu
