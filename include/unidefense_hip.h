@@ -887,6 +887,112 @@ int ud_flow_control(const float* f, int* ist, float* fst, float* history, int st
 int ud_flow_update(float* w, float* w_best, const float* gw, const int* keep, const float* x, float* x_adv, int N, int S,
                    float step, float bound, int closing, ud_stream_t stream);
 
+/* ---- decision-based minimum-norm attack, HopSkipJump (csrc/hsj.hip; unidefense_amd/hsj.py: HSJRunner) ----------------------
+ * A query is a static launch sequence inside a captured graph: propose(mode), forward, control(mode).  All samples walk ONE
+ * schedule that the host knows; what differs per sample is device state, one column per sample:
+ *   ist [13][N] int32: UD_HSJ_I_ACTIVE (still attacked), _HAS (an adversarial start is known; live = ACTIVE and HAS), _MOVED (the
+ *     bisection's upper end has moved), _STEPDONE (the step search has succeeded), _ACCEPT (the point just judged becomes x_cur:
+ *     the flag of the ud_apgd_keep that follows), _KEEP (the settled point is the best so far: likewise for x_adv), _K (the next
+ *     row of decisions), _DRAW (the next noise draw: ONE counter for the whole call, so no direction is used twice), _PB (the
+ *     next row of phi), _T (the iteration), _QUERIES (forwards that counted), _FLAGS (bit 0: a counted row held a NaN), _DONE0
+ *     (the clean input is already misclassified)
+ *   fst [8][N] fp32: UD_HSJ_F_LO, _HI (the bisection's interval of alpha: HI is the adversarial end), _DELTA (probe size), _XI
+ *     (step size), _INVN (1 / |v|, L2), _DIST (the settled point's distance), _BEST (the least so far), _RADIUS (what the call
+ *     returns: BEST, 0 for DONE0, +inf without a start)
+ *   The caller zeroes ist and fst to start a call; UD_HSJ_C_CLEAN initialises the rest.
+ * Every fp32 expression below is rounded once per operation, in the order written, without contraction; clamp is NaN-transparent.
+ * ud_hsj_propose(mode): contiguous fp32 [N][per]; dst is never a or b.  One thread per quad of four elements, a float4 where
+ *   per % 4 == 0 and the bases are 16-byte aligned, scalar accesses otherwise: the same bits.  A sample that does not take part
+ *   is left after reading its state.  With m = 0.5 (lo + hi), h = 0.5 (hi - lo):
+ *   UD_HSJ_P_COPY      every sample            dst = a
+ *   UD_HSJ_P_COPY_SEEK ACTIVE and not HAS      dst = a
+ *   UD_HSJ_P_NOISE     ACTIVE and not HAS      dst = clamp(m + h t, lo, hi), t the uniform noise of (seed, ids[n], DRAW, e)
+ *   UD_HSJ_P_BISECT    live                    dst = point(0.5 (LO + HI)), with a = x_cur, b = x0 and
+ *                        UD_HSJ_L2:   point(s) = clamp(b + s (a - b), lo, hi)
+ *                        UD_HSJ_LINF: point(s) = clamp(clamp(a, b - s, b + s), lo, hi)
+ *   UD_HSJ_P_SETTLE    live                    dst = MOVED ? point(HI) : a    (x_cur itself has been verified, point(1) has not)
+ *   UD_HSJ_P_PROBE     live                    dst = clamp(a + s t, lo, hi); LINF: s = DELTA, t uniform; L2: s = DELTA aux
+ *                                              (aux = 1 / sqrt(per) as fp32), t Gaussian; the draw is DRAW
+ *   UD_HSJ_P_STEP      live and not STEPDONE   dst = clamp(a + s b, lo, hi), b = v; LINF: s = XI; L2: s = XI INVN
+ *   The noise: ud_smooth_noise's Philox4x32-10 words, key (seed low, seed high), counter (e / 4, draw, id low, id high), and its
+ *   uniform rule, bit for bit.  The Gaussian rule is NOT ud_smooth_noise's: the same Box-Muller on the same exact uniforms, but
+ *   with log, sqrt and sincospi in DOUBLE and ONE rounding of r cos / r sin to fp32 (ud_smooth_noise: logf, sqrtf, sincospif).
+ *   The fp32 value is then float32(float64 Box-Muller) but for about one element in 10^8, which lets a host restatement
+ *   reproduce a whole attack's decisions; the two kernels' Gaussian fields for one counter differ in the last bits.
+ * ud_hsj_control(mode): one thread per sample.  UD_HSJ_C_CLEAN .. _STEP judge logits [N][C]: the class is the first maximum
+ *   (C == 1: logit > 0), bit = class != y[n] (y int64), a row with a NaN gives bit 0 and, where the sample takes part, FLAGS |= 1.
+ *   From there on only the bit is used.  ACCEPT = 0 first; a sample that takes part counts the query; then
+ *   _CLEAN       every sample: QUERIES = 1, DONE0 = bit, ACTIVE = !bit, HAS = 0, BEST = +inf
+ *   _START       ACTIVE and not HAS: bit -> HAS = ACCEPT = 1;  _START_NOISE: the same, and DRAW += 1 for every sample
+ *   _BISECT      live: mid = 0.5 (LO + HI); bit ? (HI = mid, MOVED = 1) : LO = mid
+ *   _PROBE       live: phi[PB][n] = bit (int8 [max_probes][N]); PB += 1 and DRAW += 1 for every sample
+ *   _STEP        live and not STEPDONE: bit ? STEPDONE = ACCEPT = 1 : XI = 0.5 XI
+ *   and decisions[K][n] = bit, or -1 for a sample that took no part (int8 [Q][N]); K += 1 for every sample.
+ *   The other modes read nrm [2][N] double (ud_hsj_dist) and no logits:
+ *   _BEGIN       ACTIVE and not HAS -> ACTIVE = 0; live: LO = 0, HI = L2 ? 1 : (float)max, MOVED = 0
+ *   _DIST        live: dist = (float)(L2 ? sqrt(sumsq) : max); KEEP = dist < BEST (BEST follows); ACCEPT = 1; DELTA = max(T == 0 ?
+ *                delta0 : dist inv_d, dfloor); XI = dist xis[T] (xis fp32 [steps]); STEPDONE = 0.  Every sample: PB = 0, RADIUS =
+ *                history[T][n] = live ? BEST : (DONE0 ? 0 : +inf) (fp32 [steps + 1][N]), T += 1
+ *   _VNORM       live: INVN = L2 ? (sumsq > 0 ? (float)(1 / sqrt(sumsq)) : 0) : 1
+ *   A counter outside its table writes no row.
+ * ud_hsj_dist: out[n] = sum_e (a - b)^2, out[N + n] = max_e |a - b|, differences, squares and sums in double (b NULL: of a), one
+ *   workgroup per sample and a fixed order; ist given: a sample with ACTIVE == 0 is skipped.
+ * ud_hsj_estimate: live samples (ist NULL: all): v[n][e] = sum over b = 0 .. B - 1, ascending, of w_b u_b[e], one fp32 product and
+ *   one fp32 add per term; u_b the noise of draw draw0 + b as ud_hsj_propose makes it (LINF uniform, L2 the double Box-Muller); w_b = phi[b][n] - mean, mean = (float)ones
+ *   inv_b; all phi equal: w_b = +1 (all ones) or -1 (all zeros).  LINF: the sign of the sum (+-1, 0) is written.  The B
+ *   directions are re-made in registers, the weights held in LDS: the pass reads phi and writes v, nothing else; B <= 4096.
+ * UD_EINVAL before any HIP call: a NULL pointer that the mode reads, N < 1 or > 65535, per < 1 or > 2^34, an unknown mode or
+ * norm, lo >= hi or NaN, dst == a or b, C < 1, Q < 1, Q N or (steps + 1) N > 2^31 - 1, max_probes or B outside [1, 4096],
+ * delta0, inv_d or dfloor <= 0 or NaN, draw0 < 0. */
+#define UD_HSJ_MAX_PROBES 4096
+#define UD_HSJ_LINF 0
+#define UD_HSJ_L2 1
+#define UD_HSJ_I_ACTIVE 0
+#define UD_HSJ_I_HAS 1
+#define UD_HSJ_I_MOVED 2
+#define UD_HSJ_I_STEPDONE 3
+#define UD_HSJ_I_ACCEPT 4
+#define UD_HSJ_I_KEEP 5
+#define UD_HSJ_I_K 6
+#define UD_HSJ_I_DRAW 7
+#define UD_HSJ_I_PB 8
+#define UD_HSJ_I_T 9
+#define UD_HSJ_I_QUERIES 10
+#define UD_HSJ_I_FLAGS 11
+#define UD_HSJ_I_DONE0 12
+#define UD_HSJ_F_LO 0
+#define UD_HSJ_F_HI 1
+#define UD_HSJ_F_DELTA 2
+#define UD_HSJ_F_XI 3
+#define UD_HSJ_F_INVN 4
+#define UD_HSJ_F_DIST 5
+#define UD_HSJ_F_BEST 6
+#define UD_HSJ_F_RADIUS 7
+#define UD_HSJ_P_COPY 0
+#define UD_HSJ_P_COPY_SEEK 1
+#define UD_HSJ_P_NOISE 2
+#define UD_HSJ_P_BISECT 3
+#define UD_HSJ_P_SETTLE 4
+#define UD_HSJ_P_PROBE 5
+#define UD_HSJ_P_STEP 6
+#define UD_HSJ_C_CLEAN 0
+#define UD_HSJ_C_START 1
+#define UD_HSJ_C_START_NOISE 2
+#define UD_HSJ_C_BISECT 3
+#define UD_HSJ_C_PROBE 4
+#define UD_HSJ_C_STEP 5
+#define UD_HSJ_C_BEGIN 6
+#define UD_HSJ_C_DIST 7
+#define UD_HSJ_C_VNORM 8
+int ud_hsj_propose(int mode, int norm, float* dst, const float* a, const float* b, const long long* ids, const int* ist,
+                   const float* fst, int N, long per, float lo, float hi, float aux, long seed, ud_stream_t stream);
+int ud_hsj_control(int mode, int norm, const float* logits, int C, const long long* y, const double* nrm, int* ist, float* fst,
+                   char* phi, char* decisions, float* history, const float* xis, int N, int Q, int max_probes, int steps,
+                   float delta0, float inv_d, float dfloor, ud_stream_t stream);
+int ud_hsj_dist(const float* a, const float* b, const int* ist, int N, long per, double* out, ud_stream_t stream);
+int ud_hsj_estimate(float* v, const char* phi, const long long* ids, const int* ist, int N, long per, int B, int draw0, int norm,
+                    float inv_b, long seed, ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

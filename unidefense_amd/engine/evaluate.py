@@ -66,10 +66,11 @@ class Evaluator:
             raise ValueError("test_robust needs an attack: pass attack={...} or set config['config']['attack']")
         attack = dict(attack)
         method = attack.pop("method", "pgd")
-        if method not in ROBUST:
+        if method not in ROBUST and method not in ROBUST_DECISION:
             names = [repr(name) for name in ROBUST]
             raise ValueError(f"attack method must be {', '.join(names[:-1])} or {names[-1]}, got {method!r}")
-        run = ROBUST[method](self, attack)                       # refuses what it does before any batch is drawn
+        # the run refuses what it does before any batch is drawn
+        run = (ROBUST.get(method) or ROBUST_DECISION[method])(self, attack)
         cols = self.run(batches, run.body)
         return self._result(cols, "Test(adv)", run.attack(cols))
 
@@ -317,8 +318,45 @@ class _MinNorm:
                     median_radius=float(radius.double().median()) if radius.numel() else float("nan"))
 
 
+class _HSJ(_MinNorm):
+    """"hsj": HopSkipJump from the hard label, scored like "fmn" (found, radius <= eps).  Each sample's x_init is the next
+    batch-mate in cyclic order whose clean prediction differs from the sample's label (chosen from the clean scoring forward;
+    none: the runner falls back to its noise trials); ids come from (batch index, rank, row), as test_certified's streams do."""
+
+    def __init__(self, ev, attack):
+        super().__init__("hsj_runner", ev, attack)
+        from ..hsj import _hsj_arguments
+        try:                                             # an unknown key is a bad dict, like a bad value: before any batch is drawn
+            _hsj_arguments(2 * ev.batch, ev.size, **attack)
+        except TypeError as e:
+            raise ValueError(f"attack method 'hsj' takes HSJRunner's keyword arguments and 'eps': {e}") from None
+        dist = torch.distributed
+        self.rank, self.world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
+        self.seen = 0
+
+    def body(self, x, y):
+        clean = self.ev.score(x)
+        runner = self.runner = self.ev.net.hsj_runner(x.shape[0], x.shape[-1], **self.kwargs)
+        n = x.shape[0]
+        pred = (clean < 0.5).long()                      # the label test() scores: 1 where p(real) < 0.5
+        mate = (torch.arange(n, device=x.device).reshape(-1, 1) + torch.arange(1, n + 1, device=x.device).reshape(1, -1)) % n
+        differs = pred[mate] != y.reshape(-1, 1)         # [sample, offset]: the first True is the next such batch-mate
+        first = differs.to(torch.int32).argmax(1)        # no True: offset n - 1 + 1 = the sample itself, which is no start
+        first = torch.where(differs.any(1), first, torch.full_like(first, n - 1))
+        x_init = x[mate[torch.arange(n, device=x.device), first]].contiguous()
+        ids = torch.arange(n, dtype=torch.int64, device=x.device) + (self.seen * self.world + self.rank) * n
+        self.seen += 1
+        radius = runner(x, y, ids, x_init)
+        take = runner.found if self.eps is None else runner.found & (radius <= float(self.eps))
+        adv = self.ev.score(torch.where(take.reshape(-1, 1, 1, 1), runner.x_adv, x))
+        # the runner reuses its buffers: radius and found are cloned per batch, and gathered ahead of the scores
+        return {"radius": radius.clone(), "found": runner.found.clone(), "clean": clean, "adv": adv}
+
+
 ROBUST = {"pgd": partial(_Attack, "attack_runner", None), "apgd": partial(_Attack, "apgd_runner", "device"),
           "square": partial(_Attack, "square_runner", "cpu"), "apgd+square": partial(_Ensemble, ("apgd", "square")),
           "fmn": partial(_MinNorm, "fmn_runner"), "sparse_fmn": partial(_MinNorm, "sparse_fmn_runner")}
+# the decision-based member, in a table of its own: ROBUST stays the list of the score- and gradient-based methods
+ROBUST_DECISION = {"hsj": _HSJ}
 
 

@@ -239,7 +239,12 @@ class TrainEngine(AbstractEngine):
         every found sample) and on the clean input for the rest; "attack" then also holds "eps", "radius" (CPU tensor), "found"
         (CPU tensor) and "median_radius", gathered over the ranks in the scores' order (robust_curve(radius, grid) gives the
         robust accuracy at every eps from this one run).  "method": "sparse_fmn" is the same path on the model's SparseFMNRunner
-        (norm "l1": radius and eps are sums of |x_adv - x|; "l0": numbers of changed elements)."""
+        (norm "l1": radius and eps are sums of |x_adv - x|; "l0": numbers of changed elements).
+        "method": "hsj" selects the decision-based minimum-norm attack (the model's HSJRunner, unidefense_amd/hsj.py: norm "l2" /
+        "linf", steps, probes, max_probes, bisect, halvings, init_trials, seed, ...), which sees the hard label only; it is scored
+        like "fmn" ("eps", "radius", "found", "median_radius").  Each sample starts from the next batch-mate (cyclic) whose clean
+        prediction differs from the sample's label, or from the runner's noise trials where the batch holds none; the noise
+        streams are keyed by (batch index, rank, row), so a sample's attack does not depend on the rank count."""
         return self._evaluator().test_robust(batches, attack if attack is not None else self.config["config"].get("attack"))
 
     def test_corrupted(self, batches=4, corruptions=None, levels=(1, 2, 3, 4, 5), seed=None, subsampling="420"):

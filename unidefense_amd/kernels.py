@@ -2100,6 +2100,123 @@ def smooth_vote(logits, ist, counts, votes, margins, n0):
     _call("ud_smooth_vote", _p(logits), N, Cn, _p(ist), _p(counts), _p(votes), _p(margins), votes.shape[0], int(n0), _stream())
 
 
+# ---- decision-based minimum-norm attack (csrc/hsj.hip): propose / control per query, the distance and the gradient estimate -----
+HSJ_I, HSJ_F = _rows("UD_HSJ_I_"), _rows("UD_HSJ_F_")
+HSJ_P, HSJ_C = _rows("UD_HSJ_P_"), _rows("UD_HSJ_C_")
+HSJ_NORM = {"linf": _const("UD_HSJ_LINF"), "l2": _const("UD_HSJ_L2")}
+HSJ_MAX_PROBES = _const("UD_HSJ_MAX_PROBES")
+_HSJ_READS_B = ("bisect", "settle", "step")
+_HSJ_JUDGES = ("clean", "start", "start_noise", "bisect", "probe", "step")
+
+
+def hsj_state(N, Q, steps, max_probes, device):
+    """(ist, fst, nrm, phi, decisions, history): zeroed state for N samples, Q queries, `steps` iterations"""
+    return (torch.zeros(len(HSJ_I), N, dtype=torch.int32, device=device), torch.zeros(len(HSJ_F), N, dtype=torch.float32, device=device),
+            torch.zeros(2, N, dtype=torch.float64, device=device), torch.zeros(int(max_probes), N, dtype=torch.int8, device=device),
+            torch.zeros(int(Q), N, dtype=torch.int8, device=device), torch.zeros(int(steps) + 1, N, dtype=torch.float32, device=device))
+
+
+def _chk_i8(t, rows_least, N, what):
+    if not (t.is_cuda and t.dtype == torch.int8 and t.is_contiguous() and t.dim() == 2 and t.shape[0] >= rows_least and t.shape[1] == N):
+        raise ValueError(f"{what} must be a contiguous int8 CUDA tensor [>= {rows_least}, {N}], got {t.dtype} {t.device} {tuple(t.shape)}")
+
+
+def _chk_hsj(ist, fst, N, norm):
+    _chk_state(ist, fst, N, HSJ_I, HSJ_F)
+    if norm not in HSJ_NORM:
+        raise ValueError(f"norm must be one of {tuple(HSJ_NORM)}, got {norm!r}")
+
+
+def _chk_ids(ids, N):
+    if not (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and tuple(ids.shape) == (N,)):
+        raise ValueError(f"expected a contiguous int64 CUDA tensor [{N}], got {ids.dtype} {ids.device} {tuple(ids.shape)}")
+
+
+def hsj_propose(mode, norm, dst, a, b, ids, ist, fst, lo, hi, seed=0):
+    """One pass of the header's ud_hsj_propose(mode) into dst [N, ...] fp32: a the pass's source (None for "noise"), b = x0
+    ("bisect", "settle") or v ("step"), ids int64 [N] for the noisy modes; the per-sample scalars come from ist / fst."""
+    _chk_same(*(t for t in (dst, a, b) if t is not None))
+    N = dst.shape[0] if dst.dim() >= 1 else 0
+    if N < 1 or dst.numel() == 0:
+        raise ValueError(f"expected a batch [N, ...], got {tuple(dst.shape)}")
+    _chk_hsj(ist, fst, N, norm)
+    if mode not in HSJ_P:
+        raise ValueError(f"mode must be one of {tuple(HSJ_P)}, got {mode!r}")
+    if (a is None) != (mode == "noise") or (b is None) != (mode not in _HSJ_READS_B):
+        raise ValueError(f"mode {mode!r}: a is the source (none for 'noise'), b is given for {_HSJ_READS_B} only")
+    if mode in ("noise", "probe"):
+        _chk_ids(ids, N)
+    per = dst.numel() // N
+    _call("ud_hsj_propose", HSJ_P[mode], HSJ_NORM[norm], _p(dst), _p(a), _p(b), _p(ids), _p(ist), _p(fst), N, per, float(lo),
+          float(hi), float(torch.tensor(1.0 / math.sqrt(per), dtype=torch.float64).to(torch.float32)), _seed64(seed), _stream())
+    return dst
+
+
+def hsj_control(mode, norm, ist, fst, logits=None, y=None, nrm=None, phi=None, decisions=None, history=None, xis=None,
+                delta0=0.0, inv_d=0.0, dfloor=0.0):
+    """One step of the per-sample state (the header's ud_hsj_control(mode)): the judging modes take logits [N, C] fp32, y int64
+    [N] and decisions int8 [Q, N] ("probe": phi int8 [max_probes, N] too); "begin", "dist", "vnorm" take nrm float64 [2, N]
+    ("dist": history fp32 [steps + 1, N], xis fp32 [steps] and the three constants)."""
+    N = ist.shape[1] if ist.dim() == 2 else 0
+    _chk_hsj(ist, fst, N, norm)
+    if mode not in HSJ_C:
+        raise ValueError(f"mode must be one of {tuple(HSJ_C)}, got {mode!r}")
+    Cn = Q = steps = 0
+    if mode in _HSJ_JUDGES:
+        _chk(logits)
+        if logits.dim() != 2 or logits.shape[0] != N or logits.shape[1] < 1:
+            raise ValueError(f"logits must be [{N}, C], got {tuple(logits.shape)}")
+        _chk_ids(y, N)
+        _chk_i8(decisions, 1, N, "decisions")
+        Cn, Q = logits.shape[1], decisions.shape[0]
+        if mode == "probe":
+            _chk_i8(phi, 1, N, "phi")
+    else:
+        _chk_f64(nrm, 2 * N)
+        if mode == "dist":
+            _chk(history, xis)
+            if history.dim() != 2 or history.shape[0] < 2 or history.shape[1] != N or xis.numel() != history.shape[0] - 1:
+                raise ValueError(f"history must be [steps + 1, {N}] and xis [steps], got {tuple(history.shape)} and {tuple(xis.shape)}")
+            steps = history.shape[0] - 1
+    _call("ud_hsj_control", HSJ_C[mode], HSJ_NORM[norm], _p(logits), Cn, _p(y), _p(nrm), _p(ist), _p(fst), _p(phi), _p(decisions),
+          _p(history), _p(xis), N, Q, 0 if phi is None else phi.shape[0], steps, float(delta0), float(inv_d), float(dfloor), _stream())
+
+
+def hsj_dist(a, b, nrm, ist=None):
+    """nrm[0, n] = sum (a - b)^2, nrm[1, n] = max |a - b| per sample in double (b None: of a); ist given: idle samples are skipped"""
+    _chk_same(*((a,) if b is None else (a, b)))
+    N = a.shape[0]
+    _chk_f64(nrm, 2 * N)
+    if nrm.numel() != 2 * N:
+        raise ValueError(f"nrm must be [2, {N}], got {tuple(nrm.shape)}")
+    if ist is not None:
+        _chk_i32(ist, (len(HSJ_I), N), "ist")
+    _call("ud_hsj_dist", _p(a), _p(b), _p(ist), N, a.numel() // N, _p(nrm), _stream())
+    return nrm
+
+
+def hsj_estimate(v, phi, ids, B, draw0, norm, seed, ist=None):
+    """v [N, ...] fp32 = sum over the first B rows of phi (int8 [>= B, N]) of (phi_b - mean) u_b, u_b the noise of draw draw0 + b
+    (the header's ud_hsj_estimate; "linf": the sign of the sum); ist given: live samples only.  B <= HSJ_MAX_PROBES."""
+    _chk(v)
+    N = v.shape[0] if v.dim() >= 1 else 0
+    if N < 1 or v.numel() == 0:
+        raise ValueError(f"expected a batch [N, ...], got {tuple(v.shape)}")
+    B = int(B)
+    if not 1 <= B <= HSJ_MAX_PROBES:
+        raise ValueError(f"the estimate takes 1 .. {HSJ_MAX_PROBES} probes, got {B}")
+    _chk_i8(phi, B, N, "phi")
+    _chk_ids(ids, N)
+    if norm not in HSJ_NORM:
+        raise ValueError(f"norm must be one of {tuple(HSJ_NORM)}, got {norm!r}")
+    if ist is not None:
+        _chk_i32(ist, (len(HSJ_I), N), "ist")
+    inv_b = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(B), dtype=torch.float32))
+    _call("ud_hsj_estimate", _p(v), _p(phi), _p(ids), _p(ist), N, v.numel() // N, B, int(draw0), HSJ_NORM[norm], inv_b,
+          _seed64(seed), _stream())
+    return v
+
+
 def conv_gather_wgrad(a, x, g):
     """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)]."""
     _chk(a, x)

@@ -297,6 +297,14 @@ class RunnerMethods:
         from ..smooth import certify_runner
         return certify_runner(self, batch, size, **kwargs)
 
+    def hsj_runner(self, batch, size, **kwargs):
+        """The graph-replayed decision-based minimum-norm attack (HopSkipJump: black-box, the hard label only, forward only) for
+        [batch, 3, size, size] inputs: per sample the smallest L2 / L-infinity perturbation found that changes the decision
+        (unidefense_amd/hsj.py: HSJRunner; kwargs: norm, steps, probes, max_probes, bisect, halvings, init_trials, seed, clip,
+        precision, logits)."""
+        from ..hsj import hsj_runner
+        return hsj_runner(self, batch, size, **kwargs)
+
 
 class UniDefenseModelEb4(RunnerMethods, nn.Module):
     """UniDefense model with EfficientNet backbone (reference: model/unidefense.py:28-256)."""
