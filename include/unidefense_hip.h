@@ -1191,6 +1191,26 @@ int ud_pj_bwd_fused_a(const float* d, const float* dp, const ud_bn_ref* bn, cons
                       int CO, float* dw, double* dgate, float* part, ud_stream_t stream);
 int ud_pj_bwd_fused_b(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,
                       const float* w, int N, int HW, int CE, int CO, float* dz, double* s1, double* s2, ud_stream_t stream);
+/* ---- the same two passes with the BatchNorm-1 backward folded in: dz is never written ----
+ * ud_pj_bwd_fused_a_se : ud_pj_bwd_fused_a that also sums the four per-sample dots of ud_coldot_bn_se: dots [5][N][CE] fp64, zeroed
+ *                        by the caller, receives (dgate, A1, A2, B1, B2); dgate's products are ud_pj_bwd_fused_a's.  ud_se_bwd_b_bn
+ *                        turns the dots into the sums s1 / s2.
+ * ud_pj_bwd_fused_c    : one pass over d in place of ud_pj_bwd_fused_b + ud_normbwd_apply: dz formed as there, kept in registers,
+ *                        dd = gamma invstd (dz - s1 / count - xhat s2 / count) written (ud_normbwd_apply's rounding); dgamma / dbeta
+ *                        (optional) from this rank's sums s2_local / s1_local, which they require.
+ * ud_pj_bwd_fused_c_mix: ... in place of ud_normbwd_apply_mix: diff, dalpha_acc (64 slots) and energy (optional) as there.
+ * Training-form BatchNorm only (the eval form is UD_EINVAL); (CE, CO, HW): a triple ud_pj_bwd_fused_se_ok accepts (the pairs of
+ * ud_pj_bwd_fused_ok but the 24-column ones). */
+int ud_pj_bwd_fused_se_ok(int CE, int CO, int HW);
+int ud_pj_bwd_fused_a_se(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* w, int N, int HW, int CE,
+                         int CO, float* dw, double* dots, float* part, ud_stream_t stream);
+int ud_pj_bwd_fused_c(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,
+                      const float* w, const double* s1, const double* s2, const double* s1_local, const double* s2_local, int N,
+                      int HW, int CE, int CO, float* dd, float* dgamma, float* dbeta, ud_stream_t stream);
+int ud_pj_bwd_fused_c_mix(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,
+                          const float* w, const double* s1, const double* s2, const double* s1_local, const double* s2_local,
+                          const float* diff, int N, int HW, int CE, int CO, float* dd, double* dalpha_acc, float* dgamma,
+                          float* dbeta, double* energy, ud_stream_t stream);
 /* Half storage (the mixed-precision mode): ud_normbwd_apply whose half result is laid straight into the ONE fp16 plane (P32 layout,
  * scale 1) that ud_gemm_p3 prec 1 reads — the row-major tensor and the ud_planes_from_half pass over it are not needed. */
 int ud_normbwd_apply_plane_half(const void* x, const void* dy, const float* keep, float inv_keep, const ud_bn_ref* bn,

@@ -4,8 +4,13 @@
   old: ud_coldot_bn    -> ud_se_bwd_a, ud_se_bwd_b    -> ud_se_scale_bwd_bn -> ud_normbwd_apply[_mix]
   new: ud_coldot_bn_se -> ud_se_bwd_a, ud_se_bwd_b_bn ->                       ud_normbwd_apply[_mix]_se
 
-The blocks whose project conv takes ud_pj_bwd_fused_a / _b have no dc tensor and are not routed: listed, not timed.
-This table is the source of mbconv._se_bn1_fold_policy.    python tools/bench_se_bn1_fold.py [--bs 32] [--size 256]"""
+The blocks whose project conv takes ud_pj_bwd_fused_a / _b have no dc tensor; their chains, in the same columns:
+
+  old: ud_pj_bwd_fused_a    -> ud_se_bwd_a, ud_se_bwd_b    -> ud_pj_bwd_fused_b -> ud_normbwd_apply[_mix]
+  new: ud_pj_bwd_fused_a_se -> ud_se_bwd_a, ud_se_bwd_b_bn ->                      ud_pj_bwd_fused_c[_mix]
+
+This table is the source of mbconv._se_bn1_fold_policy and mbconv._pj_bn1_fold_policy.
+    python tools/bench_se_bn1_fold.py [--bs 32] [--size 256]"""
 import argparse
 import collections
 import sys
@@ -59,18 +64,22 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     N = a.bs
-    tot_old = tot_new = 0.0
+    tot_old = tot_new = pj_old = pj_new = 0.0
     print("block shape (sf, stride, Ho, Ce)    blocks | dot old -> new | FCs old -> new | scale_bwd | apply old -> new | chain old -> new  (us)")
+    print("  (* thin project conv: dot = pass A / A with the five dots, scale_bwd = pass B, apply new = pass C)")
     for (sf, stride, Ho, Ce, Cs, Co), idx in block_shapes(a.size).items():
         HW = Ho * Ho
         name = "%-5s s%d %3d^2 Ce %4d" % ("SF" if sf else "plain", stride, Ho, Ce)
-        if K.project_bwd_fused_ok(torch.empty(1), torch.empty(Co, Ce), HW):
-            print("%-34s %2d x   thin project conv (ud_pj_bwd_fused_a / _b): not routed" % (name, len(idx)))
+        pj = K.project_bwd_fused_ok(torch.empty(1), torch.empty(Co, Ce), HW)
+        if pj and not K.project_bwd_fold_ok(torch.empty(Co, Ce), HW):
+            print("%-34s %2d x   thin project conv (ud_pj_bwd_fused_a / _b), a pair the fold is not built for" % (name, len(idx)))
             continue
         mix = sf and stride == 1
         g = torch.Generator(device=dev).manual_seed(Ce + Ho)
         d = torch.randn(N, HW, Ce, generator=g, device=dev)
-        dc = torch.randn(N, HW, Ce, generator=g, device=dev)
+        dc = None if pj else torch.randn(N, HW, Ce, generator=g, device=dev)
+        dp = torch.randn(N * HW, Co, generator=g, device=dev) if pj else None
+        Wp = torch.randn(Co, Ce, generator=g, device=dev) / Ce ** 0.5 if pj else None
         diff = torch.randn(N, HW, Ce, generator=g, device=dev) if mix else None
         s2 = torch.randn(N, Ce, generator=g, device=dev)
         s1 = torch.randn(N, Cs, generator=g, device=dev)
@@ -116,6 +125,26 @@ def main():
             else:
                 K.normbwd_apply_se(d, dc, bn, s2, st["dpool"], 1.0 / HW, N, HW, st["sacc"])
 
+        if pj:          # the same stages on the thin-project kernels: dc is re-made inside the passes
+            def dot_old():
+                st["dgate"] = K.zeros64(N * Ce, d)
+                K.project_bwd_fused_a(d, bn, s2, dp, Wp, N, HW, st["dgate"])
+
+            def dot_new():
+                st["dots"] = K.zeros64(5 * N * Ce, d)
+                K.project_bwd_fused_a_se(d, bn, s2, dp, Wp, N, HW, st["dots"])
+
+            def scale_old():
+                st["sacc"] = K.zeros64(2 * Ce, d)
+                st["dz"] = K.project_bwd_fused_b(d, bn, s2, st["dpool"], 1.0 / HW, dp, Wp, N, HW, st["sacc"])
+
+            def apply_new():
+                if mix:
+                    K.project_bwd_fused_c_mix(d, bn, s2, st["dpool"], 1.0 / HW, dp, Wp, N, HW, st["sacc"], diff, K.zeros64(64, d),
+                                              energy=K.zeros64(Ce, d))
+                else:
+                    K.project_bwd_fused_c(d, bn, s2, st["dpool"], 1.0 / HW, dp, Wp, N, HW, st["sacc"])
+
         def chain_old():
             dot_old(), fc_old(), scale_old(), apply_old()
 
@@ -128,12 +157,17 @@ def main():
         t.update({"dot1": timed(dot_new), "fc1": timed(fc_new), "ap1": timed(apply_new)})
         # the chains twice each, alternating: the second pair is reported, the first shows the spread
         c = [(timed(chain_old), timed(chain_new)) for _ in range(2)]
-        tot_old += len(idx) * c[1][0]
-        tot_new += len(idx) * c[1][1]
+        if pj:
+            pj_old += len(idx) * c[1][0]
+            pj_new += len(idx) * c[1][1]
+        else:
+            tot_old += len(idx) * c[1][0]
+            tot_new += len(idx) * c[1][1]
         print("%-34s %2d x | %5.1f -> %5.1f | %5.1f -> %5.1f | %5.1f | %5.1f -> %5.1f | %6.1f -> %6.1f  (first pair %6.1f -> %6.1f)" %
-              (name, len(idx), t["dot0"], t["dot1"], t["fc0"], t["fc1"], t["sc0"], t["ap0"], t["ap1"], c[1][0], c[1][1], c[0][0], c[0][1]),
+              (name + (" *" if pj else ""), len(idx), t["dot0"], t["dot1"], t["fc0"], t["fc1"], t["sc0"], t["ap0"], t["ap1"], c[1][0], c[1][1], c[0][0], c[0][1]),
               flush=True)
     print("routed blocks of one step: old chains %.1f us, new chains %.1f us, difference %.1f us" % (tot_old, tot_new, tot_old - tot_new))
+    print("thin-project blocks (*) of one step: old chains %.1f us, new chains %.1f us, difference %.1f us" % (pj_old, pj_new, pj_old - pj_new))
 
 
 if __name__ == "__main__":

@@ -10,6 +10,9 @@
 //     pj_bwd_a_kernel: ONE pass over d: a = swish(bn1(d)) and c = a gate re-made on load (bit for bit the forward's), dWp from the
 //                      c image (transposed reads, k = rows), the dc tile in registers, its dot with a -> dgate;
 //     pj_bwd_b_kernel: ONE pass over d: the dc tile again, relaid through LDS to the row-major quads of d, dz written, sums taken.
+//     pj_bwd_a_kernel<.., SE> + pj_bwd_c_kernel: the BatchNorm-1 backward folded in — pass A also sums the four per-sample
+//                      dots its sums are linear in, the SE FC launch folds them, and pass C is pass B whose element-wise phase IS the
+//                      BatchNorm backward apply: dz stays in registers, dd is written; pass B and the apply launch are not run.
 // dc never exists in HBM and c is not read: 200 + 200 MB per block instead of 834.  Arithmetic of the products = gemm_x3's (exact
 // three-way bf16 split, six piece products, fp32 accumulation); element-wise math = ud_se_scale_bn / ud_se_scale_bwd_bn's.
 #include "pw_common.h"
@@ -53,6 +56,9 @@ template <int CE, int CO, int CC = CE> struct PjCfg {
     static constexpr int LDS_A = 3 * CP + AP + 3 * DPL + COEF + CC * 4;
     // kernel B: dc tile, dp image, coefficients, gate, dpool / HW, two fp64 column accumulators
     static constexpr int LDS_B = AP + 3 * DPL + COEF + 2 * CC * 4 + 2 * CC * 8;
+    // kernel C: dc tile, dp image, coefficients, gate, dpool / HW, s1 / count and s2 / count, an fp64 column accumulator (energy),
+    // the waves' sums (sum dd diff)
+    static constexpr int LDS_C = AP + 3 * DPL + COEF + 4 * CC * 4 + CC * 8 + 4 * 8;
 };
 
 struct PjArgs {
@@ -66,6 +72,17 @@ struct PjArgs {
     double* dgate;             // [N][CE] (kernel A) += sum_hw dc a
     double* s1;                // [CE] (kernel B) += sum dz, sum dz xhat
     double* s2;
+    double* dots;              // [5][N][CE] (kernel A, SE) += dgate, A1, A2, B1, B2 (ud_coldot_bn_se's layout)
+    const double* bs1;         // [CE] (kernel C) the BatchNorm-1 backward sums over all ranks ...
+    const double* bs2;
+    const double* bs1l;        // ... and this rank's: dbeta, dgamma (NULL with both outputs NULL)
+    const double* bs2l;
+    const float* diff;         // [N HW][CE] (kernel C, MIX) freq - spat of the SF mix
+    float* dd;                 // [N HW][CE] (kernel C)
+    float* dgamma;             // [CE] (kernel C; may be NULL)
+    float* dbeta;
+    double* dalpha;            // [64] (kernel C, MIX) += sum dd diff
+    double* energy;            // [CE] (kernel C, MIX; may be NULL) += sum dd^2, rounded up
     const double* bsum;        // BatchNorm-1 statistics of d (NULL: the eval form, moments from rmean / rvar)
     const double* bsumsq;
     const float* rmean;
@@ -90,6 +107,12 @@ __device__ __forceinline__ float act_sel(float z, bool swish) {
 __device__ __forceinline__ float act_grad_sel(float z, bool swish) {
     const float sg = ud_sigmoid_fast(z);
     return swish ? sg * (1.0f + z * (1.0f - sg)) : 1.f;
+}
+
+// a product rounded on its own (never contracted into the add that follows): a gradient the old chain stored
+__device__ __forceinline__ float mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+    return x * y;
 }
 
 // coefficients of channels c0 .. c0 + CC - 1
@@ -134,9 +157,16 @@ __device__ __forceinline__ void load_wfrags(const float* w, int c0, int wave, in
 // ---------------------------------------------------------------------------------------------------------------------
 // kernel A: weight gradient + SE dot
 // ---------------------------------------------------------------------------------------------------------------------
-template <int CE, int CO, int CC>
+// SE: also the four per-sample dots the BatchNorm-1 backward sums are linear in (coldot_bn_se_kernel's definitions):
+//   A1 = sum u, A2 = sum u xhat (u = dc act'(y), rounded to fp32 once), B1 = sum act'(y), B2 = sum act'(y) xhat.
+// The fp32 tile then holds d itself and the lane re-evaluates BatchNorm + swish for the eight elements of its dc fragment: a
+// (the same expression as the element-wise phase: the same bits), act', xhat.  No relay, no barrier, no LDS beyond kernel A's;
+// the price is a second sigmoid per element.  Five fp32 sums per tile and column, then fp64, as the dot always was.
+template <int CE, int CO, int CC, bool SE = false>
 __global__ __launch_bounds__(NTH, 2) void pj_bwd_a_kernel(PjArgs a) {
     using CF = PjCfg<CE, CO, CC>;
+    static_assert(!SE || CC % 16 == 0, "SE: whole 16-channel blocks (the lane's coefficients are those of a real channel)");
+    constexpr int NS = SE ? 2 : 1;          // SE: a lane keeps the sum of plane g (its row group) and of plane 4
     extern __shared__ __attribute__((aligned(16))) char L[];
     char* cimg = L;
     char* abuf = L + 3 * CF::CP;
@@ -161,12 +191,13 @@ __global__ __launch_bounds__(NTH, 2) void pj_bwd_a_kernel(PjArgs a) {
     }
 
     f32x4 accw[CF::NBW][CF::NB2];
-    double dot[CF::NBW];          // (per tile: 8 products per lane in fp32, then fp64 — a sample of 128 x 128 pixels is 512 tiles)
+    double dot[CF::NBW][NS];          // (per tile: 8 products per lane in fp32, then fp64 — a sample of 128 x 128 pixels is 512 tiles)
 #pragma unroll
     for (int j = 0; j < CF::NBW; ++j) {
 #pragma unroll
         for (int m = 0; m < CF::NB2; ++m) accw[j][m] = f32x4{0.f, 0.f, 0.f, 0.f};
-        dot[j] = 0.0;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) dot[j][i] = 0.0;
     }
 
     const f32x4* d4 = reinterpret_cast<const f32x4*>(a.d) + chunk * CF::Q;
@@ -190,14 +221,26 @@ __global__ __launch_bounds__(NTH, 2) void pj_bwd_a_kernel(PjArgs a) {
         }
     };
     auto flush = [&](int n) {          // the dots of sample n (every lane of a column holds the same sum)
-        if (g == 0) {
+        if constexpr (SE) {          // row group g adds plane g, row group 0 also plane 4: at most two adds per lane and block
+            const long plane = a.M / a.HW * CE;
+#pragma unroll
+            for (int j = 0; j < CF::NBW; ++j) {
+                if (wave + 4 * j < CF::NBC) {
+                    double* o = a.dots + (long)n * CE + c0 + 16 * (wave + 4 * j) + u;
+                    atomic_add_f64(o + g * plane, dot[j][0]);
+                    if (g == 0) atomic_add_f64(o + 4 * plane, dot[j][1]);
+                }
+            }
+        } else if (g == 0) {
 #pragma unroll
             for (int j = 0; j < CF::NBW; ++j)
                 if (wave + 4 * j < CF::NBC && 16 * (wave + 4 * j) + u < CC)
-                    atomic_add_f64(a.dgate + (long)n * CE + c0 + 16 * (wave + 4 * j) + u, dot[j]);
+                    atomic_add_f64(a.dgate + (long)n * CE + c0 + 16 * (wave + 4 * j) + u, dot[j][0]);
         }
 #pragma unroll
-        for (int j = 0; j < CF::NBW; ++j) dot[j] = 0.0;
+        for (int j = 0; j < CF::NBW; ++j)
+#pragma unroll
+            for (int i = 0; i < NS; ++i) dot[j][i] = 0.0;
     };
 
     prefetch(t0);          // the first tile's loads, then everything else the prologue needs: one memory latency for all of it
@@ -208,6 +251,14 @@ __global__ __launch_bounds__(NTH, 2) void pj_bwd_a_kernel(PjArgs a) {
     const f32x4* c4 = reinterpret_cast<const f32x4*>(coef);
     const f32x4* g4 = reinterpret_cast<const f32x4*>(gate);
     __syncthreads();
+    float lmu[CF::NBW], lis[CF::NBW], lga[CF::NBW], lbe[CF::NBW];          // SE: the coefficients of the lane's column per block
+    if constexpr (SE) {
+#pragma unroll
+        for (int j = 0; j < CF::NBW; ++j) {
+            const int c = 16 * min(wave + 4 * j, CF::NBC - 1) + u;
+            lmu[j] = coef[c]; lis[j] = coef[CC + c]; lga[j] = coef[2 * CC + c]; lbe[j] = coef[3 * CC + c];
+        }
+    }
     for (long tile = t0; tile < t1; ++tile) {
         const int n = (int)(tile * R / a.HW);
         if (n != cur_n) {          // (uniform) the gate of the new sample; the finished sample's dots go out
@@ -230,7 +281,7 @@ __global__ __launch_bounds__(NTH, 2) void pj_bwd_a_kernel(PjArgs a) {
                     av[k] = act_sel(z, swish);
                     cv[k] = av[k] * gt[k];
                 }
-                *reinterpret_cast<f32x4*>(abuf + row * CF::AS + q * 16) = av;
+                *reinterpret_cast<f32x4*>(abuf + row * CF::AS + q * 16) = SE ? rd[it] : av;
                 store_split4(cimg + row * CF::CS + q * 8, CF::CP, cv);
             }
 #pragma unroll
@@ -263,15 +314,42 @@ __global__ __launch_bounds__(NTH, 2) void pj_bwd_a_kernel(PjArgs a) {
                     dc0 = mma6(a0[ks], b, dc0);
                     dc1 = mma6(a1[ks], b, dc1);
                 }
-                float t = 0.f;
+                float t = 0.f, ta1 = 0.f, ta2 = 0.f, tb1 = 0.f, tb2 = 0.f;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    t += dc0[r] * ab[r * (CF::AS / 4) + 16 * nb];
-                    t += dc1[r] * ab[(16 + r) * (CF::AS / 4) + 16 * nb];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const float dcv = h ? dc1[r] : dc0[r];
+                        const float tv = ab[(16 * h + r) * (CF::AS / 4) + 16 * nb];          // a; SE: d
+                        if constexpr (SE) {
+                            const float xh = (tv - lmu[j]) * lis[j];
+                            const float z = lga[j] * xh + lbe[j];
+                            const float ap = act_grad_sel(z, swish);
+                            const float uu = mul_rn(dcv, ap);
+                            t += mul_rn(dcv, act_sel(z, swish));          // (the plain kernel's product, rounded on its own)
+                            ta1 += uu;
+                            ta2 += uu * xh;
+                            tb1 += ap;
+                            tb2 += ap * xh;
+                        } else {
+                            t += mul_rn(dcv, tv);          // (what the build always made of it: v_pk_mul_f32, then the add)
+                        }
+                    }
                 }
-                t += __shfl_xor(t, 16, 64);
-                t += __shfl_xor(t, 32, 64);
-                dot[j] += (double)t;
+                if constexpr (SE) {          // every lane of a column gets all five sums of the tile; it keeps two of them
+                    t += __shfl_xor(t, 16, 64);     t += __shfl_xor(t, 32, 64);
+                    ta1 += __shfl_xor(ta1, 16, 64); ta1 += __shfl_xor(ta1, 32, 64);
+                    ta2 += __shfl_xor(ta2, 16, 64); ta2 += __shfl_xor(ta2, 32, 64);
+                    tb1 += __shfl_xor(tb1, 16, 64); tb1 += __shfl_xor(tb1, 32, 64);
+                    tb2 += __shfl_xor(tb2, 16, 64); tb2 += __shfl_xor(tb2, 32, 64);
+                    const float lo = (g & 1) ? ta1 : t, hi = (g & 1) ? tb1 : ta2;
+                    dot[j][0] += (double)((g & 2) ? hi : lo);
+                    dot[j][1] += (double)tb2;
+                } else {
+                    t += __shfl_xor(t, 16, 64);
+                    t += __shfl_xor(t, 32, 64);
+                    dot[j][0] += (double)t;
+                }
             }
         }
         // ---- weight gradient: dWp[co block][channel block] += dp^T c, k = the tile's rows (transposed reads of both images)
@@ -335,6 +413,37 @@ __global__ __launch_bounds__(256) void pj_fold_kernel(const float* __restrict__ 
 #pragma unroll
         for (int j = 1; j < 16; ++j) t += red[j][el];
         dw[i] = t;
+    }
+}
+
+// The dc tile of the dp image at `dimg` -> the fp32 tile `dcbuf` (from the MFMA layout: lane = column 16 nb + u, rows 16 mb + 4 g + r):
+// the relay of kernels B and C to the row-major quads of d
+template <typename CF>
+__device__ __forceinline__ void dc_tile_to_lds(const lds_char* dimg, char* dcbuf, const u32x4 (&wf)[CF::NBW][CF::KS2][3], int wave,
+                                               int u, int g) {
+    const lds_char* drow = dimg + u * CF::DS + g * 16;
+    Frag3 a0[CF::KS2], a1[CF::KS2];
+#pragma unroll
+    for (int ks = 0; ks < CF::KS2; ++ks) {
+        a0[ks] = read_rows(drow + ks * 64, CF::DPL);
+        a1[ks] = read_rows(drow + 16 * CF::DS + ks * 64, CF::DPL);
+    }
+    float* ob = reinterpret_cast<float*>(dcbuf) + (4 * g) * (CF::AS / 4) + u;
+#pragma unroll
+    for (int j = 0; j < CF::NBW; ++j) {
+        const int nb = min(wave + 4 * j, CF::NBC - 1);          // (a wave's block past the last one rewrites the last block's values)
+        f32x4 dc0 = {0.f, 0.f, 0.f, 0.f}, dc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < CF::KS2; ++ks) {
+            const Frag3 b = frag_of(wf[j][ks]);
+            dc0 = mma6(a0[ks], b, dc0);
+            dc1 = mma6(a1[ks], b, dc1);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            ob[r * (CF::AS / 4) + 16 * nb] = dc0[r];
+            ob[(16 + r) * (CF::AS / 4) + 16 * nb] = dc1[r];
+        }
     }
 }
 
@@ -426,33 +535,7 @@ __global__ __launch_bounds__(NTH, 2) void pj_bwd_b_kernel(PjArgs a) {
         for (int it = 0; it < CF::NIT; ++it) dq[it] = rd[it];
         __syncthreads();
         prefetch(tile + 1);
-        // ---- dc tile -> fp32 tile in LDS (from the MFMA layout: lane = column 16 nb + u, rows 16 mb + 4 g + r)
-        {
-            const lds_char* drow = Lp + CF::AP + u * CF::DS + g * 16;
-            Frag3 a0[CF::KS2], a1[CF::KS2];
-#pragma unroll
-            for (int ks = 0; ks < CF::KS2; ++ks) {
-                a0[ks] = read_rows(drow + ks * 64, CF::DPL);
-                a1[ks] = read_rows(drow + 16 * CF::DS + ks * 64, CF::DPL);
-            }
-            float* ob = reinterpret_cast<float*>(dcbuf) + (4 * g) * (CF::AS / 4) + u;
-#pragma unroll
-            for (int j = 0; j < CF::NBW; ++j) {
-                const int nb = min(wave + 4 * j, CF::NBC - 1);          // (a wave's block past the last one rewrites the last block's values)
-                f32x4 dc0 = {0.f, 0.f, 0.f, 0.f}, dc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int ks = 0; ks < CF::KS2; ++ks) {
-                    const Frag3 b = frag_of(wf[j][ks]);
-                    dc0 = mma6(a0[ks], b, dc0);
-                    dc1 = mma6(a1[ks], b, dc1);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    ob[r * (CF::AS / 4) + 16 * nb] = dc0[r];
-                    ob[(16 + r) * (CF::AS / 4) + 16 * nb] = dc1[r];
-                }
-            }
-        }
+        dc_tile_to_lds<CF>(Lp + CF::AP, dcbuf, wf, wave, u, g);
         __syncthreads();
         // ---- element-wise over the row-major quads
         {
@@ -498,6 +581,176 @@ __global__ __launch_bounds__(NTH, 2) void pj_bwd_b_kernel(PjArgs a) {
     for (int c = tid; c < CC; c += NTH) {
         atomic_add_f64(a.s1 + c0 + c, lacc[c]);
         atomic_add_f64(a.s2 + c0 + c, lacc[CC + c]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// kernel C: kernel B's loop whose element-wise phase is the BatchNorm-1 backward apply itself.  The sums s1 / s2 are there
+// before the pass (ud_se_bwd_b_bn folded them from kernel A's per-sample dots), so dz stays in registers and
+//     dd = gamma invstd (dz - s1 / count - xhat s2 / count)
+// leaves in its place, in normbwd_apply_kernel's rounding; dgamma / dbeta are copied from this rank's sums.  dz is never written.
+// MIX (the SF blocks): a third stream, diff = freq - spat; sum dd diff into the 64 slots of the gate's accumulator and, where asked
+// for, the per-channel energy of dd, rounded up (fp32 partials over at most 64 tiles x 1.0001, then fp64) — as normbwd_apply_kernel<MIX>.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int CE, int CO, int CC, bool MIX>
+__global__ __launch_bounds__(NTH, 2) void pj_bwd_c_kernel(PjArgs a) {
+    using CF = PjCfg<CE, CO, CC>;
+    extern __shared__ __attribute__((aligned(16))) char L[];
+    char* dcbuf = L;
+    char* dimg = L + CF::AP;
+    float* coef = reinterpret_cast<float*>(dimg + 3 * CF::DPL);
+    float* gate = coef + 4 * CC;
+    float* dpl = gate + CC;
+    float* tt = dpl + CC;                                            // [2][CC]: s1 / count, s2 / count
+    double* eacc = reinterpret_cast<double*>(tt + 2 * CC);          // [CC]
+    double* wsum = eacc + CC;                                        // [4]
+    const lds_char* Lp = (const lds_char*)L;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int u = lane & 15, g = lane >> 4;
+    const bool swish = a.act == 1;
+    const int chunk = blockIdx.x / a.gc, bb = blockIdx.x - chunk * a.gc;          // (uniform)
+    const int c0 = chunk * CC;
+
+    if constexpr (CF::COP != CO) {
+        for (int i = tid; i < 3 * CF::DPL / 16; i += NTH) reinterpret_cast<u32x4*>(dimg)[i] = u32x4{0u, 0u, 0u, 0u};
+    }
+    for (int c = tid; c < CC; c += NTH) {
+        tt[c] = (float)a.bs1[c0 + c] * (float)a.inv_count;          // (normbwd_apply_kernel's rounding)
+        tt[CC + c] = (float)a.bs2[c0 + c] * (float)a.inv_count;
+        if constexpr (MIX) eacc[c] = 0.0;
+    }
+
+    const f32x4* d4 = reinterpret_cast<const f32x4*>(a.d) + chunk * CF::Q;
+    const f32x4* f4 = MIX ? reinterpret_cast<const f32x4*>(a.diff) + chunk * CF::Q : nullptr;
+    const f32x4* dp4 = reinterpret_cast<const f32x4*>(a.dp);
+    f32x4* dd4 = reinterpret_cast<f32x4*>(a.dd) + chunk * CF::Q;
+    const long t0 = (long)bb * a.tiles / a.gc, t1 = (long)(bb + 1) * a.tiles / a.gc;
+    f32x4 rd[CF::NIT], rp[CF::NITP], rf[MIX ? CF::NIT : 1];
+    auto prefetch = [&](long tile_) {
+        const long tile = min(tile_, a.tiles - 1);          // (uniform: a scalar base + the thread's fixed offsets; M % 32 == 0: no row tail)
+        const f32x4* db = d4 + tile * (R * CF::QT);
+        const f32x4* fb = MIX ? f4 + tile * (R * CF::QT) : nullptr;
+#pragma unroll
+        for (int it = 0; it < CF::NIT; ++it) {
+            const int idx = tid + it * NTH;
+            const int row = idx / CF::Q, q = idx - row * CF::Q;
+            const int o = ((it + 1) * NTH <= R * CF::Q || idx < R * CF::Q) ? row * CF::QT + q : 0;
+            rd[it] = db[o];
+            if constexpr (MIX) rf[it] = fb[o];
+        }
+        const f32x4* pb = dp4 + tile * (R * CF::DQ);
+#pragma unroll
+        for (int it = 0; it < CF::NITP; ++it) {
+            const int idx = tid + it * NTH;
+            rp[it] = pb[((it + 1) * NTH <= R * CF::DQ || idx < R * CF::DQ) ? idx : 0];
+        }
+    };
+
+    prefetch(t0);
+    load_coef(a, coef, c0, CC, tid);
+    u32x4 wf[CF::NBW][CF::KS2][3];
+    load_wfrags<CE, CO, CF::NBC, CF::NBW, CF::KS2>(a.w, c0, wave, u, g, wf);
+    double acc = 0.0;                     // MIX: sum dd diff over this thread's elements
+    float en[MIX ? CF::NIT : 1][4];       // MIX: sum dd^2 per channel over at most 64 tiles
+#pragma unroll
+    for (int it = 0; it < (MIX ? CF::NIT : 1); ++it)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) en[it][k] = 0.f;
+    auto en_flush = [&]() {
+#pragma unroll
+        for (int it = 0; it < (MIX ? CF::NIT : 1); ++it) {
+            const int idx = tid + it * NTH;
+            if (idx < R * CF::Q) {
+                const int q = idx % CF::Q;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) atomicAdd(&eacc[4 * q + k], (double)en[it][k] * 1.0001);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) en[it][k] = 0.f;
+        }
+    };
+    int cur_n = -1;
+    const f32x4* c4 = reinterpret_cast<const f32x4*>(coef);
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(gate);
+    const f32x4* p4 = reinterpret_cast<const f32x4*>(dpl);
+    const f32x4* t4 = reinterpret_cast<const f32x4*>(tt);
+    __syncthreads();
+    for (long tile = t0; tile < t1; ++tile) {
+        const int n = (int)(tile * R / a.HW);
+        if (n != cur_n) {          // (uniform) the previous tile's element-wise phase still reads gate / dpl: wait for it
+            __syncthreads();
+            for (int c = tid; c < CC; c += NTH) {
+                gate[c] = ud_sigmoid_fast(a.s[(long)n * CE + c0 + c]);
+                dpl[c] = a.dpool[(long)n * CE + c0 + c] * a.inv_hw;
+            }
+            cur_n = n;
+        }
+#pragma unroll
+        for (int it = 0; it < CF::NITP; ++it) {
+            const int idx = tid + it * NTH;
+            const int row = idx / CF::DQ, q = idx - row * CF::DQ;
+            store_split4(dimg + row * CF::DS + q * 8, CF::DPL, rp[it]);
+        }
+        // this tile's quads move out of the ring before the next tile's loads are issued into it
+        f32x4 dq[CF::NIT], fq[MIX ? CF::NIT : 1];
+#pragma unroll
+        for (int it = 0; it < CF::NIT; ++it) {
+            dq[it] = rd[it];
+            if constexpr (MIX) fq[it] = rf[it];
+        }
+        __syncthreads();
+        prefetch(tile + 1);
+        dc_tile_to_lds<CF>(Lp + CF::AP, dcbuf, wf, wave, u, g);
+        __syncthreads();
+        // ---- element-wise over the row-major quads
+        {
+            f32x4* ob4 = dd4 + tile * (R * CF::QT);
+#pragma unroll
+            for (int it = 0; it < CF::NIT; ++it) {
+                const int idx = tid + it * NTH;
+                const int row = idx / CF::Q, q = idx - row * CF::Q;
+                const bool ok = (it + 1) * NTH <= R * CF::Q || idx < R * CF::Q;          // (compile-time true but for a last partial item)
+                const f32x4 mu = c4[q], is = c4[CF::Q + q], ga = c4[2 * CF::Q + q], be = c4[3 * CF::Q + q], gt = g4[q], pl = p4[q];
+                const f32x4 ta = t4[q], tb = t4[CF::Q + q];
+                const f32x4 dc = *reinterpret_cast<const f32x4*>(dcbuf + row * CF::AS + q * 16);
+                f32x4 o;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float xh = (dq[it][k] - mu[k]) * is[k];
+                    const float dz = mul_rn(dc[k] * gt[k] + pl[k], act_grad_sel(ga[k] * xh + be[k], swish));
+                    const float ov = mul_rn(ga[k], is[k]) * __builtin_fmaf(-xh, tb[k], dz - ta[k]);          // (the rounding stated)
+                    o[k] = ok ? ov : 0.f;
+                    if constexpr (MIX) {
+                        acc += (double)o[k] * (double)fq[it][k];
+                        en[it][k] += o[k] * o[k];
+                    }
+                }
+                if (ok) ob4[row * CF::QT + q] = o;
+            }
+        }
+        if constexpr (MIX) {
+            if (a.energy && ((tile - t0) & 63) == 63) en_flush();          // (uniform)
+        }
+        // (the next tile's dp image store and dc tile stores come after its own barriers, as in kernel B)
+    }
+    if (bb == 0) {          // one workgroup per chunk: dbeta = sum dz, dgamma = sum dz xhat of this rank
+        for (int c = tid; c < CC; c += NTH) {
+            if (a.dbeta) a.dbeta[c0 + c] = (float)a.bs1l[c0 + c];
+            if (a.dgamma) a.dgamma[c0 + c] = (float)a.bs2l[c0 + c];
+        }
+    }
+    if constexpr (MIX) {
+        if (a.energy) {          // (uniform)
+            en_flush();
+            __syncthreads();
+            for (int c = tid; c < CC; c += NTH) atomic_add_f64(a.energy + c0 + c, eacc[c]);
+        }
+        acc = ud_wave_sum_d(acc);
+        if (lane == 0) wsum[wave] = acc;
+        __syncthreads();
+        // 64 slots, as normbwd_apply_kernel: a few workgroups per address
+        if (tid == 0) atomic_add_f64(a.dalpha + (blockIdx.x & 63), (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
     }
 }
 
@@ -648,18 +901,18 @@ int launch_f(const PjFwdArgs& a, int grid, hipStream_t s) {
     return 0;
 }
 
-template <int CE, int CO, int CC>
+template <int CE, int CO, int CC, bool SE = false>
 int launch_a(const PjArgs& a, int grid, hipStream_t s) {
     using CF = PjCfg<CE, CO, CC>;
     static_assert(CF::LDS_A <= 80 * 1024, "two workgroups per CU");
     static bool attr_set = false;          // (> 64 KiB of dynamic LDS; set on the first launch, which is never inside a capture: eager warm-up)
     if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pj_bwd_a_kernel<CE, CO, CC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pj_bwd_a_kernel<CE, CO, CC, SE>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 CF::LDS_A) != hipSuccess)
             return UD_EINVAL;
         attr_set = true;
     }
-    hipLaunchKernelGGL((pj_bwd_a_kernel<CE, CO, CC>), dim3((unsigned)grid), dim3(NTH), CF::LDS_A, s, a);
+    hipLaunchKernelGGL((pj_bwd_a_kernel<CE, CO, CC, SE>), dim3((unsigned)grid), dim3(NTH), CF::LDS_A, s, a);
     return 0;
 }
 template <int CE, int CO, int CC>
@@ -668,6 +921,18 @@ int launch_b(const PjArgs& a, int grid, hipStream_t s) {
     static_assert(CF::LDS_B <= 64 * 1024, "dynamic LDS within the default limit");
     hipLaunchKernelGGL((pj_bwd_b_kernel<CE, CO, CC>), dim3((unsigned)grid), dim3(NTH), CF::LDS_B, s, a);
     return 0;
+}
+template <int CE, int CO, int CC, bool MIX>
+int launch_c(const PjArgs& a, int grid, hipStream_t s) {
+    using CF = PjCfg<CE, CO, CC>;
+    static_assert(CF::LDS_C <= 64 * 1024, "dynamic LDS within the default limit");
+    hipLaunchKernelGGL((pj_bwd_c_kernel<CE, CO, CC, MIX>), dim3((unsigned)grid), dim3(NTH), CF::LDS_C, s, a);
+    return 0;
+}
+template <bool MIX>
+int launch_c_of(const PjArgs& a, int CE, int CO, int grid, hipStream_t st) {
+    return CO == 32 ? (CE == 144 ? launch_c<144, 32, 144, MIX>(a, grid, st) : launch_c<192, 32, 192, MIX>(a, grid, st))
+                    : (CE == 336 ? launch_c<336, 56, 112, MIX>(a, grid, st) : launch_c<192, 56, 96, MIX>(a, grid, st));
 }
 
 // the (CE, CO) pairs built, and the chunk width each is walked in
@@ -690,6 +955,21 @@ void fill(PjArgs& a, const float* d, const float* dp, const ud_bn_ref* bn, const
     a.M = (long)N * HW; a.tiles = a.M / R;
     a.gc = (int)(ud_pj_bwd_fused_grid(N, HW, CE, CO) / (CE / chunk_of(CE, CO)));
     a.dpool = nullptr; a.dz = nullptr; a.part = nullptr; a.dgate = nullptr; a.s1 = a.s2 = nullptr; a.inv_hw = 0.f;
+    a.dots = nullptr; a.bs1 = a.bs2 = a.bs1l = a.bs2l = nullptr; a.diff = nullptr; a.dd = nullptr; a.dgamma = a.dbeta = nullptr;
+    a.dalpha = a.energy = nullptr;
+}
+
+// kernel C's operands (ud_normbwd_apply_se's rules: the outputs dgamma / dbeta need this rank's sums)
+bool c_args_ok(const void* d, const void* dp, const ud_bn_ref* bn, const void* s, const void* dpool, const void* w, const double* s1,
+               const double* s2, const double* s1_local, const double* s2_local, int N, int HW, int CE, int CO, const void* dd,
+               const float* dgamma, const float* dbeta) {
+    return args_ok(d, dp, bn, s, w, N, HW, CE, CO) && ud_pj_bwd_fused_se_ok(CE, CO, HW) && dpool && s1 && s2 && dd &&
+           !((dgamma || dbeta) && (!s1_local || !s2_local));
+}
+void fill_c(PjArgs& a, const float* dpool, float inv_hw, const double* s1, const double* s2, const double* s1_local,
+            const double* s2_local, float* dd, float* dgamma, float* dbeta) {
+    a.dpool = dpool; a.inv_hw = inv_hw; a.bs1 = s1; a.bs2 = s2; a.bs1l = s1_local; a.bs2l = s2_local; a.dd = dd; a.dgamma = dgamma;
+    a.dbeta = dbeta;
 }
 
 }  // namespace
@@ -698,6 +978,9 @@ extern "C" {
 
 int ud_pj_bwd_fused_ok(int CE, int CO, int HW) { return (chunk_of(CE, CO) && HW >= R && HW % R == 0) ? 1 : 0; }
 int ud_pj_fwd_fused_ok(int CE, int CO, int HW) { return (CO <= 32 && chunk_of(CE, CO) == CE && HW >= R && HW % R == 0) ? 1 : 0; }
+
+// the pairs whose BatchNorm-1 backward folds into the passes (kernel A with the five dots, kernel C): not the narrow (24-column) ones
+int ud_pj_bwd_fused_se_ok(int CE, int CO, int HW) { return (ud_pj_bwd_fused_ok(CE, CO, HW) && CO != 24) ? 1 : 0; }
 
 long ud_pj_bwd_fused_grid(int N, int HW, int CE, int CO) {
     const int cc = chunk_of(CE, CO);
@@ -753,6 +1036,52 @@ int ud_pj_bwd_fused_b(const float* d, const float* dp, const ud_bn_ref* bn, cons
     const int rc = CO == 32 ? (CE == 144 ? launch_b<144, 32, 144>(a, grid, st) : launch_b<192, 32, 192>(a, grid, st))
                  : CO == 24 ? (CE == 48 ? launch_b<48, 24, 48>(a, grid, st) : launch_b<24, 24, 24>(a, grid, st))
                             : (CE == 336 ? launch_b<336, 56, 112>(a, grid, st) : launch_b<192, 56, 96>(a, grid, st));
+    if (rc) return rc;
+    UD_LAUNCH_CHECK();
+    return 0;
+}
+
+int ud_pj_bwd_fused_a_se(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* w, int N, int HW, int CE,
+                         int CO, float* dw, double* dots, float* part, ud_stream_t stream) {
+    if (!args_ok(d, dp, bn, s, w, N, HW, CE, CO) || !ud_pj_bwd_fused_se_ok(CE, CO, HW) || !dw || !dots || !part) return UD_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    PjArgs a;
+    fill(a, d, dp, bn, s, w, N, HW, CE, CO);
+    a.part = part; a.dots = dots;
+    const int grid = (int)ud_pj_bwd_fused_grid(N, HW, CE, CO);
+    const int rc = CO == 32 ? (CE == 144 ? launch_a<144, 32, 144, true>(a, grid, st) : launch_a<192, 32, 192, true>(a, grid, st))
+                            : (CE == 336 ? launch_a<336, 56, 112, true>(a, grid, st) : launch_a<192, 56, 96, true>(a, grid, st));
+    if (rc) return rc;
+    UD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pj_fold_kernel, dim3((unsigned)ud_cdiv((long)CO * CE, 16)), dim3(256), 0, st, part, a.gc, CO, CE, chunk_of(CE, CO), dw);
+    UD_LAUNCH_CHECK();
+    return 0;
+}
+
+int ud_pj_bwd_fused_c(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,
+                      const float* w, const double* s1, const double* s2, const double* s1_local, const double* s2_local, int N,
+                      int HW, int CE, int CO, float* dd, float* dgamma, float* dbeta, ud_stream_t stream) {
+    if (!c_args_ok(d, dp, bn, s, dpool, w, s1, s2, s1_local, s2_local, N, HW, CE, CO, dd, dgamma, dbeta)) return UD_EINVAL;
+    PjArgs a;
+    fill(a, d, dp, bn, s, w, N, HW, CE, CO);
+    fill_c(a, dpool, inv_hw, s1, s2, s1_local, s2_local, dd, dgamma, dbeta);
+    const int rc = launch_c_of<false>(a, CE, CO, (int)ud_pj_bwd_fused_grid(N, HW, CE, CO), (hipStream_t)stream);
+    if (rc) return rc;
+    UD_LAUNCH_CHECK();
+    return 0;
+}
+
+int ud_pj_bwd_fused_c_mix(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,
+                          const float* w, const double* s1, const double* s2, const double* s1_local, const double* s2_local,
+                          const float* diff, int N, int HW, int CE, int CO, float* dd, double* dalpha_acc, float* dgamma,
+                          float* dbeta, double* energy, ud_stream_t stream) {
+    if (!c_args_ok(d, dp, bn, s, dpool, w, s1, s2, s1_local, s2_local, N, HW, CE, CO, dd, dgamma, dbeta) || !diff || !dalpha_acc)
+        return UD_EINVAL;
+    PjArgs a;
+    fill(a, d, dp, bn, s, w, N, HW, CE, CO);
+    fill_c(a, dpool, inv_hw, s1, s2, s1_local, s2_local, dd, dgamma, dbeta);
+    a.diff = diff; a.dalpha = dalpha_acc; a.energy = energy;
+    const int rc = launch_c_of<true>(a, CE, CO, (int)ud_pj_bwd_fused_grid(N, HW, CE, CO), (hipStream_t)stream);
     if (rc) return rc;
     UD_LAUNCH_CHECK();
     return 0;

@@ -3540,6 +3540,56 @@ def project_bwd_fused_b(d, bn, s, dpool, inv_hw, dp2, w2, N, HW, sacc):
     return dz
 
 
+def project_bwd_fold_ok(w2, HW):
+    """do ud_pj_bwd_fused_a_se / _c take this pair too (the BatchNorm-1 backward folded into the two passes: DESIGN 3z)?"""
+    return _lib.call("ud_pj_bwd_fused_se_ok", int(w2.shape[1]), int(w2.shape[0]), int(HW)) == 1
+
+
+def project_bwd_fused_a_se(d, bn, s, dp2, w2, N, HW, dots):
+    """project_bwd_fused_a that also sums the four per-sample dots of coldot_bn_se: dots fp64 [5 N Ce], zeroed by the caller, receives
+    (dgate, A1, A2, B1, B2) — se_bwd(fold=...) turns them into the BatchNorm-1 backward sums.  Returns dw."""
+    _chk(d, dp2, w2, s)
+    Co, Ce = w2.shape
+    assert d.numel() == N * HW * Ce and dp2.numel() == N * HW * Co and s.numel() == N * Ce and dp2.is_contiguous()
+    assert dots.numel() >= 5 * N * Ce
+    dw = empty((Co, Ce), d)
+    grid = _lib.call("ud_pj_bwd_fused_grid", N, HW, Ce, Co)
+    part = empty((grid, Co * Ce), d)          # (an upper bound, as in project_bwd_fused_a)
+    _call("ud_pj_bwd_fused_a_se", _p(d), _p(dp2), C.byref(bn.ref()), _p(s), _p(w2), N, HW, Ce, Co, _p(dw), _pd(dots), _p(part),
+          _stream())
+    return dw
+
+
+def project_bwd_fused_c(d, bn, s, dpool, inv_hw, dp2, w2, N, HW, sacc, sacc_local=None):
+    """project_bwd_fused_b and normbwd_apply in one pass over d: dz = ((dp w) sigmoid(s) + dpool inv_hw) act'(bn(d)) stays in
+    registers, dd = the BatchNorm backward of it leaves; sacc from se_bwd(fold=...).  Returns (dd, dgamma, dbeta)."""
+    _chk(d, dp2, w2, s, dpool)
+    Co, Ce = w2.shape
+    loc = sacc if sacc_local is None else sacc_local
+    dd = torch.empty_like(d)
+    dg = empty((Ce,), d)
+    db = empty((Ce,), d)
+    _call("ud_pj_bwd_fused_c", _p(d), _p(dp2), C.byref(bn.ref()), _p(s), _p(dpool), float(inv_hw), _p(w2), _pd(sacc), _pd(sacc, Ce),
+          _pd(loc), _pd(loc, Ce), N, HW, Ce, Co, _p(dd), _p(dg), _p(db), _stream())
+    dd._ud_absmax = None
+    return dd, dg, db
+
+
+def project_bwd_fused_c_mix(d, bn, s, dpool, inv_hw, dp2, w2, N, HW, sacc, diff, dalpha_acc, sacc_local=None, energy=None):
+    """project_bwd_fused_c for the SF mix: diff, dalpha_acc and energy as normbwd_apply_mix.  Returns (dd, dgamma, dbeta)."""
+    _chk(d, dp2, w2, s, dpool, diff)
+    assert diff.dtype == torch.float32 and diff.numel() == d.numel()
+    Co, Ce = w2.shape
+    loc = sacc if sacc_local is None else sacc_local
+    dd = torch.empty_like(d)
+    dg = empty((Ce,), d)
+    db = empty((Ce,), d)
+    _call("ud_pj_bwd_fused_c_mix", _p(d), _p(dp2), C.byref(bn.ref()), _p(s), _p(dpool), float(inv_hw), _p(w2), _pd(sacc),
+          _pd(sacc, Ce), _pd(loc), _pd(loc, Ce), _p(diff), N, HW, Ce, Co, _p(dd), _pd(dalpha_acc), _p(dg), _p(db),
+          _pd(energy) if energy is not None else None, _stream())
+    return dd, dg, db
+
+
 def normbwd_apply_mix(x, dz, bn, G, R, sacc, diff, dalpha_acc, sacc_local=None, energy=None):
     """diff = freq - spat (irfft2_mix).  energy: C zeroed doubles that receive sum_rows dd^2 per channel (rfft2_ex_planes' bound)."""
     h = _act(x, dz, diff)

@@ -109,6 +109,28 @@ def _se_bn1_fold_policy(sf, stride, Ho, Ce, half):
     return True
 
 
+# The same fold on the blocks whose project conv is thin (pj_fused: no dc tensor): K.project_bwd_fused_a_se sums the dots
+# inside the weight-gradient pass, K.se_bwd(fold=...) folds them, and K.project_bwd_fused_c / _c_mix is project_bwd_fused_b and the
+# BN1 apply in one pass — dz1 stays in registers.
+_PJ_BN1_FOLD_OVERRIDE = {}
+# (sf, stride, Ho, Ce) -> routed?  One entry per block shape MEASURED; a shape that is not in the table keeps passes A and B.
+_PJ_BN1_FOLD_RULE = {(False, 2, 64, 144): True, (False, 1, 64, 192): True, (True, 2, 32, 192): True, (True, 1, 32, 336): True}
+
+
+def _pj_bn1_fold_policy(sf, stride, Ho, Ce):
+    """BatchNorm-1 backward folded into the thin-project passes (A with the five dots, C instead of B + the apply)?  For the blocks
+    on ud_pj_bwd_fused_a / _b (pj_fused: fp32 storage by construction) whose (Ce, Co) pair K.project_bwd_fold_ok takes.  Measured per
+    block shape, old chain against new (tools/bench_se_bn1_fold.py on an MI355X, profiles/r28/pj_bn1_fold.txt; us, bs 32): plain
+    stride 2 64^2 x 144 129 -> 103, plain 64^2 x 192 155 -> 114, SF stride 2 32^2 x 192 79 -> 63, SF 32^2 x 336 120 -> 98 (pass A
+    costs 7-15 us more for its second BatchNorm + swish evaluation; pass C is FASTER than pass B, and the apply launch is gone):
+    every shape of the UDEB4 step at 256 x 256 wins and is on.  Shapes nobody measured stay off; the override reaches any shape."""
+    key = (bool(sf), stride, Ho, Ce)
+    ov = _PJ_BN1_FOLD_OVERRIDE.get(key)
+    if ov is not None:
+        return ov
+    return _PJ_BN1_FOLD_RULE.get(key, False)
+
+
 # ONE geometry per (block, input shape), read by all five nodes.
 # sizes: x [N,H,W,Cin] (M pixels) -> expanded [N,H,W,Ce] -> depthwise [N,Ho,Wo,Ce] (HWo per sample, Mo pixels) -> [N,Ho,Wo,Co];
 # pt / pl: the depthwise conv's top / left zero pad.  2-D weight views: We expand [Ce,Cin] (None: no expand conv), Wsr / Wse the
@@ -444,8 +466,13 @@ def _bwd_project(b, tape, gr):
     gr.se_dots = None
     if gr.pj_fused:
         gr.dc = None
-        gr.dgate = K.zeros64(g.N * g.Ce, x)
-        dWp = K.project_bwd_fused_a(b.d, b.bn1, b.s2, gr.dp2, g.Wp, g.N, g.HWo, gr.dgate)
+        if K.project_bwd_fold_ok(g.Wp, g.HWo) and _pj_bn1_fold_policy(g.sf, g.stride, g.Ho, g.Ce):
+            gr.se_dots = K.zeros64(5 * g.N * g.Ce, x)
+            gr.dgate = gr.se_dots[:g.N * g.Ce]
+            dWp = K.project_bwd_fused_a_se(b.d, b.bn1, b.s2, gr.dp2, g.Wp, g.N, g.HWo, gr.se_dots)
+        else:
+            gr.dgate = K.zeros64(g.N * g.Ce, x)
+            dWp = K.project_bwd_fused_a(b.d, b.bn1, b.s2, gr.dp2, g.Wp, g.N, g.HWo, gr.dgate)
     else:
         dc, dWp = K.spectral_bwd(b.pctx, gr.dp2, dy_absmax=dp_amax)          # (one launch for both where that fills the chip better)
         gr.dc = dc.view(g.N, g.Ho, g.Wo, g.Ce)
@@ -481,8 +508,11 @@ def _bwd_se(b, tape, gr):
 
 
 def _bn1_apply(b, gr):
-    """the BN1 backward apply from dz1 or, where dz1 was never written (gr.se_dots), from dc through the SE gate"""
+    """the BN1 backward apply from dz1 or, where dz1 was never written (gr.se_dots), from dc through the SE gate — a tensor, or
+    (pj_fused: gr.dc is None) re-made per tile from the thin dp2 inside the pass"""
     g = b.geo
+    if gr.dz1 is None and gr.dc is None:
+        return K.project_bwd_fused_c(b.d, b.bn1, b.s2, gr.dpool, 1.0 / g.HWo, gr.dp2, g.Wp, g.N, g.HWo, gr.sb1, gr.loc1)
     if gr.dz1 is None:
         return K.normbwd_apply_se(b.d, gr.dc, b.bn1, b.s2, gr.dpool, 1.0 / g.HWo, g.N, g.HWo, gr.sb1, gr.loc1)
     return K.normbwd_apply(b.d, gr.dz1, None, 1.0, b.bn1, True, g.N, g.HWo, gr.sb1, gr.loc1)
@@ -502,7 +532,10 @@ def _bwd_bn1(b, tape, gr):
             dacc = K.zeros64(64, x)
             dyf_pl = sctx.plans is not None and K.rfft2_planes_ok(d, None)
             en = K.zeros64(g.Ce, x) if dyf_pl else None
-            if gr.dz1 is None:
+            if gr.dz1 is None and gr.dc is None:
+                dd, dg1, db1 = K.project_bwd_fused_c_mix(d, b.bn1, b.s2, gr.dpool, 1.0 / g.HWo, gr.dp2, g.Wp, g.N, g.HWo, gr.sb1,
+                                                         b.fr, dacc, gr.loc1, energy=en)
+            elif gr.dz1 is None:
                 dd, dg1, db1 = K.normbwd_apply_mix_se(d, gr.dc, b.bn1, b.s2, gr.dpool, 1.0 / g.HWo, g.N, g.HWo, gr.sb1, b.fr, dacc,
                                                       gr.loc1, energy=en)
             else:
