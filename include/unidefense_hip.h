@@ -993,6 +993,60 @@ int ud_hsj_dist(const float* a, const float* b, const int* ist, int N, long per,
 int ud_hsj_estimate(float* v, const char* phi, const long long* ids, const int* ist, int N, long per, int B, int draw0, int norm,
                     float inv_b, long seed, ud_stream_t stream);
 
+/* ---- attribution: integrated gradients and the deletion / insertion score (csrc/attrib.hip; unidefense_amd/attrib.py) ---------
+ * x, b, xp, g, attr, xq contiguous fp32 [N][per], per = 3 S^2 (b: the baseline, one per sample: the host expands a shared one);
+ * acc float64 [N][per]; heat fp32 [N][S^2].  One iteration of the path integral is a static launch sequence inside a captured
+ * graph: point, (noise,) forward + d/dx, accumulate, control; k int32 [N] is the sample's iteration counter (row UD_ATTR_I_K of
+ * ist [1][N], which the caller zeroes to start a run) and `iters` the length of the run: iteration k takes node k % steps.
+ * The element-wise kernels give one thread a quad of four consecutive elements (finish, mask: pixels): a float4 per thread where
+ * the length is a multiple of 4 and every base is 16-byte aligned, scalar accesses otherwise, the same bits either way.  Every
+ * expression is rounded once per operation, in the order written, without contraction.  No floating-point atomics: a replay
+ * gives the same bits.
+ * ud_attr_point: a = alpha[k[n] % steps] (alpha: an fp32 table [steps]); xp = b + a (x - b): d = x - b, m = a d, xp = b + m, three
+ *   fp32 operations.  By rule, not arithmetic: a == 1 writes x bit for bit, a == 0 writes b.  A NaN in x shows at its own element
+ *   only (not at a == 0).  k[n] outside [0, iters) leaves xp[n] untouched.  xp is a buffer of its own.
+ * ud_attr_accumulate: acc[n][e] = acc[n][e] + (double)w[k[n] % steps] (double)g[n][e] (w: a float64 table [steps]): one double
+ *   product and one double add.  A NaN in g stays at its element.  k[n] outside [0, iters) leaves acc[n] untouched.
+ * ud_attr_control: one thread per sample.  With k = ist[K][n] in [0, iters): path[k][n] = f[n] (fp32 [iters][N]), ist[K][n] =
+ *   k + 1.  k outside [0, iters) writes nothing.  The deletion runner records its curve with it.
+ * ud_attr_finish: per element the double value v = ((double)x - (double)b) acc scale (UD_ATTR_IG: the difference, the product
+ *   with acc, the product with scale) or v = acc scale (UD_ATTR_GRAD; x and b do not enter); attr = (float)v;
+ *   heat[n][p] = (float)(t0 + t1 + t2), t_c = v (UD_ATTR_SUM) or |v| (UD_ATTR_ABS) at channel c of pixel p, added in double in the
+ *   order 0, 1, 2; total[n] (double) = the sum over all elements of v, before the fp32 rounding.  total: a thread adds the values
+ *   of its pixels (pixel by pixel, channels 0, 1, 2; its pixels in ascending order) from 0.0, a workgroup adds its threads in a
+ *   fixed tree (a butterfly in each wave, then the waves in order) into ws[n][part]; the number of workgroups per sample depends
+ *   on S alone; a second kernel (one thread per sample) folds the sample's partials in index order.  total[n] therefore does not
+ *   depend on arrival order, on N or on the sample's row.  ws: ud_attr_finish_ws_bytes(N, 3 S^2) bytes (per must be 3 S^2).
+ * ud_attr_rank_select: one workgroup per (sample n, j < K).  The key of pixel p is 64 bits: the high word is the order-preserving
+ *   uint32 image of heat[n][p] (u = the bit pattern; a NaN: 0, so it ranks last; -0 as +0; otherwise u < 2^31 ? u | 2^31 : ~u), the
+ *   low word is ~p: among equal heats the LOWER pixel index has the larger key, and all keys of a sample differ.  thr[j][n]
+ *   (uint64 [K][N]) = the kcount[j]-th largest key (kcount int32 [K] in device memory; a value above HW counts as HW), found by a
+ *   radix select of 8 passes of 8 bits on integer counts in LDS; 2^64 - 1 for kcount[j] <= 0.  Exactly kcount[j] pixels have
+ *   key >= thr[j][n].
+ * ud_attr_mask: j = ist[K][n]; top = key(p) >= thr[j][n].  UD_ATTR_DELETE: xq = top ? b : x at the three channels of pixel p;
+ *   UD_ATTR_INSERT: xq = top ? x : b.  Copies only.  j outside [0, K) leaves xq[n] untouched.  xq is a buffer of its own.
+ * UD_EINVAL before any HIP call: a NULL pointer, N < 1 or > 65535, per < 1, steps < 1, iters < 1, iters N > 2^31 - 1; S < 1 or
+ * > 32768, an unknown mode or reduce, a NaN scale, ws_bytes below ud_attr_finish_ws_bytes (itself UD_EINVAL for a per that is no
+ * multiple of 3 or a workspace beyond 2^31 - 1 bytes: 8 bytes per 1024 pixels, at most 8192 parts per sample); HW < 1 or > 2^30, K < 1, K N > 2^31 - 1. */
+#define UD_ATTR_I_K 0
+#define UD_ATTR_IG 0
+#define UD_ATTR_GRAD 1
+#define UD_ATTR_SUM 0
+#define UD_ATTR_ABS 1
+#define UD_ATTR_DELETE 0
+#define UD_ATTR_INSERT 1
+int ud_attr_point(const float* x, const float* b, float* xp, const int* k, const float* alpha, int steps, int iters, int N,
+                  long per, ud_stream_t stream);
+int ud_attr_accumulate(const float* g, double* acc, const int* k, const double* w, int steps, int iters, int N, long per,
+                       ud_stream_t stream);
+int ud_attr_control(const float* f, int* ist, float* path, int N, int iters, ud_stream_t stream);
+int ud_attr_finish_ws_bytes(int N, long per);
+int ud_attr_finish(const float* x, const float* b, const double* acc, float* attr, float* heat, double* total, double* ws,
+                   long ws_bytes, int mode, int reduce, double scale, int N, int S, ud_stream_t stream);
+int ud_attr_rank_select(const float* heat, const int* kcount, unsigned long long* thr, int N, long HW, int K, ud_stream_t stream);
+int ud_attr_mask(const float* x, const float* b, const float* heat, const unsigned long long* thr, const int* ist, float* xq,
+                 int mode, int N, int S, int K, ud_stream_t stream);
+
 /* ---- pass-2 input perturbations (model/unidefense.py:177-198), NCHW planes x[planes][H][W], no gradients --------
  * ud_gather2d      : out[p][y][x] = in[p][iy[y]][ix[x]] — downscale (model/modules.py:19-21): the two nearest
  *                    F.interpolate calls composed into one gather (index vectors from ATen's float32 rule)

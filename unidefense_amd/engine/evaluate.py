@@ -1,4 +1,4 @@
-"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal / test_flow / test_certified: one scoring
+"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal / test_flow / test_certified / test_attribution: one scoring
 forward, one batch source, one loop-and-gather, one metrics dictionary, and a table of test_robust's methods.  The Evaluator
 takes its model and iterator as arguments and imports nothing that loads the HIP library, so the stage rules run on the CPU
 against stubs (tests/test_evaluate_cpu.py, tests/test_universal_cpu.py).  What every stage keeps: its order inside a batch, who owns which generator, the sequence of
@@ -244,6 +244,60 @@ class Evaluator:
                 args["norm"], args["sigma"], ret["accuracy"], ret["abstained"], ret["median_radius"],
                 " ".join("%.3g:%.4f" % (e, a) for e, a in zip(grid.tolist(), ret["certified_accuracy"].tolist()))))
         return {"clean": clean, "certify": ret}
+
+    def test_attribution(self, batches, attribution, noise=None):
+        """noise: kernels.smooth_noise unless a caller (a CPU test) brings a host stand-in"""
+        attribution = dict(attribution) if attribution else {}
+        fractions = attribution.pop("fractions", None)
+        if not batches >= 1 or int(batches) != batches:
+            raise ValueError(f"batches must be an integer >= 1, got {batches!r}")
+        curve = {} if fractions is None else {"fractions": tuple(fractions)}
+        n = 2 * self.batch
+        try:                                             # ONE runner of each kind for every batch; every refusal before the first batch
+            runner = self.net.attribution_runner(n, self.size, **attribution)
+        except TypeError as e:                           # an unknown key is a bad dict, like a bad value
+            raise ValueError(f"attribution takes AttributionRunner's keyword arguments and 'fractions': {e}") from None
+        if runner.args["baseline"] == "given":
+            raise ValueError("the attribution stage has no baseline tensor to pass: baseline must be 'black' or 'grey'")
+        curves = {mode: self.net.deletion_runner(n, self.size, mode=mode, baseline=runner.args["baseline"],
+                                                 precision=self.precision, **curve) for mode in ("deletion", "insertion")}
+        if noise is None:
+            from ..kernels import smooth_noise as noise
+        args = dict(runner.args, fractions=curves["deletion"].args["fractions"])
+        dist = torch.distributed
+        rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
+        seen = 0
+
+        def body(x, y):                                  # clean, the map, its two curves, the random map's two curves
+            nonlocal seen
+            clean = self.score(x)
+            # a stream id per sample of the whole run: neither the tunnel's noise nor the random map depends on rank or batch
+            ids = torch.arange(x.shape[0], dtype=torch.int64, device=x.device) + (seen * world + rank) * x.shape[0]
+            seen += 1
+            runner(x, y, ids)
+            # the runners reuse their buffers: every column is cloned per batch
+            heat, gap, span = runner.heat.clone(), runner.gap.clone(), runner.f_x.double() - runner.f_b.double()
+            zeros = torch.zeros(x.shape[0], x.shape[-1] * x.shape[-1], dtype=torch.float32, device=x.device)
+            random = noise(zeros, torch.empty_like(zeros), ids, None, 0, "uniform", 1.0, args["seed"]).reshape(heat.shape)
+            cols = {}
+            for name, h in (("ig", heat), ("random", random)):
+                for mode in ("deletion", "insertion"):
+                    cols[(mode, name)] = curves[mode](x, y, h).clone()
+            return {**cols, "gap": gap, "span": span, "clean": clean}
+
+        cols = self.run(int(batches), body)
+        gap, span = cols["gap"][0].double().cpu(), cols["span"][0].double().cpu()
+        ret = {"clean": self.metrics(*cols["clean"], "Test"), "attribution": args,
+               "gap_rel": gap.abs() / span.abs().clamp_min(torch.finfo(torch.float64).tiny)}
+        for mode in ("deletion", "insertion"):
+            each = {name: cols[(mode, name)][0].double().cpu() for name in ("ig", "random")}
+            ret[mode + "_auc"] = {**{name: float(t.mean()) for name, t in each.items()}, "per_sample": each}
+        if self.local_rank == 0:
+            print("Test(attribution %s, %d steps) | deletion AUC ig %.4f random %.4f | insertion AUC ig %.4f random %.4f | "
+                  "median relative gap %.3g" % (args["method"], args["steps"], ret["deletion_auc"]["ig"], ret["deletion_auc"]["random"],
+                                                ret["insertion_auc"]["ig"], ret["insertion_auc"]["random"],
+                                                float(ret["gap_rel"].median())))
+        return ret
 
 
 # ---- test_robust's methods: ROBUST[method](ev, attack) refuses and resolves the dict (given without "method") and is the run:

@@ -2100,6 +2100,134 @@ def smooth_vote(logits, ist, counts, votes, margins, n0):
     _call("ud_smooth_vote", _p(logits), N, Cn, _p(ist), _p(counts), _p(votes), _p(margins), votes.shape[0], int(n0), _stream())
 
 
+# ---- attribution (csrc/attrib.hip): the path integral around the forward + d/dx, the heat map, the deletion / insertion masks ----
+ATTR_I = _rows("UD_ATTR_I_")
+ATTR_MODE = {"ig": _const("UD_ATTR_IG"), "grad": _const("UD_ATTR_GRAD")}
+ATTR_REDUCE = {"sum": _const("UD_ATTR_SUM"), "abs": _const("UD_ATTR_ABS")}
+ATTR_MASK = {"deletion": _const("UD_ATTR_DELETE"), "insertion": _const("UD_ATTR_INSERT")}
+
+
+def _chk_batch(x):
+    N = x.shape[0] if x.dim() >= 1 else 0
+    if N < 1 or x.numel() == 0:
+        raise ValueError(f"expected a batch [N, ...], got {tuple(x.shape)}")
+    return N, x.numel() // N
+
+
+def _chk_table(t, dtype, what):
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.dim() == 1 and t.numel() >= 1):
+        raise ValueError(f"{what} must be a contiguous {dtype} CUDA tensor [steps], got {t.dtype} {t.device} {tuple(t.shape)}")
+    return t.numel()
+
+
+def _chk_square(x, heat):
+    """x [N, 3, S, S] fp32 and heat [N, S, S] fp32: (N, S)"""
+    _chk(x, heat)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[0] < 1 or x.shape[2] < 1:
+        raise ValueError(f"expected [N, 3, S, S] images, got {tuple(x.shape)}")
+    N, S = x.shape[0], x.shape[2]
+    if tuple(heat.shape) != (N, S, S):
+        raise ValueError(f"a heat map is [{N}, {S}, {S}], got {tuple(heat.shape)}")
+    return N, S
+
+
+def attr_point(x, b, xp, k, alpha, iters):
+    """xp[n] = b[n] + alpha[k[n] % steps] (x[n] - b[n]) (alpha == 1: x, alpha == 0: b, bit for bit): x, b, xp fp32 [N, ...], k
+    int32 [N], alpha an fp32 table [steps]; a counter outside [0, iters) leaves its row of xp untouched."""
+    _chk_same(x, b, xp)
+    N, per = _chk_batch(x)
+    _chk_apart(x=x, xp=xp)
+    _chk_apart(b=b, xp=xp)
+    _chk_i32(k, (N,), "k")
+    steps = _chk_table(alpha, torch.float32, "alpha")
+    _call("ud_attr_point", _p(x), _p(b), _p(xp), _p(k), _p(alpha), steps, int(iters), N, per, _stream())
+    return xp
+
+
+def attr_accumulate(g, acc, k, w, iters):
+    """acc[n] += w[k[n] % steps] g[n] in double (one product, one add): g fp32 [N, ...], acc float64 of g's shape, k int32 [N], w a
+    float64 table [steps]; a counter outside [0, iters) leaves its row untouched."""
+    _chk(g)
+    N, per = _chk_batch(g)
+    if acc.shape != g.shape:
+        raise ValueError(f"acc must be like g {tuple(g.shape)}, got {tuple(acc.shape)}")
+    _chk_f64(acc, N * per)
+    _chk_i32(k, (N,), "k")
+    steps = _chk_table(w, torch.float64, "w")
+    _call("ud_attr_accumulate", _p(g), _p(acc), _p(k), _p(w), steps, int(iters), N, per, _stream())
+    return acc
+
+
+def attr_control(f, ist, path):
+    """path[k] = f and counter + 1 for k = ist's counter in [0, iters): f fp32 [N], path fp32 [iters, N]"""
+    _chk(f, path)
+    N = f.numel()
+    _chk_i32(ist, (len(ATTR_I), N), "ist")
+    if path.dim() != 2 or path.shape[0] < 1 or path.shape[1] != N:
+        raise ValueError(f"path must be [iters, {N}] with iters >= 1, got {tuple(path.shape)}")
+    _call("ud_attr_control", _p(f), _p(ist), _p(path), N, path.shape[0], _stream())
+
+
+def attr_finish_ws_bytes(N, per):
+    return _call("ud_attr_finish_ws_bytes", int(N), int(per))
+
+
+def attr_finish(x, b, acc, attr, heat, total, mode="ig", reduce="sum", scale=1.0, ws=None):
+    """attr = (x - b) acc scale ("ig") or acc scale ("grad") formed in double and rounded once; heat [N, S, S] = the channel sum
+    of the double values ("sum") or of their absolute values ("abs"); total [N] float64 = the sum of the double values, in a
+    fixed order.  ws: a float64 scratch of attr_finish_ws_bytes(N, 3 S^2) bytes, allocated unless given."""
+    _chk_same(x, b, attr)
+    N, S = _chk_square(x, heat)
+    if acc.shape != x.shape:
+        raise ValueError(f"acc must be like x {tuple(x.shape)}, got {tuple(acc.shape)}")
+    _chk_f64(acc, x.numel())
+    _chk_f64(total, N)
+    if mode not in ATTR_MODE or reduce not in ATTR_REDUCE:
+        raise ValueError(f"mode must be one of {tuple(ATTR_MODE)} and reduce one of {tuple(ATTR_REDUCE)}, got {mode!r}, {reduce!r}")
+    need = attr_finish_ws_bytes(N, 3 * S * S) // 8
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.float64, device=x.device)
+    _chk_f64(ws, need)
+    _call("ud_attr_finish", _p(x), _p(b), _p(acc), _p(attr), _p(heat), _p(total), _p(ws), ws.numel() * 8, ATTR_MODE[mode],
+          ATTR_REDUCE[reduce], float(scale), N, S, _stream())
+    return attr
+
+
+def _chk_thr(thr, K, N):
+    if not (thr.is_cuda and thr.dtype == torch.int64 and thr.is_contiguous() and tuple(thr.shape) == (K, N)):
+        raise ValueError(f"thr must be a contiguous int64 CUDA tensor [{K}, {N}] (the bits of the uint64 keys), got {thr.dtype} "
+                         f"{thr.device} {tuple(thr.shape)}")
+
+
+def attr_rank_select(heat, kcount, thr):
+    """thr[j, n] = the kcount[j]-th largest pixel key of heat[n] (the header's key: the heat's order, a NaN last, ties to the
+    lower pixel index), all ones for kcount[j] == 0: heat fp32 [N, ...], kcount int32 [K], thr int64 [K, N] holding the uint64 bits."""
+    _chk(heat)
+    N, HW = _chk_batch(heat)
+    K = kcount.numel()
+    _chk_i32(kcount, (K,), "kcount")
+    _chk_thr(thr, K, N)
+    _call("ud_attr_rank_select", _p(heat), _p(kcount), _p(thr), N, HW, K, _stream())
+    return thr
+
+
+def attr_mask(x, b, heat, thr, ist, xq, mode="deletion"):
+    """xq = x with the pixels whose key >= thr[j, n] taken from b ("deletion"), or b with those pixels taken from x ("insertion"),
+    j = ist's counter; a counter outside [0, K) leaves its row of xq untouched."""
+    _chk_same(x, b, xq)
+    N, S = _chk_square(x, heat)
+    _chk_apart(x=x, xq=xq)
+    _chk_apart(b=b, xq=xq)
+    _chk_i32(ist, (len(ATTR_I), N), "ist")
+    if thr.dim() != 2:
+        raise ValueError(f"thr must be [K, {N}], got {tuple(thr.shape)}")
+    _chk_thr(thr, thr.shape[0], N)
+    if mode not in ATTR_MASK:
+        raise ValueError(f"mode must be one of {tuple(ATTR_MASK)}, got {mode!r}")
+    _call("ud_attr_mask", _p(x), _p(b), _p(heat), _p(thr), _p(ist), _p(xq), ATTR_MASK[mode], N, S, thr.shape[0], _stream())
+    return xq
+
+
 # ---- decision-based minimum-norm attack (csrc/hsj.hip): propose / control per query, the distance and the gradient estimate -----
 HSJ_I, HSJ_F = _rows("UD_HSJ_I_"), _rows("UD_HSJ_F_")
 HSJ_P, HSJ_C = _rows("UD_HSJ_P_"), _rows("UD_HSJ_C_")

@@ -305,6 +305,20 @@ class RunnerMethods:
         from ..hsj import hsj_runner
         return hsj_runner(self, batch, size, **kwargs)
 
+    def attribution_runner(self, batch, size, **kwargs):
+        """The graph-replayed attribution — integrated gradients, or SmoothGrad / a plain saliency map: which pixels the score of
+        the label rests on, with the completeness defect `gap` — for [batch, 3, size, size] inputs (unidefense_amd/attrib.py:
+        AttributionRunner; kwargs: method, steps, rule, baseline, samples, sigma, score, reduce, seed, precision, grad_scale)."""
+        from ..attrib import attribution_runner
+        return attribution_runner(self, batch, size, **kwargs)
+
+    def deletion_runner(self, batch, size, **kwargs):
+        """The graph-replayed deletion / insertion curve that scores a heat map: the class probability while the map's top pixels
+        are replaced by the baseline, or inserted into it (unidefense_amd/attrib.py: DeletionRunner; kwargs: fractions, mode,
+        baseline, score, precision)."""
+        from ..attrib import deletion_runner
+        return deletion_runner(self, batch, size, **kwargs)
+
 
 class UniDefenseModelEb4(RunnerMethods, nn.Module):
     """UniDefense model with EfficientNet backbone (reference: model/unidefense.py:28-256)."""
