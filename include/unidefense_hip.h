@@ -1439,7 +1439,7 @@ int ud_dwtile_wgrad(const void* src, const ud_bn_ref* bn_in, const void* dy, con
  *   s1 += sum dz, s2 += sum dz * xhat (bn given; ws: ud_dwtile_ws_doubles(N, H, W, C) doubles),
  *   dwt[C][K*K] = gate * sum_pixels act(bn(x))(oh + i - P_t, ow + j - P_l) * dy(oh, ow)
  * (ud_dwtile epi 2 + ud_dwtile_wgrad, which read each operand twice).  wpart: ud_dwtile_wgrad_part_rows(N, H, W) rows.
- * dwt == NULL: the partial rows are left for ud_dwtile_wgrad_finalize_multi and their number is returned. */
+ * dwt == NULL: the partial rows are left for ud_param_fold_multi and their number is returned. */
 int ud_dwtile_bwd(const void* dy, const void* x, const ud_bn_ref* bn, const float* wt, const float* gate_alpha, int gate_mode,
                   const void* add, void* dz, float* dwt, float* wpart, long part_rows, double* s1, double* s2, double* ws,
                   int N, int H, int W, int C, int K, int P_t, int P_l, int f16, ud_stream_t stream);
@@ -1455,17 +1455,43 @@ int ud_dwtile_dgrad_eval(const void* dy, const float* wt, const float* gate_alph
  * outside csrc/dwtile.hip that produce them (ud_irfft2_dwbwd) */
 int ud_dwtile_wgrad_finalize(const float* part, int nparts, int K, int C, const float* gate_alpha, int gate_mode, float* dwt,
                              ud_stream_t stream);
-/* The folds of ALL depthwise convs of a backward pass in one launch per 48 items (the items travel by value in the kernel
- * arguments: capturable).  ud_dwtile_wgrad / ud_dwtile_bwd called with dwt == NULL leave their partial rows in `part` / `wpart` and
- * RETURN their number (> 0) instead of folding; ud_irfft2_dwbwd's wpart holds N rows.  The partial buffers must stay untouched
- * until this call. */
+/* The folds that only FINISH a parameter's gradient — nothing else in a backward reads their result — as items of ONE launch per
+ * 44 items (csrc/param_fold.hip; the items travel by value in the kernel arguments: capturable, no device table).  Every producer
+ * that leaves per-workgroup partials also folds through this entry point when called in its immediate form, so one kernel body
+ * (one summation order per kind) serves both.  Producers called with a NULL result pointer (ud_dwtile_wgrad / ud_dwtile_bwd dwt,
+ * ud_pw_bwd_fused / ud_pj_bwd_fused_a / _a_se dw, ud_conv_small_wgrad / ud_conv_mfma_wgrad out) leave their partials in `part` and
+ * RETURN their number (> 0) instead of folding; ud_irfft2_dwbwd's wpart holds N rows; ud_norm_bwd with dgamma == dbeta == NULL
+ * leaves the group sum to an item.  The partial buffers must stay untouched until this call.  Item kinds (p0, p1, p2 per kind):
+ *   UD_FOLD_DW      dst[C][K*K] = gate * sum_p part[p][K*K][C], fp64 (16 strided lanes, then lanes 0..15); p0 K, p1 C, p2 gate_mode,
+ *                   aux = gate_alpha
+ *   UD_FOLD_F32     dst[i] = sum_p part[p][i] (i < n), fp32: lane j of 16 adds partials j, j + 32, .. and j + 16, j + 48, .. in two chains, the 16
+ *                   lane sums then in order (the thin expand convs, the direct MFMA weight gradients); p2 = CE > 0: also
+ *                   dgamma[c] = (float)s2l[c], dbeta[c] = (float)s1l[c] for c < CE (CE <= 16 n)
+ *   UD_FOLD_PJ      UD_FOLD_F32's order over the column-chunked partials of ud_pj_bwd_fused_a: dst[co][c] = sum_p
+ *                   part[c / CC][p][co][c % CC]; nparts per chunk, n = CO CE, p0 CO, p1 CE, p2 CC
+ *   UD_FOLD_F64     dst[i] = sum_p part[p][i] (i < n), fp64: 16 strided lanes, then lanes 0..15 (ud_conv_small_wgrad)
+ *   UD_FOLD_GROUP   dgamma[c] = sum_g aux[g][c], dbeta[c] = sum_g part[g][c], fp64, ascending g (InstanceNorm: part = s1, aux = s2 of
+ *                   ud_norm_bwd); nparts = G, n = C; either result may be NULL
+ *   UD_FOLD_LAYOUT  dst = part in the parameter's layout (a permuting copy), n elements
+ * UD_FOLD_F32 / _F64 / _LAYOUT with p0 = KH KW > 1 and p1 = B write a conv weight gradient [A][KH KW][B] (n = A p0 p1) straight
+ * into the parameter's [A][B][KH][KW] (F.conv2d: A = Cout, B = Cin; ConvTranspose2d: A = Cin, B = Cout); p0 <= 1: as it is. */
+#define UD_FOLD_DW 0
+#define UD_FOLD_F32 1
+#define UD_FOLD_PJ 2
+#define UD_FOLD_F64 3
+#define UD_FOLD_GROUP 4
+#define UD_FOLD_LAYOUT 5
 typedef struct {
-    const float* part;          /* [nparts][K*K][C] */
-    float* dwt;                 /* [C][K*K] */
-    const float* gate_alpha;    /* gate_mode != 0 */
-    int nparts, K, C, gate_mode;
+    const float* part;          /* the partials [nparts][..] (UD_FOLD_LAYOUT: the source matrix) */
+    float* dst;                 /* the gradient (unused by UD_FOLD_GROUP) */
+    const float* aux;           /* UD_FOLD_DW: gate_alpha (gate_mode != 0); UD_FOLD_GROUP: s2 */
+    const double* s1l;          /* UD_FOLD_F32 with p2 > 0 */
+    const double* s2l;
+    float* dgamma;              /* UD_FOLD_F32 with p2 > 0, UD_FOLD_GROUP */
+    float* dbeta;
+    int kind, nparts, n, p0, p1, p2;
 } ud_wgrad_fold;
-int ud_dwtile_wgrad_finalize_multi(const ud_wgrad_fold* items, int n, ud_stream_t stream);
+int ud_param_fold_multi(const ud_wgrad_fold* items, int n, ud_stream_t stream);
 /* Half storage (the mixed-precision mode): ud_rfft2_ex of a half-stored x whose half result is laid straight into the ONE fp16
  * plane (P32 layout over [N S (S/2+1)] x 2C, scale 1) that ud_gemm_p3 prec 1 reads — no row-major spectrum, no layout pass.  The
  * one-kernel transform sizes (8, 16, 32, 12, 24, 48).  dw_wt / dw_out / dw_k as in ud_rfft2_ex_planes (the stride-1 depthwise conv

@@ -455,6 +455,7 @@ int launch_wgrad(const ud_conv_geom& g, const float* a, const float* x, float* p
     hipLaunchKernelGGL((conv_mfma_wgrad<C>), dim3((unsigned)parts, (unsigned)C::NY), dim3(256), 0, s, g, a, x, part, tiles_x, tiles_y,
                        (int)ntiles);
     UD_LAUNCH_CHECK();
+    if (!out) return parts;          // the caller folds the partials later (ud_param_fold_multi)
     return pw::fold_launch(part, parts, C::MA * 9 * C::CIN, out, nullptr, nullptr, 0, nullptr, nullptr, s);
 }
 
@@ -541,7 +542,7 @@ long ud_conv_mfma_wgrad_ws_floats(int Cin, int Ma) {
 
 // out[Ma][9*Cin] = sum over rows m = (n,oh,ow) of g's output grid of a[m][Ma] (x) patch(x)[m][9*Cin]; pointers 16-byte aligned
 int ud_conv_mfma_wgrad(const ud_conv_geom* g, const float* a, const float* x, float* part, float* out, int Ma, ud_stream_t stream) {
-    if (!g || !a || !x || !part || !out) return UD_EINVAL;
+    if (!g || !a || !x || !part) return UD_EINVAL;
     const int mode = mode_of(*g);
     if (mode < 0 || !ud_conv_mfma_wgrad_supported(g->Cin, Ma, mode)) return UD_EINVAL;
     if ((((uintptr_t)a | (uintptr_t)x) & 15) != 0) return UD_EINVAL;

@@ -208,22 +208,6 @@ __global__ __launch_bounds__(NT) void conv_small_wgrad(ud_conv_geom g, const flo
     }
 }
 
-// out[i] = sum_b part[b][i]; 16 entries x 16 partial-lanes per workgroup, fp64 accumulation
-__global__ __launch_bounds__(NT) void sum_partials(const float* __restrict__ part, int nparts, int n, float* __restrict__ out) {
-    __shared__ double sm[NT];
-    const int el = threadIdx.x & 15, pl = threadIdx.x >> 4;
-    const int i = blockIdx.x * 16 + el;
-    double acc = 0.0;
-    if (i < n)
-        for (int b = pl; b < nparts; b += 16) acc += (double)part[(long)b * n + i];
-    sm[threadIdx.x] = acc;
-    __syncthreads();
-    if (pl == 0 && i < n) {
-        for (int k = 1; k < 16; ++k) acc += sm[k * 16 + el];
-        out[i] = (float)acc;
-    }
-}
-
 constexpr int WGRAD_BLOCKS = 1024;
 
 template <int CIN, int MA>
@@ -234,10 +218,11 @@ int launch_wgrad(const ud_conv_geom& g, const float* a, const float* x, float* p
     const int blocks = (int)((M + rows - 1) / rows);
     hipLaunchKernelGGL((conv_small_wgrad<CIN, MA>), dim3(blocks), dim3(NT), 0, s, g, a, x, part, M, rows);
     UD_LAUNCH_CHECK();
-    const int n = MA * 9 * CIN;
-    hipLaunchKernelGGL(sum_partials, dim3(ud_cdiv(n, 16)), dim3(NT), 0, s, part, blocks, n, out);
-    UD_LAUNCH_CHECK();
-    return 0;
+    if (!out) return blocks;          // the caller folds the partials later (ud_param_fold_multi)
+    ud_wgrad_fold f{};                // out[i] = sum_b part[b][i], fp64: one UD_FOLD_F64 item of csrc/param_fold.hip
+    f.part = part; f.dst = out;
+    f.kind = UD_FOLD_F64; f.nparts = blocks; f.n = MA * 9 * CIN;
+    return ud_param_fold_multi(&f, 1, (ud_stream_t)s);
 }
 }  // namespace
 

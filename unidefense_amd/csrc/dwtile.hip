@@ -267,7 +267,7 @@ __global__ __launch_bounds__(NT, (kTileWaves<K, CQ, SW, EPI>)) void dw_tile_kern
 }
 
 // Weight gradient: acc[tap] += src_tile[.. + tap] * dy over the workgroup's tiles (images n0, n0 + nstep, ...), folded over
-// its pixel-threads, one fp32 partial row [K*K][C] per workgroup for dw_tile_wgrad_finalize.
+// its pixel-threads, one fp32 partial row [K*K][C] per workgroup for the UD_FOLD_DW fold.
 template <typename T, int K, int CQ, int SW, int ST = 1>
 __global__ __launch_bounds__(NT, 2) void dw_tile_wgrad_kernel(TileGeom g, const T* __restrict__ src, ud_bn_ref bn_in,
                                                            int has_bn_in, const T* __restrict__ dy, int n_step,
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(NT, 2) void dw_tile_wgrad_kernel(TileGeom g, const 
 // Here a workgroup stages BOTH halo tiles once per image — tileA = dy (zero outside the image), tileB = act(bn_in(x)) — and
 //   phase 1  da = gate * conv_flipped(tileA) [+ add];  dz = da * act'(bn_in(x)); dz stored; BatchNorm backward sums of dz
 //   phase 2  acc_w[i][j] += tileB(window + (i, j)) * tileA(centre)               (the dy strip comes out of the staged tile)
-// over images n0, n0 + n_step, ...; one fp32 partial row [K*K][C] per workgroup for dw_tile_wgrad_finalize and one fp64
+// over images n0, n0 + n_step, ...; one fp32 partial row [K*K][C] per workgroup for the UD_FOLD_DW fold and one fp64
 // partial (or atomics, <= 64 workgroups per channel) of the sums.  Tiles of (CQ, SW) = (8, 4): 16 x 8 outputs of 32 channels,
 // two halo tiles = 67 KB at K = 5 (two workgroups per CU); maps up to 8 x 8: (16, 4), the whole map of 64 channels.
 template <typename T, int K, int CQ, int SW>
@@ -534,74 +534,12 @@ __global__ __launch_bounds__(NT, 2) void dw_tile_bwd_kernel(TileGeom g, const T*
     }
 }
 
-// dw[c][tap] = gate * sum_p part[p][tap][c]   (fp64 accumulation; the parameter's own layout [C][K*K])
-__global__ __launch_bounds__(NT) void dw_tile_wgrad_finalize(int nparts, int KK, int C, const float* __restrict__ part,
-                                                             const float* __restrict__ gate_alpha, int gate_mode,
-                                                             float* __restrict__ dw) {
-    __shared__ double sm[16][16][4];
-    const int KKC = KK * C;
-    const int lane = threadIdx.x & 15, sl = threadIdx.x >> 4;
-    const int i = (blockIdx.x * 16 + lane) * 4;
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    if (i < KKC) {
-        const f32x4* p4 = reinterpret_cast<const f32x4*>(part + i);
-        const long step = (long)KKC / 4;
-        for (int p = sl; p < nparts; p += 16) {
-            const f32x4 v = p4[(long)p * step];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a[e] += (double)v[e];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sm[sl][lane][e] = a[e];
-    __syncthreads();
-    if (sl < 4 && i < KKC) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += sm[k][lane][sl];
-        const int o = i + sl, tap = o / C, c = o % C;
-        dw[(long)c * KK + tap] = (float)(t * (double)gate_factor(gate_alpha, gate_mode));
-    }
-}
-
-// The same fold for EVERY depthwise conv of a backward pass in one launch (ud_dwtile_wgrad_finalize_multi): the items travel by
-// value in the kernel arguments (no device table: the launch sits inside a captured graph), a workgroup finds its item by a scan
-// of the (uniform) block prefix.
-constexpr int FOLD_MAX = 48;
-struct FoldArgs {
-    ud_wgrad_fold it[FOLD_MAX];
-    int block0[FOLD_MAX + 1];
-    int n;
-};
-
-__global__ __launch_bounds__(NT) void dw_tile_wgrad_finalize_multi(const FoldArgs a) {
-    __shared__ double sm[16][16][4];
-    int j = 0;
-    while (j + 1 < a.n && (int)blockIdx.x >= a.block0[j + 1]) ++j;
-    const ud_wgrad_fold& f = a.it[j];
-    const int KK = f.K * f.K, C = f.C, KKC = KK * C, nparts = f.nparts;
-    const int lane = threadIdx.x & 15, sl = threadIdx.x >> 4;
-    const int i = (((int)blockIdx.x - a.block0[j]) * 16 + lane) * 4;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    if (i < KKC) {
-        const f32x4* p4 = reinterpret_cast<const f32x4*>(f.part + i);
-        const long step = (long)KKC / 4;
-        for (int p = sl; p < nparts; p += 16) {
-            const f32x4 w = p4[(long)p * step];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += (double)w[e];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sm[sl][lane][e] = v[e];
-    __syncthreads();
-    if (sl < 4 && i < KKC) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += sm[k][lane][sl];
-        const int o = i + sl, tap = o / C, c = o % C;
-        f.dwt[(long)c * KK + tap] = (float)(t * (double)gate_factor(f.gate_alpha, f.gate_mode));
-    }
+// the fold of the partial rows, dw[c][tap] = gate * sum_p part[p][tap][c]: one UD_FOLD_DW item of csrc/param_fold.hip
+inline int fold_dw_now(const float* part, int nparts, int K, int C, const float* gate_alpha, int gate_mode, float* dw, hipStream_t s) {
+    ud_wgrad_fold f{};
+    f.part = part; f.dst = dw; f.aux = gate_alpha;
+    f.kind = UD_FOLD_DW; f.nparts = nparts; f.p0 = K; f.p1 = C; f.p2 = gate_mode;
+    return ud_param_fold_multi(&f, 1, (ud_stream_t)s);
 }
 
 inline bool tile_args_ok(int N, int Hs, int Ws, int C, int Ho, int Wo, int K) {
@@ -677,12 +615,8 @@ int launch_wgrad(TileGeom g, const T* src, const ud_bn_ref* bn_in, const T* dy, 
     hipLaunchKernelGGL((dw_tile_wgrad_kernel<T, K, CQ, SW, ST>), grid, dim3(NT), lds, s, g, src, bi, bn_in ? 1 : 0, dy,
                        n_step, part);
     UD_LAUNCH_CHECK();
-    if (!dw) return (int)nparts;          // the caller folds the partial rows later (ud_dwtile_wgrad_finalize_multi)
-    const int KKC = K * K * g.C4 * 4;
-    hipLaunchKernelGGL(dw_tile_wgrad_finalize, dim3(ud_cdiv(KKC, 64)), dim3(NT), 0, s, (int)nparts, K * K, g.C4 * 4, part,
-                       gate_alpha, gate_mode, dw);
-    UD_LAUNCH_CHECK();
-    return 0;
+    if (!dw) return (int)nparts;          // the caller folds the partial rows later (ud_param_fold_multi)
+    return fold_dw_now(part, (int)nparts, K, g.C4 * 4, gate_alpha, gate_mode, dw, s);
 }
 
 template <typename T, int K, int CQ, int SW>
@@ -716,17 +650,16 @@ int launch_bwd(TileGeom g, const T* dy, const T* x, const ud_bn_ref* bn, const f
     hipLaunchKernelGGL((dw_tile_bwd_kernel<T, K, CQ, SW>), grid, dim3(NT), lds, s, g, dy, x, bn ? *bn : none, bn ? 1 : 0, wt,
                        gate_alpha, gate_mode, add, dz, n_step, wpart, use_part ? ws : nullptr, s1, s2);
     UD_LAUNCH_CHECK();
-    const int C = g.C4 * 4, KKC = K * K * C;
+    const int C = g.C4 * 4;
     if (dwt) {
-        hipLaunchKernelGGL(dw_tile_wgrad_finalize, dim3(ud_cdiv(KKC, 64)), dim3(NT), 0, s, (int)nparts, K * K, C, wpart,
-                           gate_alpha, gate_mode, dwt);
-        UD_LAUNCH_CHECK();
+        const int rc = fold_dw_now(wpart, (int)nparts, K, C, gate_alpha, gate_mode, dwt, s);
+        if (rc) return rc;
     }
     if (use_part) {
         hipLaunchKernelGGL(partials_to_acc, dim3(ud_cdiv(C, 8)), dim3(NT), 0, s, 2, 1, C, (int)nparts, ws, s1, s2);
         UD_LAUNCH_CHECK();
     }
-    return dwt ? 0 : (int)nparts;          // no dwt: the caller folds the partial rows later (ud_dwtile_wgrad_finalize_multi)
+    return dwt ? 0 : (int)nparts;          // no dwt: the caller folds the partial rows later (ud_param_fold_multi)
 }
 
 }  // namespace
@@ -847,37 +780,10 @@ int ud_dwtile_bwd(const void* dy, const void* x, const ud_bn_ref* bn, const floa
 #undef UD_BW
 }
 
-int ud_dwtile_wgrad_finalize_multi(const ud_wgrad_fold* items, int n, ud_stream_t stream) {
-    if (!items || n < 1) return UD_EINVAL;
-    for (int i = 0; i < n; ++i) {
-        const ud_wgrad_fold& f = items[i];
-        if (!f.part || !f.dwt || f.nparts < 1 || (f.K != 3 && f.K != 5) || f.C < 4 || f.C % 4 || f.gate_mode < 0 || f.gate_mode > 2 ||
-            (f.gate_mode != 0 && !f.gate_alpha))
-            return UD_EINVAL;
-    }
-    for (int i0 = 0; i0 < n; i0 += FOLD_MAX) {
-        FoldArgs a;
-        a.n = n - i0 < FOLD_MAX ? n - i0 : FOLD_MAX;
-        int b = 0;
-        for (int j = 0; j < a.n; ++j) {
-            a.it[j] = items[i0 + j];
-            a.block0[j] = b;
-            b += ud_cdiv(a.it[j].K * a.it[j].K * a.it[j].C, 64);
-        }
-        a.block0[a.n] = b;
-        hipLaunchKernelGGL(dw_tile_wgrad_finalize_multi, dim3((unsigned)b), dim3(NT), 0, (hipStream_t)stream, a);
-        UD_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
 int ud_dwtile_wgrad_finalize(const float* part, int nparts, int K, int C, const float* gate_alpha, int gate_mode, float* dwt,
                              ud_stream_t stream) {
     if (!part || nparts < 1 || (K != 3 && K != 5) || C < 4 || C % 4 || !dwt) return UD_EINVAL;
-    hipLaunchKernelGGL(dw_tile_wgrad_finalize, dim3(ud_cdiv(K * K * C, 64)), dim3(NT), 0, (hipStream_t)stream, nparts, K * K, C,
-                       part, gate_alpha, gate_mode, dwt);
-    UD_LAUNCH_CHECK();
-    return 0;
+    return fold_dw_now(part, nparts, K, C, gate_alpha, gate_mode, dwt, (hipStream_t)stream);
 }
 
 }  // extern "C"

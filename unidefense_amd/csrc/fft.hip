@@ -571,7 +571,7 @@ inline int xcd_remap_on(int run_bytes) {
 // x act'(bn0(e)), BatchNorm backward sums): four launches over (n, c) planes of 8 x 8 pixels — 57 us for 13 MB tensors.  Here the
 // workgroup that produces the da_f plane of (n, 64 channels) also stages the planes dd (the conv's output gradient) and a =
 // act(bn0(e)) in LDS and finishes the job: dz = (gate * conv_flipped(dd) + da_f) * act'(bn0(e)), its BatchNorm sums (fp64 atomics,
-// N workgroups per channel), and the weight-gradient partial [K*K][64] of its image (summed over N by dw_tile_wgrad_finalize).
+// N workgroups per channel), and the weight-gradient partial [K*K][64] of its image (summed over N by a UD_FOLD_DW fold).
 // Thread (h, c): row h of channel c throughout.  LDS: the transform's planes, then (aliased) the two staged planes, then the folds.
 // ---------------------------------------------------------------------------------------------------------
 template <int S, int CB, int K>

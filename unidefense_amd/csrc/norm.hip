@@ -169,7 +169,7 @@ __global__ __launch_bounds__(NT) void stats_finalize(int G, int R, int C, int P,
     }
 }
 
-// s1,s2: float [G][C] sums over chunks; for G == 1 also dgamma = s2, dbeta = s1 (saves the group_sum launch)
+// s1,s2: float [G][C] sums over chunks; for G == 1 also dgamma = s2, dbeta = s1 (saves the group sum: a UD_FOLD_GROUP item)
 __global__ __launch_bounds__(NT) void normbwd_finalize(int G, int C, int P, const double* __restrict__ part1,
                                                        const double* __restrict__ part2, float* __restrict__ s1o,
                                                        float* __restrict__ s2o, float* __restrict__ dgamma,
@@ -183,20 +183,6 @@ __global__ __launch_bounds__(NT) void normbwd_finalize(int G, int C, int P, cons
         if (dbeta) dbeta[idx] = (float)s1;
         if (dgamma) dgamma[idx] = (float)s2;
     }
-}
-
-// dgamma[c] = sum_g s2[g][c], dbeta[c] = sum_g s1[g][c]   (G > 1: InstanceNorm)
-__global__ void group_sum(int G, int C, const float* __restrict__ s1, const float* __restrict__ s2,
-                          float* __restrict__ dgamma, float* __restrict__ dbeta) {
-    int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double a = 0.0, b = 0.0;
-    for (int g = 0; g < G; ++g) {
-        a += (double)s1[(long)g * C + c];
-        b += (double)s2[(long)g * C + c];
-    }
-    if (dbeta) dbeta[c] = (float)a;
-    if (dgamma) dgamma[c] = (float)b;
 }
 
 __global__ __launch_bounds__(NT) void partial_sum_finalize(int G, int C, int P, const double* __restrict__ part1,
@@ -361,8 +347,11 @@ int ud_norm_bwd(const float* x, const float* dy, int G, int R, int C, const floa
     hipLaunchKernelGGL(normbwd_finalize, fin_grid(G, C), dim3(NT), 0, s, G, C, q.P, part1, part2, s1, s2, dgamma, dbeta);
     UD_LAUNCH_CHECK();
     if (G > 1 && (dgamma || dbeta)) {
-        hipLaunchKernelGGL(group_sum, dim3(ud_cdiv(C, 256)), dim3(256), 0, s, G, C, s1, s2, dgamma, dbeta);
-        UD_LAUNCH_CHECK();
+        ud_wgrad_fold f{};          // dgamma[c] = sum_g s2[g][c], dbeta[c] = sum_g s1[g][c]: one UD_FOLD_GROUP item (csrc/param_fold.hip)
+        f.part = s1; f.aux = s2; f.dgamma = dgamma; f.dbeta = dbeta;
+        f.kind = UD_FOLD_GROUP; f.nparts = G; f.n = C;
+        const int rc = ud_param_fold_multi(&f, 1, stream);
+        if (rc) return rc;
     }
     if (dx) {
         long total4 = (long)G * R * (C / 4);

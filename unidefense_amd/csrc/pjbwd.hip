@@ -388,32 +388,14 @@ __global__ __launch_bounds__(NTH, 2) void pj_bwd_a_kernel(PjArgs a) {
     }
 }
 
-// dw[co][c0 + cc] = the gc partials of chunk c0 / CC summed in workgroup order (the form of pw_bwd_fold_kernel: 16 elements x 16
-// lanes of partials per workgroup, the lane sums added in order through LDS)
-__global__ __launch_bounds__(256) void pj_fold_kernel(const float* __restrict__ part, int gc, int CO, int CE, int CC, float* __restrict__ dw) {
-    __shared__ float red[16][17];
-    const int el = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    const int i = blockIdx.x * 16 + el, numel = CO * CE;
-    float s0 = 0.f, s1 = 0.f;
-    if (i < numel) {
-        const int co = i / CE, c = i - co * CE, chunk = c / CC, cc = c - chunk * CC;
-        const float* src = part + (long)chunk * gc * (CO * CC) + co * CC + cc;
-        const long st = (long)CO * CC;
-        int p = grp;
-        for (; p + 16 < gc; p += 32) {
-            s0 += src[p * st];
-            s1 += src[(p + 16) * st];
-        }
-        if (p < gc) s0 += src[p * st];
-    }
-    red[grp][el] = s0 + s1;
-    __syncthreads();
-    if (grp == 0 && i < numel) {
-        float t = red[0][el];
-#pragma unroll
-        for (int j = 1; j < 16; ++j) t += red[j][el];
-        dw[i] = t;
-    }
+// dw[co][c0 + cc] = the gc partials of chunk c0 / CC summed in workgroup order: one UD_FOLD_PJ item of csrc/param_fold.hip; dw NULL: the
+// caller folds later and gets gc
+inline int pj_fold(const float* part, int gc, int CO, int CE, int CC, float* dw, hipStream_t st) {
+    if (!dw) return gc;
+    ud_wgrad_fold f{};
+    f.part = part; f.dst = dw;
+    f.kind = UD_FOLD_PJ; f.nparts = gc; f.n = CO * CE; f.p0 = CO; f.p1 = CE; f.p2 = CC;
+    return ud_param_fold_multi(&f, 1, (ud_stream_t)st);
 }
 
 // The dc tile of the dp image at `dimg` -> the fp32 tile `dcbuf` (from the MFMA layout: lane = column 16 nb + u, rows 16 mb + 4 g + r):
@@ -1009,7 +991,7 @@ int ud_pj_fwd_fused(const float* d, const ud_bn_ref* bn, const float* s, const f
 
 int ud_pj_bwd_fused_a(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* w, int N, int HW, int CE, int CO,
                       float* dw, double* dgate, float* part, ud_stream_t stream) {
-    if (!args_ok(d, dp, bn, s, w, N, HW, CE, CO) || !dw || !dgate || !part) return UD_EINVAL;
+    if (!args_ok(d, dp, bn, s, w, N, HW, CE, CO) || !dgate || !part) return UD_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     PjArgs a;
     fill(a, d, dp, bn, s, w, N, HW, CE, CO);
@@ -1020,9 +1002,7 @@ int ud_pj_bwd_fused_a(const float* d, const float* dp, const ud_bn_ref* bn, cons
                             : (CE == 336 ? launch_a<336, 56, 112>(a, grid, st) : launch_a<192, 56, 96>(a, grid, st));
     if (rc) return rc;
     UD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pj_fold_kernel, dim3((unsigned)ud_cdiv((long)CO * CE, 16)), dim3(256), 0, st, part, a.gc, CO, CE, chunk_of(CE, CO), dw);
-    UD_LAUNCH_CHECK();
-    return 0;
+    return pj_fold(part, a.gc, CO, CE, chunk_of(CE, CO), dw, st);
 }
 
 int ud_pj_bwd_fused_b(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,
@@ -1043,7 +1023,7 @@ int ud_pj_bwd_fused_b(const float* d, const float* dp, const ud_bn_ref* bn, cons
 
 int ud_pj_bwd_fused_a_se(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* w, int N, int HW, int CE,
                          int CO, float* dw, double* dots, float* part, ud_stream_t stream) {
-    if (!args_ok(d, dp, bn, s, w, N, HW, CE, CO) || !ud_pj_bwd_fused_se_ok(CE, CO, HW) || !dw || !dots || !part) return UD_EINVAL;
+    if (!args_ok(d, dp, bn, s, w, N, HW, CE, CO) || !ud_pj_bwd_fused_se_ok(CE, CO, HW) || !dots || !part) return UD_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     PjArgs a;
     fill(a, d, dp, bn, s, w, N, HW, CE, CO);
@@ -1053,9 +1033,7 @@ int ud_pj_bwd_fused_a_se(const float* d, const float* dp, const ud_bn_ref* bn, c
                             : (CE == 336 ? launch_a<336, 56, 112, true>(a, grid, st) : launch_a<192, 56, 96, true>(a, grid, st));
     if (rc) return rc;
     UD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pj_fold_kernel, dim3((unsigned)ud_cdiv((long)CO * CE, 16)), dim3(256), 0, st, part, a.gc, CO, CE, chunk_of(CE, CO), dw);
-    UD_LAUNCH_CHECK();
-    return 0;
+    return pj_fold(part, a.gc, CO, CE, chunk_of(CE, CO), dw, st);
 }
 
 int ud_pj_bwd_fused_c(const float* d, const float* dp, const ud_bn_ref* bn, const float* s, const float* dpool, float inv_hw,

@@ -11,7 +11,7 @@
 // three exact bf16 pieces, lays them into ONE row-major LDS image and runs both products from that image: the data gradient reads
 // rows (ds_read_b128: k = channels), the weight gradient reads the SAME image column-wise (ds_read_b64_tr_b16: k = rows).  W lives
 // in registers as bf16 fragments for the whole kernel; the weight gradient accumulates in registers over all the workgroup's tiles
-// and leaves one partial per workgroup, folded in a fixed order by pw_bwd_fold_kernel (deterministic by construction).
+// and leaves one partial per workgroup, folded in a fixed order by a UD_FOLD_F32 item (csrc/param_fold.hip) (deterministic by construction).
 // Arithmetic = gemm_x3's: six piece products of order <= 2^-16 per k-step on v_mfma_f32_16x16x32_bf16, fp32 accumulation.
 #include "pw_common.h"
 
@@ -307,40 +307,6 @@ __global__ __launch_bounds__(NTH, WPC) void pw_bwd_kernel(PwArgs a) {
     }
 }
 
-// dW = the partials summed in a FIXED order; dgamma / dbeta from this rank's sums (ud_normbwd_apply's side outputs).
-// Workgroup = 16 consecutive elements x 16 lanes of partials: lane group j adds partials j, j + 16, ... (independent loads, 64-byte
-// segments), the 16 group sums are added in order through LDS.  (A first form — one thread per element walking all 512 partials —
-// took 40-50 us: 14 workgroups of dependent loads; profiles/r06/pw_bwd_fused.txt.)
-__global__ __launch_bounds__(256) void pw_bwd_fold_kernel(const float* __restrict__ part, int nparts, int numel, float* __restrict__ dw,
-                                                          const double* __restrict__ s1l, const double* __restrict__ s2l, int CE,
-                                                          float* __restrict__ dgamma, float* __restrict__ dbeta) {
-    __shared__ float red[16][17];
-    const int el = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    const int i = blockIdx.x * 16 + el;
-    float s0 = 0.f, s1 = 0.f;
-    if (i < numel) {
-        int p = grp;
-        for (; p + 16 < nparts; p += 32) {
-            s0 += part[(long)p * numel + i];
-            s1 += part[(long)(p + 16) * numel + i];
-        }
-        if (p < nparts) s0 += part[(long)p * numel + i];
-    }
-    red[grp][el] = s0 + s1;
-    __syncthreads();
-    if (grp == 0 && i < numel) {
-        float t = red[0][el];
-#pragma unroll
-        for (int j = 1; j < 16; ++j) t += red[j][el];
-        dw[i] = t;
-    }
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c < CE) {
-        if (dbeta) dbeta[c] = (float)s1l[c];
-        if (dgamma) dgamma[c] = (float)s2l[c];
-    }
-}
-
 template <int CE, int CIN, int D, int WPC>
 int launch(const PwArgs& a, int grid, hipStream_t s) {
     using CF = PwCfg<CE, CIN>;
@@ -353,12 +319,15 @@ int g_pw_form = 0;          // tools/bench_pwbwd.py: 0 the shipped form per shap
 
 }  // namespace
 
+// dW = the partials summed in a FIXED order; dgamma / dbeta from this rank's sums (ud_normbwd_apply's side outputs): one UD_FOLD_F32
+// item of csrc/param_fold.hip.  (A first form — one thread per element walking all 512 partials — took 40-50 us: 14 workgroups of
+// dependent loads; profiles/r06/pw_bwd_fused.txt.)
 int pw::fold_launch(const float* part, int nparts, int numel, float* dw, const double* s1l, const double* s2l, int CE, float* dgamma,
                     float* dbeta, hipStream_t s) {
-    hipLaunchKernelGGL(pw_bwd_fold_kernel, dim3((unsigned)ud_cdiv(numel, 16)), dim3(256), 0, s, part, nparts, numel, dw, s1l, s2l, CE,
-                       dgamma, dbeta);
-    UD_LAUNCH_CHECK();
-    return 0;
+    ud_wgrad_fold f{};
+    f.part = part; f.dst = dw; f.s1l = s1l; f.s2l = s2l; f.dgamma = dgamma; f.dbeta = dbeta;
+    f.kind = UD_FOLD_F32; f.nparts = nparts; f.n = numel; f.p2 = (dgamma || dbeta) ? CE : 0;
+    return ud_param_fold_multi(&f, 1, (ud_stream_t)s);
 }
 
 extern "C" {
@@ -381,7 +350,7 @@ int ud_pw_bwd_fused(const float* e, const float* dz, const ud_bn_ref* bn, const 
                     const double* s2_local, const float* x, const float* w, const float* add, long M, int CE, int CIN, float* dx,
                     float* dw, float* part, float* dgamma, float* dbeta, ud_stream_t stream) {
     if (ud_bn_eval_form(bn)) return UD_EINVAL;          // a backward: the eval form of ud_bn_ref is a forward-only BatchNorm
-    if (!e || !dz || !bn || !s1 || !s2 || !x || !w || !dx || !dw || !part || M < 1 || !ud_pw_bwd_fused_ok(CE, CIN) || bn->G != 1 ||
+    if (!e || !dz || !bn || !s1 || !s2 || !x || !w || !dx || !part || M < 1 || !ud_pw_bwd_fused_ok(CE, CIN) || bn->G != 1 ||
         !bn->gamma)
         return UD_EINVAL;
     if ((dgamma || dbeta) && (!s1_local || !s2_local)) return UD_EINVAL;
@@ -401,6 +370,7 @@ int ud_pw_bwd_fused(const float* e, const float* dz, const ud_bn_ref* bn, const 
            : form == 3 ? launch<192, 32, 3, 1>(a, grid, s) : launch<192, 32, 4, 1>(a, grid, s);
     if (rc) return rc;
     UD_LAUNCH_CHECK();
+    if (!dw) return grid;          // the caller folds the partials later (ud_param_fold_multi), dgamma / dbeta with them
     return pw::fold_launch(part, grid, CE * CIN, dw, s1_local, s2_local, CE, dgamma, dbeta, s);
 }
 

@@ -5,6 +5,7 @@ torch — torch only owns device memory and the stream.
 Tensor convention: fp32, contiguous, pixel-major [N, H, W, C] (a row-major matrix [N*H*W, C]);
 image-domain 3-channel tensors are planes [N, 3, H, W].
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -2345,8 +2346,28 @@ def hsj_estimate(v, phi, ids, B, draw0, norm, seed, ist=None):
     return v
 
 
-def conv_gather_wgrad(a, x, g):
-    """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)]."""
+def conv_wgrad_param(a, x, g):
+    """conv_gather_wgrad in the parameter's layout [Ma, Cin, KH, KW] (g.Cin the gathered channels: F.conv2d's weight with a = dy,
+    ConvTranspose2d's with a = x).  While a tape's backward collects the folds, the kernels that leave partials keep them and the
+    flush's launch folds them straight into that layout; a GEMM's [Ma, KH*KW*Cin] result is copied into it there."""
+    shape = (a.shape[-1], g.Cin, g.KH, g.KW)
+    if not folds_deferred():
+        return conv_gather_wgrad(a, x, g).view(shape[0], g.KH, g.KW, g.Cin).permute(0, 3, 1, 2).contiguous()
+    dst = empty(shape, a)
+    out = conv_gather_wgrad(a, x, g, dst)
+    if out is not dst:
+        _defer_fold("layout", (dst,), part=out, dst=dst, nparts=1, n=out.numel(), p0=g.KH * g.KW, p1=g.Cin)
+    return dst
+
+
+def _defer_conv_fold(kind, part, nparts, out, n, g, layout):
+    """the fold of a conv weight gradient's partials [nparts][Ma][KH*KW*Cin] as an item; layout: out is the parameter's [Ma, Cin, KH, KW]"""
+    _defer_fold(kind, (out,), part=part, dst=out, nparts=int(nparts), n=int(n), p0=g.KH * g.KW if layout else 0, p1=g.Cin if layout else 0)
+
+
+def conv_gather_wgrad(a, x, g, param_dst=None):
+    """out[Ma, KH*KW*Cin] = a[(n,oh,ow), Ma]^T @ gather(x)[(n,oh,ow), (tap,ci)].  param_dst (conv_wgrad_param, folds being collected):
+    a kernel that leaves partials defers their fold into param_dst [Ma, Cin, KH, KW] and returns it."""
     _chk(a, x)
     Kdim = g.N * g.Hout * g.Wout
     Ma = a.shape[-1]
@@ -2354,15 +2375,19 @@ def conv_gather_wgrad(a, x, g):
     Ncols = g.KH * g.KW * g.Cin
     if _conv_mfma_wgrad_takes(g, Ma, Kdim, a, x):
         # decoder conv / transposed-conv weight gradients: pixels as the MFMA's reduction index, partials folded in a fixed order
-        ws = _CONV_MFMA_WS.get(a, _call("ud_conv_mfma_wgrad_ws_floats", g.Cin, Ma))
-        out = empty((Ma, Ncols), a)
-        _call("ud_conv_mfma_wgrad", C.byref(g), _p(a), _p(x), _p(ws), _p(out), Ma, _stream())
+        ws, defer = _wgrad_part(a, _call("ud_conv_mfma_wgrad_ws_floats", g.Cin, Ma), _CONV_MFMA_WS)
+        out = empty((Ma, Ncols), a) if param_dst is None else param_dst
+        nparts = _call("ud_conv_mfma_wgrad", C.byref(g), _p(a), _p(x), _p(ws), None if defer else _p(out), Ma, _stream())
+        if defer:
+            _defer_conv_fold("f32", ws, nparts, out, Ma * Ncols, g, param_dst is not None)
         return out
     if _CONV_SMALL and Kdim >= _CONV_SMALL_MIN_M and _conv_small_wgrad_supported(g.Cin, Ma, g.KH, g.KW):
         # a 20 x 180 (3 x 180, 48 x 27) result reduced over 524 288 rows: streamed through LDS, register-blocked
-        ws = _CONV_SMALL_WS.get(a, _call("ud_conv_small_wgrad_ws_floats", g.Cin, Ma))
-        out = empty((Ma, Ncols), a)
-        _call("ud_conv_small_wgrad", C.byref(g), _p(a), _p(x), _p(ws), _p(out), Ma, _stream())
+        ws, defer = _wgrad_part(a, _call("ud_conv_small_wgrad_ws_floats", g.Cin, Ma), _CONV_SMALL_WS)
+        out = empty((Ma, Ncols), a) if param_dst is None else param_dst
+        nparts = _call("ud_conv_small_wgrad", C.byref(g), _p(a), _p(x), _p(ws), None if defer else _p(out), Ma, _stream())
+        if defer:
+            _defer_conv_fold("f64", ws, nparts, out, Ma * Ncols, g, param_dst is not None)
         return out
     split = _pick_split(_tiles(Ma, Ncols), Kdim)
     if g.Cin % 4 == 0 and Ma % 4 == 0:
@@ -2465,15 +2490,19 @@ def norm_apply(x2, G, R, mean, invstd, gamma, beta, act):
 
 
 def norm_bwd(x2, dy, G, R, mean, invstd, gamma, beta, act):
-    """Returns (dx, dgamma[C], dbeta[C])."""
+    """Returns (dx, dgamma[C], dbeta[C]).  G > 1 while a tape's backward collects the folds: the sum over the groups into dgamma /
+    dbeta is an item of the flush's launch."""
     _chk(x2, dy)
     Cc = x2.shape[-1]
     s = empty((2, G, Cc), x2)
     dg = empty((Cc,), x2)
     db = empty((Cc,), x2)
     dx = torch.empty_like(x2)
+    defer = G > 1 and folds_deferred()
     _call("ud_norm_bwd", _p(x2), _p(dy), G, R, Cc, _p(mean), _p(invstd), _p(gamma), _p(beta), int(act),
-          _reduce_ws(x2, G, R, Cc), _p(s[0]), _p(s[1]), _p(dg), _p(db), _p(dx), _stream())
+          _reduce_ws(x2, G, R, Cc), _p(s[0]), _p(s[1]), None if defer else _p(dg), None if defer else _p(db), _p(dx), _stream())
+    if defer:
+        _defer_fold("group", (dg, db), keep=(s,), part=s[0], aux=s[1], dgamma=dg, dbeta=db, nparts=G, n=Cc)
     return dx, dg, db
 
 
@@ -3614,8 +3643,12 @@ def expand_bwd_fused(e, dz, bn, sacc, sacc_local, x2, w2, add=None):
     db = empty((Ce,), x2)
     grid = _lib.call("ud_pw_bwd_fused_grid", M)
     part = empty((grid, Ce * Cin), x2)
-    _call("ud_pw_bwd_fused", _p(e), _p(dz), C.byref(bn.ref()), _pd(sacc), _pd(sacc, Ce), _pd(loc), _pd(loc, Ce), _p(x2), _p(w2),
-          _p(add), M, Ce, Cin, _p(dx), _p(dw), _p(part), _p(dg), _p(db), _stream())
+    defer = folds_deferred()
+    nparts = _call("ud_pw_bwd_fused", _p(e), _p(dz), C.byref(bn.ref()), _pd(sacc), _pd(sacc, Ce), _pd(loc), _pd(loc, Ce), _p(x2), _p(w2),
+                   _p(add), M, Ce, Cin, _p(dx), None if defer else _p(dw), _p(part), _p(dg), _p(db), _stream())
+    if defer:          # dW's partials, and dgamma / dbeta from the fp64 sums, finished by the flush's launch
+        _defer_fold("f32", (dw, dg, db), keep=(loc,), part=part, dst=dw, s1l=loc.data_ptr(), s2l=loc.data_ptr() + 8 * Ce, dgamma=dg,
+                    dbeta=db, nparts=int(nparts), n=Ce * Cin, p2=Ce)
     return dx, dw, dg, db
 
 
@@ -3645,6 +3678,11 @@ def project_fwd_fused(d, bn, s, w2, N, HW, stats=None):
     return p, ctx
 
 
+def _defer_pj_fold(part, gc, grid, Co, Ce, dw):
+    """the fold of ud_pj_bwd_fused_a's partials as an item: gc partials for each of the grid / gc column chunks of Ce"""
+    _defer_fold("pj", (dw,), part=part, dst=dw, nparts=int(gc), n=Co * Ce, p0=Co, p1=Ce, p2=Ce // (grid // gc))
+
+
 def project_bwd_fused_a(d, bn, s, dp2, w2, N, HW, dgate):
     """dw[Co, Ce] = dp^T (act(bn(d)) sigmoid(s)) and dgate[N, Ce] (fp64, zeroed by the caller) += sum_hw (dp w) act(bn(d)) in one
     pass over d [N, .., Ce]; dp2 [N HW, Co]; w2 [Co, Ce]; s [N, Ce]."""
@@ -3654,7 +3692,11 @@ def project_bwd_fused_a(d, bn, s, dp2, w2, N, HW, dgate):
     dw = empty((Co, Ce), d)
     grid = _lib.call("ud_pj_bwd_fused_grid", N, HW, Ce, Co)
     part = empty((grid, Co * Ce), d)          # (an upper bound: a workgroup's partial covers its chunk of the Ce columns)
-    _call("ud_pj_bwd_fused_a", _p(d), _p(dp2), C.byref(bn.ref()), _p(s), _p(w2), N, HW, Ce, Co, _p(dw), _pd(dgate), _p(part), _stream())
+    defer = folds_deferred()
+    gc = _call("ud_pj_bwd_fused_a", _p(d), _p(dp2), C.byref(bn.ref()), _p(s), _p(w2), N, HW, Ce, Co, None if defer else _p(dw),
+               _pd(dgate), _p(part), _stream())
+    if defer:
+        _defer_pj_fold(part, gc, grid, Co, Ce, dw)
     return dw
 
 
@@ -3683,8 +3725,11 @@ def project_bwd_fused_a_se(d, bn, s, dp2, w2, N, HW, dots):
     dw = empty((Co, Ce), d)
     grid = _lib.call("ud_pj_bwd_fused_grid", N, HW, Ce, Co)
     part = empty((grid, Co * Ce), d)          # (an upper bound, as in project_bwd_fused_a)
-    _call("ud_pj_bwd_fused_a_se", _p(d), _p(dp2), C.byref(bn.ref()), _p(s), _p(w2), N, HW, Ce, Co, _p(dw), _pd(dots), _p(part),
-          _stream())
+    defer = folds_deferred()
+    gc = _call("ud_pj_bwd_fused_a_se", _p(d), _p(dp2), C.byref(bn.ref()), _p(s), _p(w2), N, HW, Ce, Co, None if defer else _p(dw),
+               _pd(dots), _p(part), _stream())
+    if defer:
+        _defer_pj_fold(part, gc, grid, Co, Ce, dw)
     return dw
 
 
@@ -4015,48 +4060,79 @@ def dwtile_dgrad_eval(dy, wt, K, pad_t, pad_l, x, bn, gate_alpha=None, gate_mode
     return dx
 
 
-# The depthwise weight gradients come out of their kernels as partial rows [parts][K*K][C] that a small launch folds into the
-# parameter's layout: 47 such launches per UDEB4 backward (~5 us each, the floor).  While a tape's backward collects them
-# (begin_wgrad_folds ... flush_wgrad_folds: Tape.backward), every conv keeps its rows in a buffer of its own and ONE launch folds
-# them all at the end (ud_dwtile_wgrad_finalize_multi).  A gradient that is read before the end — a second use of the parameter,
-# a data-parallel reducer taking it as soon as it is complete — flushes first (Tape.add_param_grad).
+# Launches that only FINISH a parameter's gradient: the folds of per-workgroup partials into a weight gradient (depthwise convs: 47 per
+# UDEB4 backward; the thin expand / project convs; the direct MFMA and small-conv weight gradients), InstanceNorm's sum over samples
+# into dgamma / dbeta, the copy of a conv weight gradient into the parameter's layout.  Nothing in the backward reads their result,
+# yet each costs the ~5 us launch floor on the replayed graph's one queue.  While a tape's backward collects them (begin_wgrad_folds
+# ... flush_wgrad_folds: Tape.backward), every producer keeps its partials in a buffer of its own and ONE launch per 44 items finishes
+# them all at the end (ud_param_fold_multi: the same kernel, the same order of summation as the immediate form).  A gradient that is
+# read before the end — a second use of the parameter, a data-parallel reducer taking it as soon as it is complete — flushes first
+# (Tape.add_param_grad).
 _WGRAD_FOLDS = None
 _WGRAD_PART_WS = Scratch(torch.float32)
+_FOLDS_IMMEDIATE = False
+FOLD_KINDS = _rows("UD_FOLD_")
+
+
+@contextlib.contextmanager
+def immediate_folds():
+    """every backward started inside folds each gradient at once, as calls outside a tape do (tests and tools: the reference form)"""
+    global _FOLDS_IMMEDIATE
+    prev, _FOLDS_IMMEDIATE = _FOLDS_IMMEDIATE, True
+    try:
+        yield
+    finally:
+        _FOLDS_IMMEDIATE = prev
 
 
 def begin_wgrad_folds():
     global _WGRAD_FOLDS
     if _WGRAD_FOLDS:
         flush_wgrad_folds()          # a backward started inside another one's: the outer tape's pending folds are done first, not dropped
-    _WGRAD_FOLDS = []
+    _WGRAD_FOLDS = None if _FOLDS_IMMEDIATE else []
 
 
 def flush_wgrad_folds(end=False):
-    """fold every collected weight gradient now (end: and stop collecting)"""
+    """finish every collected gradient now (end: and stop collecting)"""
     global _WGRAD_FOLDS
     items = _WGRAD_FOLDS
     if items:
         from .lib import WgradFold
         arr = (WgradFold * len(items))()
-        for a, (part, nparts, K_, Cc, alpha, mode, dwt) in zip(arr, items):
-            a.part, a.dwt, a.gate_alpha = part.data_ptr(), dwt.data_ptr(), (alpha.data_ptr() if alpha is not None else None)
-            a.nparts, a.K, a.C, a.gate_mode = int(nparts), int(K_), int(Cc), int(mode)
-        _call("ud_dwtile_wgrad_finalize_multi", arr, len(items), _stream())
-        for it in items:
-            it[6]._ud_deferred = False
+        for a, (fields, _keep, _dsts) in zip(arr, items):
+            for k, v in fields.items():
+                setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+        _call("ud_param_fold_multi", arr, len(items), _stream())
+        for _fields, _keep, dsts in items:
+            for t in dsts:
+                t._ud_deferred = False
     _WGRAD_FOLDS = None if (end or items is None) else []
 
 
-def _wgrad_part(like, need):
-    """the partial-row buffer of one depthwise weight gradient: the shared scratch, or (folds being collected) its own"""
+def folds_deferred():
+    """is a tape's backward collecting the parameter-gradient folds?"""
+    return _WGRAD_FOLDS is not None
+
+
+def _wgrad_part(like, need, ws=None):
+    """the partial buffer of one weight gradient: the producer's shared scratch, or (folds being collected) its own"""
     if _WGRAD_FOLDS is not None:
         return torch.empty(need, dtype=torch.float32, device=like.device), True
-    return _WGRAD_PART_WS.get(like, need), False
+    return (_WGRAD_PART_WS if ws is None else ws).get(like, need), False
+
+
+def _defer_fold(kind, dsts, keep=(), **fields):
+    """one item of the flush's launch (the fields of ud_wgrad_fold; tensors go as their pointers); dsts: the gradients it finishes, keep:
+    what must stay alive (and untouched) until then"""
+    for t in dsts:
+        t._ud_deferred = True
+    fields["kind"] = FOLD_KINDS[kind]
+    _WGRAD_FOLDS.append((fields, tuple(keep) + tuple(v for v in fields.values() if isinstance(v, torch.Tensor)), tuple(dsts)))
 
 
 def _defer_wgrad_fold(part, nparts, K_, Cc, gate_alpha, gate_mode, dwt):
-    dwt._ud_deferred = True
-    _WGRAD_FOLDS.append((part, nparts, K_, Cc, gate_alpha if gate_mode else None, gate_mode, dwt))
+    _defer_fold("dw", (dwt,), part=part, dst=dwt, aux=gate_alpha if gate_mode else None, nparts=int(nparts), p0=int(K_), p1=int(Cc),
+                p2=int(gate_mode))
 
 
 def dwtile_bwd_weight(x, dy, K, pad_t, pad_l, bn=None, gate_alpha=None, gate_mode=0, stride=1):

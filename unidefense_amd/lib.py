@@ -152,7 +152,7 @@ SplitItem = _abi.structs["ud_split_item"]          # one weight matrix of ud_spl
 LayoutItem = _abi.structs["ud_layout_item"]        # one conv weight of ud_weight_layouts_multi's device table
 BnRef = _abi.structs["ud_bn_ref"]                  # a deferred BatchNorm, applied by the consuming kernel
 LossTail = _abi.structs["ud_loss_tail"]            # the scalar tail of a pass's loss (ud_loss_tail_run)
-WgradFold = _abi.structs["ud_wgrad_fold"]          # one depthwise weight-gradient fold of ud_dwtile_wgrad_finalize_multi
+WgradFold = _abi.structs["ud_wgrad_fold"]          # one item of ud_param_fold_multi: a launch that only finishes a parameter's gradient
 
 EXPORTED = tuple(_abi.protos)
 

@@ -34,7 +34,7 @@ class Tape:
         self.param_ready = None
         self.param_uses = None
         self.param_seen = {}
-        self._deferred = set()   # id(param) whose stored gradient still waits for the one-launch fold (kernels.flush_wgrad_folds)
+        self._deferred = set()   # id(param) whose stored gradient still waits for the flush's launch (kernels.flush_wgrad_folds)
         self.weight_snapshot = None      # kernels.weight_batch_snapshot() of the forward (checked before the replay)
         # gradient with respect to the input image: `input` is the tracked x planes [N,3,H,W] (model(x) with x.requires_grad
         # and no perturbation), its gradient is left in `input_grad` by backward().  wgrad_on = False: no parameter takes a
@@ -100,7 +100,7 @@ class Tape:
     def backward(self):
         if self.weight_snapshot is not None:
             K.weight_batch_check(self.weight_snapshot)
-        K.begin_wgrad_folds()          # the depthwise weight gradients' folds: one launch at the end instead of one per conv
+        K.begin_wgrad_folds()          # the launches that only finish a parameter's gradient: one at the end instead of one each
         try:
             for fn in reversed(self.nodes):
                 fn()
@@ -256,8 +256,7 @@ def conv_dense(tape, x, w, stride, pad_t, pad_l, Hout, Wout, need_dx=True, x_pla
             elif stem_dx:
                 _stem_dgrad(tape, dy, w, g, x_planes)
             if _wgrad(tape):
-                dw = K.conv_gather_wgrad(dy.view(-1, Co), x, g)        # [Co, KH*KW*Ci]
-                tape.add_param_grad(w, dw.view(Co, KH, KW, Ci).permute(0, 3, 1, 2).contiguous())
+                tape.add_param_grad(w, K.conv_wgrad_param(dy.view(-1, Co), x, g))        # [Co, Ci, KH, KW]
         tape.record(bwd)
     return y
 
@@ -282,8 +281,7 @@ def conv_transpose_s2(tape, x, w):
             gd = K.conv_geom(N, Ho, Wo, Co, H, W, KH, KW, 2, 1, 1, 0)
             tape.add_grad(x, K.conv_gather_nt(dy, wd, gd))
             if _wgrad(tape):
-                dw = K.conv_gather_wgrad(x.view(-1, Ci), dy, gd)       # [Ci, KH*KW*Co]
-                tape.add_param_grad(w, dw.view(Ci, KH, KW, Co).permute(0, 3, 1, 2).contiguous())
+                tape.add_param_grad(w, K.conv_wgrad_param(x.view(-1, Ci), dy, gd))       # [Ci, Co, KH, KW]
         tape.record(bwd)
     return y
 
@@ -881,8 +879,7 @@ def conv_dense_any(tape, x, w, stride, pad, need_dx=True, x_planes=None):
             elif stem_dx:
                 _stem_dgrad(tape, dy, w, g, x_planes)
             if _wgrad(tape):
-                dw = K.conv_gather_wgrad(dy.view(-1, Co), x, g)
-                tape.add_param_grad(w, dw.view(Co, KH, KW, Ci).permute(0, 3, 1, 2).contiguous())
+                tape.add_param_grad(w, K.conv_wgrad_param(dy.view(-1, Co), x, g))
         tape.record(bwd)
     return y
 
