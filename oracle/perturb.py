@@ -68,12 +68,14 @@ def spatial_style_transfer(content, style, lmda):
     return out.reshape(b, c, h, w)
 
 
-def mat_sqrt(x):
-    u, d, vh = np.linalg.svd(x)
+def mat_sqrt(x, svd=None):
+    """U sqrt(D) V: NOT invariant under the sign a solver gives a singular pair (u_i, v_i) -> (-u_i, -v_i).  `svd` lets a caller
+    hand in a solver with a pinned sign convention (tests/perturb_cases.py:reference_svd); the default is numpy's own."""
+    u, d, vh = (svd or np.linalg.svd)(x)
     return u @ np.diag(np.sqrt(d)) @ vh.T      # the reference calls svd's third output V and transposes it
 
 
-def coral_one(source, target):
+def coral_one(source, target, svd=None):
     def stats(t):
         f = t.reshape(3, -1)
         mean = f.mean(-1, keepdims=True)
@@ -83,13 +85,13 @@ def coral_one(source, target):
 
     s_n, _, _, s_cov = stats(source)
     _, t_mean, t_std, t_cov = stats(target)
-    out = mat_sqrt(t_cov) @ (np.linalg.inv(mat_sqrt(s_cov)) @ s_n)
+    out = mat_sqrt(t_cov, svd) @ (np.linalg.inv(mat_sqrt(s_cov, svd)) @ s_n)
     return (out * t_std + t_mean).reshape(source.shape)
 
 
-def coral(source, target):
+def coral(source, target, svd=None):
     """model/unidefense.py:186-190: per sample, coral(style_i, content_i)."""
-    return np.stack([coral_one(s, t) for s, t in zip(source, target)], 0)
+    return np.stack([coral_one(s, t, svd) for s, t in zip(source, target)], 0)
 
 
 def random_noise(x, noise):

@@ -50,24 +50,11 @@ def test_oracle_functions_vs_reference_golden(golden_dir):
 
 def _replay_branch(g, x, name):
     """The draws of model/unidefense.py:177-198 from the seeded global generator, fed to the oracle."""
+    from tests.perturb_cases import replay_branch
     seed, color = [int(v) for v in g[f"branch_{name}_seed"]]
-    torch.manual_seed(seed)
-    style_branch = bool(torch.rand(1) > 0.5)
-    if style_branch:
-        st = _style(g, x)
-        if color:
-            st = OP.coral(st, x)
-        which = int(torch.randint(0, 2, size=(1,)))
-        if which == 0:
-            lm = (torch.rand((x.shape[0], 1, 1, 1)) / 2.0 + 0.5).numpy().astype(np.float64)
-            return OP.freq_style_transfer(x, st, lm)
-        lm = (torch.rand((x.shape[0], 1, 1)) / 2.0 + 0.5).numpy().astype(np.float64)
-        return OP.spatial_style_transfer(x, st, lm)
-    which = int(torch.randint(0, 3, size=(1,)))
-    if which == 0:
-        return OP.random_noise(x, torch.normal(0.0, 1e-4, size=x.shape).numpy())
-    assert which == 2
-    return OP.downscale(x)
+    branch, out = replay_branch(x, g["pert_real"], g["pert_fake"], seed, color)
+    assert branch == name.split("_")[0], (name, branch)
+    return out
 
 
 @pytest.mark.parametrize("name,tol", [("noise", 1e-7), ("down", 0.0), ("freq", 2e-6), ("spat", 2e-7),

@@ -83,16 +83,18 @@ __global__ __launch_bounds__(NT) void amp_mix(const float* __restrict__ A, const
         const float ar = A[re_i], ai = A[im_i], br = B[re_i], bi = B[im_i];
         const float ma = hypotf(ar, ai), mb = hypotf(br, bi);
         const float amp = l * ma + (1.0f - l) * mb;
-        const float w = (kx == 0 || kx == S / 2) ? 1.f : 2.f;
+        const float w = (kx == 0 || (kx == S / 2 && (S & 1) == 0)) ? 1.f : 2.f;          // odd S has no Nyquist column
         const float c = ma > 0.f ? ar / ma : 1.f, s = ma > 0.f ? ai / ma : 0.f;
         out[re_i] = w * amp * c;
         out[im_i] = w * amp * s;
     }
 }
 
-// Order-preserving map float -> uint32 (negative: all bits flipped, else sign bit set) and back.
+// Order-preserving map float -> uint32 (negative: all bits flipped, else sign bit set) and back.  -0.0 takes the key of
+// +0.0: the two compare equal, so a stable sort keeps them in index order (and the style's -0.0 comes back as +0.0).
 __device__ __forceinline__ unsigned f2key(float f) {
-    const unsigned u = __float_as_uint(f);
+    unsigned u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float key2f(unsigned k) {
@@ -270,6 +272,17 @@ __global__ __launch_bounds__(SORT_NT) void seg_sort_kernel(const float* __restri
     }
 }
 
+// (c + om * sv) - om * c with every operation rounded to float32 on its own.  hipcc contracts by default, and the _rn
+// intrinsics do not stop it: the headers define them as plain `*`, `+`, `-` compiled under that default (two v_fma_f32 came out
+// of them).  The pragma is lexical, so the operators are written out here.
+__device__ __forceinline__ float efdm_mix(float c, float om, float sv) {
+#pragma clang fp contract(off)
+    const float a = om * sv;
+    const float b = om * c;
+    const float s = c + a;
+    return s - b;
+}
+
 // sorted position j of row r holds content index i = sidx[r][j] and the style value of the same rank:
 // out[r][i] = (c + (1-l) * sv) - (1-l) * c      (model/modules.py:70-73, same operation order, no contraction)
 __global__ __launch_bounds__(NT) void efdm_scatter(const float* __restrict__ content, const unsigned* __restrict__ sidx,
@@ -279,9 +292,9 @@ __global__ __launch_bounds__(NT) void efdm_scatter(const float* __restrict__ con
     for (long e = (long)blockIdx.x * NT + threadIdx.x; e < total; e += (long)gridDim.x * NT) {
         const long r = e / L;
         const long i = r * L + sidx[e];
-        const float om = __fsub_rn(1.0f, lmda[r / rows_per_sample]);
+        const float om = 1.0f - lmda[r / rows_per_sample];
         const float c = content[i], sv = key2f(sk_sorted[e]);
-        out[i] = __fsub_rn(__fadd_rn(c, __fmul_rn(om, sv)), __fmul_rn(om, c));
+        out[i] = efdm_mix(c, om, sv);
     }
 }
 

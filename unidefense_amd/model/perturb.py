@@ -6,8 +6,8 @@ same draws, same order, so a seeded run takes the reference's branches with the 
 SURVEY.md §8(f) rank 1.  The arithmetic runs in HIP kernels (csrc/perturb.hip + the DFT-matrix GEMMs of ud_gemm)
 through the C-ABI; there is no torch-op fallback.  What stays torch: the RNG draws (they DEFINE parity with the
 reference), the style-partner row gather `x[perm]`, the noise field `torch.normal(.., device=x.device)` and the 3x3
-SVDs of the colour transfer (host LAPACK, as in a CPU run of the reference; the reference's `_mat_sqrt` result
-depends on the solver's singular-vector signs, so it is implementation-defined across devices).
+SVDs of the colour transfer (host LAPACK; the reference's `_mat_sqrt` result depends on the solver's singular-vector
+signs, so it is implementation-defined across devices: the signs are those of a CPU run of the reference, float32).
 
 Semantics restated from:
   random_noise / random_blur / downscale      model/modules.py:7-21  (pert_noise = std 1e-4, model/unidefense.py:17)
@@ -101,7 +101,14 @@ def spatial_style_transfer(content, style):
 
 
 def _mat_sqrt(x):
+    """x: fp64 [N, 3, 3].  U sqrt(D) V flips with the sign the solver gives a singular pair, so the reference's value is defined
+    by ITS solver: torch.linalg.svd in float32 (utils/operation.py:15-17).  The signs are taken from that call; the factors
+    from the fp64 one, so that near-degenerate covariances (noise images: three nearly equal singular values) do not cost
+    1e-4 of the transferred image to a single-precision 3 x 3 SVD."""
     u, d, vh = torch.linalg.svd(x)
+    u32 = torch.linalg.svd(x.float())[0].double()
+    sign = torch.where((u * u32).sum(-2) < 0, -1.0, 1.0).to(x.dtype)          # per singular pair
+    u, vh = u * sign[:, None, :], vh * sign[:, :, None]
     # the reference multiplies by the transpose of svd's THIRD output, i.e. by V (utils/operation.py:15-17)
     return u @ torch.diag_embed(d.pow(0.5)) @ vh.transpose(-1, -2)
 
@@ -126,7 +133,7 @@ def coral(source, target):
     A = sqrt(cov_t) inv(sqrt(cov_s)), applied as ONE affine colour map per sample."""
     s_mean, s_std, s_cov = _coral_stats(source)
     t_mean, t_std, t_cov = _coral_stats(target)
-    a = (_mat_sqrt(t_cov.float()) @ torch.linalg.inv(_mat_sqrt(s_cov.float()))).double()
+    a = _mat_sqrt(t_cov) @ torch.linalg.inv(_mat_sqrt(s_cov))
     lin = t_std[:, :, None] * a / s_std[:, None, :]
     off = t_mean - (lin @ s_mean[:, :, None])[:, :, 0]
     m = torch.cat([lin, off[:, :, None]], 2).float().contiguous().to(source.device)
