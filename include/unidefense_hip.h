@@ -814,6 +814,30 @@ int ud_uap_update_linf(float* delta, const float* gsum, const float* x, float* x
 int ud_uap_apply(float* delta, const double* dss, const float* x, float* x_adv, int N, long per, float eps, float lo, float hi,
                  ud_stream_t stream);
 
+/* ---- frequency-band attack (csrc/band.hip; unidefense_amd/band.py: dct2, idct2, BandRunner) -----------------------------------
+ * ud_plane_dct2: the orthonormal 2-D DCT-II of P contiguous fp32 planes [P][S][S], 2 <= S <= 480, any S in between (odd, no
+ *   multiple of 32).  d is D [S][S] row-major (D[u][i] = c_u cos(pi (2 i + 1) u / (2 S)), made in float64 and rounded once), dt
+ *   its transpose, also row-major.  inverse == 0: y_p = mask (.) (D x_p D^T); inverse != 0: y_p = D^T (mask (.) x_p) D.  mask
+ *   [S][S] fp32 may be NULL (bitwise a mask of ones); it multiplies, so a 0 entry gives +-0.  The inverse takes base [P][S][S]
+ *   with clip != 0: y_p = clamp(base_p + D^T (mask (.) x_p) D, lo, hi), one fp32 rounding for the sum, a NaN kept.  Products are
+ *   exact fp32 on the fp32-input MFMA, fp32 accumulation, in an order that depends on S alone: a second launch gives the same
+ *   bits.  One workgroup per (plane, 32-column strip), the strip of the intermediate in LDS; no workspace.  x is only read.
+ *   16-byte loads where S % 4 == 0 and the bases are 16-byte aligned, element loads otherwise.
+ * ud_band_dots: out[n][0..2] = |w[n]|^2, <w[n], g[n]>, |g[n]|^2 for contiguous fp32 [N][per], products and sums in double, one
+ *   pass.  per is cut into fixed 4096-element parts as ud_sample_sumsq cuts it; with more than one part the partial sums go to
+ *   ws (3 ud_sample_sumsq_ws_bytes(N, per) bytes, 0 for one part) and are folded in part order: deterministic.
+ * ud_band_update: in place, with the sample's dots (ww, wg, gg) = dots[n][0..2], all in double and unfused:
+ *   a = step / max(sqrt(gg), 1e-12); n2 = ww + 2 a wg + a a gg; s = min(1, eps / max(sqrt(max(n2, 0)), 1e-12));
+ *   w[n][e] <- (float)(s ((double)w[n][e] + a (double)g[n][e])): the normalised step and the projection onto |w|_2 <= eps in
+ *   one pass, because the stepped point's norm follows from the dots of the old one.  step may be negative.
+ * UD_EINVAL before any HIP call: a NULL pointer (but mask, base, ws for one part), x == y, d == dt, base == y, w == g, S < 2 or
+ *   > 480, P < 1, N < 1 or > 65535, per < 1, base without clip or without inverse, clip without base, lo > hi or NaN, a NaN step,
+ *   eps < 0 or NaN, a ws smaller than 3 ud_sample_sumsq_ws_bytes(N, per). */
+int ud_plane_dct2(const float* x, float* y, const float* d, const float* dt, const float* mask, const float* base, long P, int S,
+                  int inverse, int clip, float lo, float hi, ud_stream_t stream);
+int ud_band_dots(const float* w, const float* g, int N, long per, double* out, double* ws, long ws_bytes, ud_stream_t stream);
+int ud_band_update(float* w, const float* g, const double* dots, int N, long per, float step, float eps, ud_stream_t stream);
+
 /* ---- randomized smoothing (csrc/smooth.hip; unidefense_amd/smooth.py: CertifyRunner) ----------------------------------------
  * One draw of a certificate is a static launch sequence inside a captured graph: noise, forward, vote.
  * ud_smooth_noise: out[n][e] = x[n][e] + scale noise(n, e) for contiguous fp32 [N][per]; out may be x itself (no other overlap).

@@ -1,4 +1,4 @@
-"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal / test_flow / test_certified / test_attribution: one scoring
+"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal / test_flow / test_band / test_certified / test_attribution: one scoring
 forward, one batch source, one loop-and-gather, one metrics dictionary, and a table of test_robust's methods.  The Evaluator
 takes its model and iterator as arguments and imports nothing that loads the HIP library, so the stage rules run on the CPU
 against stubs (tests/test_evaluate_cpu.py, tests/test_universal_cpu.py).  What every stage keeps: its order inside a batch, who owns which generator, the sequence of
@@ -200,6 +200,66 @@ class Evaluator:
         args = dict(runner.args, flow_linf_mean=float(linf.mean()), flow_linf_max=float(linf.max()), flow_tv_mean=float(tv.mean()),
                     flow_tv_max=float(tv.max()), fooled=float(wrong[right].double().mean()) if bool(right.any()) else float("nan"))
         return self._result(cols, "Test(flow)", args)
+
+    def test_band(self, batches, band, band_filter=None):
+        """band_filter: band.band_filter unless a caller (a CPU test) brings a host stand-in"""
+        from .. import band as BD
+        band = dict(band) if band else {}
+        bands = band.pop("bands", None)
+        bands = list(BD.DEFAULT_BANDS if bands is None else bands)
+        if not batches >= 1 or int(batches) != batches:
+            raise ValueError(f"batches must be an integer >= 1, got {batches!r}")
+        for key in ("band", "mask"):
+            if key in band:
+                raise ValueError(f"band takes BandRunner's keyword arguments and 'bands': the stage sets {key!r} itself, per band")
+        if not bands or any(not isinstance(b, (tuple, list)) or len(b) != 2 for b in bands):
+            raise ValueError(f"bands must be a list of (lo, hi) pairs, got {bands!r}")
+        bands = [tuple(b) for b in bands]
+        # every mask before any batch (a bad band or shape is refused here); the last is the control's: the full spectrum
+        masks = [BD.band_mask(self.size, lo, hi, band.get("shape", "radial")).to(self.device) for lo, hi in bands]
+        masks.append(torch.ones_like(masks[0]))
+        clip = band.get("clip", (-1.0, 1.0))
+        try:                                             # only the binding is wrapped: an unknown key is a bad dict, like a bad value
+            BD._band_arguments(2 * self.batch, self.size, mask=masks[-1], **band)
+        except TypeError as e:
+            raise ValueError(f"band takes BandRunner's keyword arguments and 'bands': {e}") from None
+        # ONE runner (one pair of graphs) for the control and every band, and for every later call with these arguments: it
+        # owns its mask, and the stage refills it through set_mask before each attack
+        runner = self.net.band_runner(2 * self.batch, self.size, mask=masks[-1], **band)
+        band_filter = band_filter or BD.band_filter
+        names = ["control"] + list(range(len(bands)))
+
+        def body(x, y):                                  # clean; the control; then per band: attacked, leak, removed
+            cols = {"clean": self.score(x)}
+            for name, m in zip(names, masks[-1:] + masks[:-1]):
+                runner.set_mask(m)
+                cols[("adv", name)] = self.score(runner(x, y))
+                cols[("leak", name)] = runner.leak.clone()           # the runner reuses its buffers
+                if name != "control":
+                    cols[("removed", name)] = self.score(band_filter(x, 1.0 - m, clip))
+            return cols
+
+        cols = self.run(int(batches), body)
+        labels = cols["clean"][1]
+        right = (cols["clean"][0] < 0.5).long() == labels
+
+        def fooled(name):
+            wrong = (cols[("adv", name)][0] < 0.5).long() != labels
+            return float(wrong[right].double().mean()) if bool(right.any()) else float("nan")
+
+        def row(name, tag):
+            return {"adv": self.metrics(*cols[("adv", name)], "Test(%s)" % tag), "fooled": fooled(name),
+                    "leak": float(cols[("leak", name)][0].double().mean())}
+
+        ret = {"clean": self.metrics(*cols["clean"], "Test"), "control": row("control", "band control"), "bands": [],
+               "attack": dict(runner.args, bands=bands)}
+        for i, (lo, hi) in enumerate(bands):
+            tag = "band %g-%s" % (lo, "inf" if hi is None else "%g" % hi)
+            ret["bands"].append(dict(row(i, tag), band=(lo, hi), removed=self.metrics(*cols[("removed", i)], "Test(%s removed)" % tag)))
+            if self.local_rank == 0:
+                print("%-17s | fooled %.4f (control %.4f), leak %.3g" % (
+                    tag.capitalize(), ret["bands"][i]["fooled"], ret["control"]["fooled"], ret["bands"][i]["leak"]))
+        return ret
 
     def test_certified(self, batches, certify):
         from ..smooth import certified_curve

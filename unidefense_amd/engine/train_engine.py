@@ -297,6 +297,22 @@ class TrainEngine(AbstractEngine):
         gathered over the ranks as in test(), in this order."""
         return self._evaluator().test_flow(batches, flow if flow is not None else self.config["config"].get("flow"))
 
+    def test_band(self, batches=4, band=None):
+        """In which frequency band the model is fragile (unidefense_amd/band.py): every test batch is scored as test() does
+        (inference_graph / inference_precision keep their meaning), then attacked with the true labels by the model's BandRunner
+        — L2 PGD whose perturbation is confined to one band of the image's 2-D DCT — once per band at the SAME eps, and once with
+        a mask of ones: the full-spectrum control, which is plain L2 PGD.  Per band the batch is also scored with the band REMOVED
+        and nothing attacked (band_filter(x, 1 - mask)).  band (default config['config']['band']): the runner's keyword arguments,
+        e.g. {"eps": 1.0, "steps": 10, "shape": "radial"}, plus "bands", a list of (lo, hi) in cycles per pixel over the DCT's
+        [0, 1) axis (default [(0, 1/8), (1/8, 1/4), (1/4, 1/2), (1/2, None)]); "precision": "fp16" (UDEB4) runs the attack's
+        frozen pass in half storage.  One runner serves every band: it owns its mask and the stage refills it (set_mask).  Returns {"clean": what
+        test() returns, "control": {"adv": the same keys on the control's x_adv, "fooled": the fraction of the samples classified
+        correctly clean that it flips (NaN where there are none), "leak": the mean share of |x_adv - x|^2 outside the band after
+        the clip}, "bands": one such row per band plus "band" and "removed" (test()'s keys with the band filtered out), "attack":
+        the resolved arguments and "bands"}.  Scores are gathered over the ranks as in test(): clean, then the control's and
+        each band's columns in order."""
+        return self._evaluator().test_band(batches, band if band is not None else self.config["config"].get("band"))
+
     def test_certified(self, batches=4, certify=None):
         """A LOWER bound on robustness, where test_robust gives upper bounds (unidefense_amd/smooth.py): every test batch is scored
         as test() does (inference_graph / inference_precision keep their meaning), then certified by the model's CertifyRunner —

@@ -1960,6 +1960,60 @@ def uap_apply(delta, dss, x, x_adv, eps, lo, hi):
     return x_adv
 
 
+# ---- frequency-band attack (csrc/band.hip): planes fp32 [..., S, S]; d / dt: band.dct_matrix(S) and its transpose, fp32 [S, S] ----
+def plane_dct2(x, d, dt, mask=None, inverse=False, out=None, base=None, clip=None):
+    """out = mask (.) (D x D^T) for every [S, S] plane of x (inverse: D^T (mask (.) x) D); mask [S, S] or None.  The inverse with
+    base (like x) and clip (lo, hi): out = clamp(base + ..., lo, hi).  out: a new tensor unless given (never x)."""
+    _chk(x, d, dt, mask, base, out)
+    if x.dim() < 2 or x.shape[-1] != x.shape[-2] or x.numel() == 0:
+        raise ValueError(f"expected [..., S, S] planes, got {tuple(x.shape)}")
+    S = x.shape[-1]
+    if any(t is not None and tuple(t.shape) != (S, S) for t in (d, dt, mask)):
+        raise ValueError(f"d, dt and mask must be [{S}, {S}], got {[None if t is None else tuple(t.shape) for t in (d, dt, mask)]}")
+    if (base is None) != (clip is None) or (base is not None and (not inverse or base.shape != x.shape)):
+        raise ValueError("base (a tensor like x) and clip (lo, hi) go together, on the inverse transform")
+    out = torch.empty_like(x) if out is None else out
+    if out.shape != x.shape:
+        raise ValueError(f"out {tuple(out.shape)} differs from x {tuple(x.shape)}")
+    lo, hi = (0.0, 0.0) if clip is None else (float(clip[0]), float(clip[1]))
+    _call("ud_plane_dct2", _p(x), _p(out), _p(d), _p(dt), _p(mask), _p(base), x.numel() // (S * S), S, int(bool(inverse)),
+          int(clip is not None), lo, hi, _stream())
+    return out
+
+
+def band_dots_ws_bytes(N, per):
+    """three sums per part of ud_sample_sumsq's partition"""
+    return 3 * sample_sumsq_ws_bytes(N, per)
+
+
+def band_dots(w, g, out=None, ws=None):
+    """out[n] = (|w[n]|^2, <w[n], g[n]>, |g[n]|^2) in double, deterministic.  out [N, 3] float64 and ws (a float64 scratch of
+    band_dots_ws_bytes(N, per) bytes) are allocated unless given (a graph-captured caller gives its own)."""
+    _chk_same(w, g)
+    N = w.shape[0]
+    per = w.numel() // N
+    need = band_dots_ws_bytes(N, per)
+    if out is None:
+        out = torch.empty(N, 3, dtype=torch.float64, device=w.device)
+    _chk_f64(out, 3 * N)
+    if ws is None and need:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=w.device)
+    if need:
+        _chk_f64(ws, need // 8)
+    _call("ud_band_dots", _p(w), _p(g), N, per, _p(out), _p(ws) if need else None, ws.numel() * 8 if need else 0, _stream())
+    return out
+
+
+def band_update(w, g, dots, step, eps):
+    """In place: w[n] <- s (w[n] + a g[n]) with a = step / max(|g[n]|, 1e-12) and s the factor that puts the stepped point onto
+    |.|_2 <= eps, both formed in double from dots [N, 3] float64 (band_dots(w, g))."""
+    _chk_same(w, g)
+    N = w.shape[0]
+    _chk_f64(dots, 3 * N)
+    _call("ud_band_update", _p(w), _p(g), _p(dots), N, w.numel() // N, float(step), float(eps), _stream())
+    return w
+
+
 # ---- flow-field attack (csrc/flow.hip): images fp32 [N, 3, S, S], flows fp32 [N, 2, S, S] in pixels (column, row) ---------------
 FLOW_I = _rows("UD_FLOW_I_")
 FLOW_F = {"f_best": _const("UD_FLOW_F_BEST")}

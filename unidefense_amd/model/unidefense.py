@@ -290,6 +290,13 @@ class RunnerMethods:
         from ..flow import flow_runner
         return flow_runner(self, batch, size, **kwargs)
 
+    def band_runner(self, batch, size, **kwargs):
+        """The graph-replayed frequency-band attack — L2 PGD whose perturbation is confined to one band of the image's 2-D DCT —
+        for [batch, 3, size, size] inputs (unidefense_amd/band.py: BandRunner; kwargs: band, shape, mask, eps, steps, step,
+        targeted, clip, objective, precision, grad_scale)."""
+        from ..band import band_runner
+        return band_runner(self, batch, size, **kwargs)
+
     def certify_runner(self, batch, size, **kwargs):
         """The graph-replayed randomized-smoothing certificate — per sample a radius inside which the smoothed decision provably
         does not change — for [batch, 3, size, size] inputs (unidefense_amd/smooth.py: CertifyRunner; kwargs: sigma, noise, n0, n,
