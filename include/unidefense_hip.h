@@ -814,6 +814,45 @@ int ud_uap_update_linf(float* delta, const float* gsum, const float* x, float* x
 int ud_uap_apply(float* delta, const double* dss, const float* x, float* x_adv, int N, long per, float eps, float lo, float hi,
                  ud_stream_t stream);
 
+/* ---- adversarial patch (csrc/patch.hip; unidefense_amd/patch.py: paste, PatchRunner) ------------------------------------------
+ * ONE texture patch fp32 [3][P][P] with a fixed coverage mask alpha fp32 [P][P] in [0, 1], pasted into every sample of x fp32
+ * [N][3][S][S] under the sample's own placement.  table [rows][N][UD_PATCH_ROW] int32 and k (one int32) are DEVICE data: sample n
+ * uses the row table[clamp(k[0], 0, rows - 1)][n].  The clamp is part of the contract, as are reach clamped into
+ * [0, UD_PATCH_MAX_REACH], the window cut to the image and every tap tested against the texture: the host cannot see the table
+ * at launch, and the kernels stay in bounds for any content of it.  (The host side that MAKES a table, patch.placement_q16 and
+ * patch.check_table, refuses a row with reach > UD_PATCH_MAX_REACH or a non-zero reserved word before it is uploaded.)
+ * A row (patch.placement_q16), pixel and texel centres on the integers, x to the right, y down, t0 = (P - 1) / 2, the forward
+ * map p = s R(angle) (t - t0) + centre, made in float64 and quantised as floor(v 65536 + 0.5):
+ *     words 0..5   m00 m01 o0 m10 m11 o1: the INVERSE map, texel column = m00 c + m01 r + o0, texel row = m10 c + m11 r + o1
+ *     words 6..11  the FORWARD map likewise: pixel column from (texel column j, texel row i), then the pixel row
+ *     word  12     reach = floor(s sqrt(2) (1 + 2^-7)) + 2;   words 13..15 zero
+ * Weights.  For the output pixel (r, c): U = m00 c + m01 r + o0, V = m10 c + m11 r + o1 in int64; j0 = U >> 16, fx = (U >> 8) & 255,
+ *   i0 = V >> 16, fy = (V >> 8) & 255 (arithmetic shifts).  The four taps, in this order: (i0, j0), (i0, j0 + 1), (i0 + 1, j0),
+ *   (i0 + 1, j0 + 1), with the integer weights w = wx wy / 65536, wx = 256 - fx | fx, wy = 256 - fy | fy: exact dyadics.  The tap
+ *   weight is omega = fl32(w alpha[i][j]), ONE rounding, the only weight either direction uses.  A tap outside [0, P - 1]^2 is
+ *   absent, and so is a tap whose omega is zero (so a NaN texel shows exactly where it has weight).
+ * ud_patch_paste: cov = sum omega, acc_ch = sum omega patch[ch][i][j], both fp32 from 0.f over the present taps in tap order,
+ *   the product rounded, then the sum, no fused multiply-add; out = clamp((1 - cov) x + acc, lo, hi) (difference, product, sum:
+ *   one rounding each; the clamp keeps a NaN).  A pixel with no present tap, or cov == 0, gets x's own bits, unclamped.  One
+ *   launch, one thread per pixel for the three channels; x is only read; out != x.
+ * ud_patch_grad: the adjoint with respect to the texture, per sample, as a GATHER.  For sample n and the texel (i, j): the pixel
+ *   nearest its forward image, pc = (f00 j + f01 i + fo0 + 32768) >> 16, pr likewise (int64); the window [pr - reach, pr + reach] x
+ *   [pc - reach, pc + reach] cut to the image, walked in row-major order; every candidate pixel evaluates the weights above and
+ *   keeps the tap that names (i, j), if any; gp[n][ch][i][j] = fl32(sum of (double) omega (double) g[n][ch][r][c]), the sum in
+ *   double in the walk's order, rounded ONCE.  Every element of gp fp32 [N][3][P][P] is written, zeros included.  No atomics, no
+ *   workspace: a replay gives the same bits.  gp != g.
+ * ud_patch_update: patch[e] <- clamp(patch[e] + step sign(gsum[e]), lo, hi) for e < per, sign(0) = 0, a NaN in gsum becomes a NaN
+ *   in patch: bitwise the torch fp32 expression.  gsum != patch.
+ * UD_EINVAL before any HIP call: a NULL pointer, out == x, gp == g, gsum == patch, N < 1 or > 65535, S < 2 or > 32768, P < 1 or
+ * > 256, rows < 1, per < 1 or > 3 256^2, lo > hi or NaN, a NaN step. */
+#define UD_PATCH_ROW 16
+#define UD_PATCH_MAX_REACH 8
+int ud_patch_paste(const float* x, const float* patch, const float* alpha, const int* table, const int* k, int rows, float* out,
+                   int N, int S, int P, float lo, float hi, ud_stream_t stream);
+int ud_patch_grad(const float* g, const float* alpha, const int* table, const int* k, int rows, float* gp, int N, int S, int P,
+                  ud_stream_t stream);
+int ud_patch_update(float* patch, const float* gsum, long per, float step, float lo, float hi, ud_stream_t stream);
+
 /* ---- frequency-band attack (csrc/band.hip; unidefense_amd/band.py: dct2, idct2, BandRunner) -----------------------------------
  * ud_plane_dct2: the orthonormal 2-D DCT-II of P contiguous fp32 planes [P][S][S], 2 <= S <= 480, any S in between (odd, no
  *   multiple of 32).  d is D [S][S] row-major (D[u][i] = c_u cos(pi (2 i + 1) u / (2 S)), made in float64 and rounded once), dt

@@ -1,4 +1,4 @@
-"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal / test_flow / test_band / test_certified / test_attribution: one scoring
+"""The evaluation stages behind TrainEngine.test / test_robust / test_corrupted / test_spatial / test_universal / test_patch / test_flow / test_band / test_certified / test_attribution: one scoring
 forward, one batch source, one loop-and-gather, one metrics dictionary, and a table of test_robust's methods.  The Evaluator
 takes its model and iterator as arguments and imports nothing that loads the HIP library, so the stage rules run on the CPU
 against stubs (tests/test_evaluate_cpu.py, tests/test_universal_cpu.py).  What every stage keeps: its order inside a batch, who owns which generator, the sequence of
@@ -176,6 +176,55 @@ class Evaluator:
         args = dict(args, delta=d, linf=float(d.abs().max()), l2=float(d.double().norm()), fooled=fooled("adv"),
                     fooled_control=fooled("control"), fit_counted=[int(c) for c in torch.cat(counted).cpu()])
         return dict(self._result(cols, "Test(universal)", args), control=self.metrics(*cols["control"], "Test(control)"))
+
+    def test_patch(self, batches, fit_batches, epochs, patch, paste=None):
+        """paste: patch.paste unless a caller (a CPU test) brings a host stand-in"""
+        from .. import patch as PT
+        patch = dict(patch) if patch else {}
+        seed = patch.pop("seed", None)
+        for name, v in (("batches", batches), ("fit_batches", fit_batches), ("epochs", epochs)):
+            if not v >= 1 or int(v) != v:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            patch.setdefault("reduce", dist.all_reduce)          # every rank sums gsum in place: the same patch everywhere
+        try:                                             # ONE runner holds the patch; every refusal before the first batch
+            runner = self.net.patch_runner(2 * self.batch, self.size, **patch)
+        except TypeError as e:                           # an unknown key is a bad dict, like a bad value
+            raise ValueError(f"patch takes PatchRunner's keyword arguments and 'seed': {e}") from None
+        paste = paste or PT.paste
+        generator = None if seed is None else torch.Generator().manual_seed(int(seed))     # one CPU generator per call
+        runner.reset()
+        counted = []
+        for _ in range(int(epochs)):                     # the fit: the iterator's steps 1 .. fit_batches, epochs times over
+            for x, y in self.batches(int(fit_batches)):
+                runner(x, y, generator)
+                counted.append(runner.counted.sum(1))
+        # the two controls, made once: a patch fitted on nothing, and one that only hides what is under it
+        args = runner.args
+        texture, alpha, (lo, hi) = runner.patch, runner.alpha, args["clip"]
+        random = (torch.rand(tuple(texture.shape), generator=generator, dtype=torch.float32) * (hi - lo) + lo).to(texture.device)
+        middle = torch.full_like(texture, 0.5 * (lo + hi))
+
+        def body(x, y):                                  # the held-out steps, scored four ways at ONE draw of placements
+            table = PT.patch_placements(x.shape[0], self.size, args["patch"], args["max_angle"], args["scales"], args["region"],
+                                        generator)[1]
+            return {"clean": self.score(x), "adv": self.score(runner.apply(x, table=table)),
+                    "random": self.score(paste(x, random, table, alpha, (lo, hi))),
+                    "occlusion": self.score(paste(x, middle, table, alpha, (lo, hi)))}
+
+        cols = self.run(int(batches), body, first=int(fit_batches) + 1)
+        labels = cols["clean"][1]
+        right = (cols["clean"][0] < 0.5).long() == labels
+
+        def fooled(name):
+            wrong = (cols[name][0] < 0.5).long() != labels
+            return float(wrong[right].double().mean()) if bool(right.any()) else float("nan")
+
+        args = dict(args, texture=texture.detach().cpu(), fooled=fooled("adv"), fooled_random=fooled("random"),
+                    fooled_occlusion=fooled("occlusion"), fit_counted=[int(c) for c in torch.cat(counted).cpu()])
+        return dict(self._result(cols, "Test(patch)", args), random=self.metrics(*cols["random"], "Test(random patch)"),
+                    occlusion=self.metrics(*cols["occlusion"], "Test(occlusion)"))
 
     def test_flow(self, batches, flow):
         flow = dict(flow) if flow else {}

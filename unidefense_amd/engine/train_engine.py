@@ -285,6 +285,23 @@ class TrainEngine(AbstractEngine):
         universal = universal if universal is not None else self.config["config"].get("universal")
         return self._evaluator().test_universal(batches, fit_batches, epochs, universal)
 
+    def test_patch(self, batches=4, fit_batches=4, epochs=2, patch=None):
+        """What ONE sticker costs wherever it lands (unidefense_amd/patch.py): the model's PatchRunner is reset and fitted on the
+        test iterator's steps 1 .. fit_batches, `epochs` times over, with the true labels, at freshly drawn placements; the
+        held-out steps fit_batches + 1 .. fit_batches + batches are then scored as test() does (inference_graph /
+        inference_precision keep their meaning) four ways, all at the SAME freshly drawn placements: clean, with the fitted patch
+        (runner.apply), with a uniform-random patch, and with a constant mid-range patch, which is plain occlusion.  patch
+        (default config['config']['patch']): the runner's keyword arguments, e.g. {"patch": 48, "shape": "circle", "steps": 1};
+        an optional "seed" seeds the one CPU generator of the placements and the random control.  Returns {"clean", "adv",
+        "random", "occlusion": what test() returns, "attack": the resolved arguments (with "area", the patch's nominal share
+        of the image) plus "texture" (CPU [3, P, P]), "fooled" (the fraction of the held-out samples classified correctly clean
+        that the patch flips; NaN where there are none), "fooled_random", "fooled_occlusion" and "fit_counted" (the samples that
+        steered each fit iteration, this rank's)}.  Under data parallel every rank's gradient sum is all-reduced inside the
+        iteration, so all ranks hold the same patch; scores are gathered as in test(), in the order clean, adv, random,
+        occlusion."""
+        patch = patch if patch is not None else self.config["config"].get("patch")
+        return self._evaluator().test_patch(batches, fit_batches, epochs, patch)
+
     def test_flow(self, batches=4, flow=None):
         """test() on clean inputs and on each sample's flow-field (stAdv) adversarial image (unidefense_amd/flow.py): every test
         batch is scored as test() does (inference_graph / inference_precision keep their meaning), attacked with the true labels

@@ -1960,6 +1960,69 @@ def uap_apply(delta, dss, x, x_adv, eps, lo, hi):
     return x_adv
 
 
+# ---- adversarial patch (csrc/patch.hip): one texture patch [3, P, P] and mask alpha [P, P] for [N, 3, S, S] batches ---------------
+PATCH_ROW = _const("UD_PATCH_ROW")
+PATCH_MAX_REACH = _const("UD_PATCH_MAX_REACH")
+
+
+def _chk_patch(x, alpha, table, k, P):
+    """x [N, 3, S, S], alpha [P, P], table [rows, N, PATCH_ROW] int32 (made and checked by patch.placement_q16 / check_table
+    before its upload), k [>= 1] int32 whose first value names the row: (N, S, rows)"""
+    _chk(x, alpha)
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[0] < 1 or x.shape[2] < 2:
+        raise ValueError(f"expected [N, 3, S, S] images with N >= 1 and S >= 2, got {tuple(x.shape)}")
+    N, S = x.shape[0], x.shape[2]
+    if tuple(alpha.shape) != (P, P):
+        raise ValueError(f"alpha must be [{P}, {P}], got {tuple(alpha.shape)}")
+    if table.dim() != 3 or table.shape[0] < 1:
+        raise ValueError(f"table must be [rows, {N}, {PATCH_ROW}] with rows >= 1, got {tuple(table.shape)}")
+    _chk_i32(table, (table.shape[0], N, PATCH_ROW), "table")
+    if not (k.is_cuda and k.dtype == torch.int32 and k.is_contiguous() and k.numel() >= 1):
+        raise ValueError(f"k must be a contiguous int32 CUDA tensor of at least one value, got {k.dtype} {k.device} {tuple(k.shape)}")
+    return N, S, table.shape[0]
+
+
+def _chk_texture(patch):
+    _chk(patch)
+    if patch.dim() != 3 or patch.shape[0] != 3 or patch.shape[1] != patch.shape[2] or patch.shape[1] < 1:
+        raise ValueError(f"a patch is [3, P, P], got {tuple(patch.shape)}")
+    return patch.shape[1]
+
+
+def patch_paste(x, patch, alpha, table, k, out, lo, hi):
+    """out = x with the patch pasted into sample n under the placement table[clamp(k[0], 0, rows - 1), n] (the header's rule:
+    bitwise patch.ref_patch_paste); x's own bits wherever the patch has no weight; one launch, x only read, out is not x."""
+    _chk_same(x, out)
+    P = _chk_texture(patch)
+    N, S, rows = _chk_patch(x, alpha, table, k, P)
+    _chk_apart(x=x, out=out)
+    _call("ud_patch_paste", _p(x), _p(patch), _p(alpha), _p(table), _p(k), rows, _p(out), N, S, P, float(lo), float(hi), _stream())
+    return out
+
+
+def patch_grad(g, alpha, table, k, gp):
+    """gp[n] = the adjoint of patch_paste with respect to the patch at sample n's placement, applied to g[n]: a gather, sums in
+    double rounded once, every element of gp [N, 3, P, P] written; a second launch gives the same bits."""
+    _chk(gp)
+    if gp.dim() != 4 or gp.shape[1] != 3 or gp.shape[2] != gp.shape[3]:
+        raise ValueError(f"gp must be [N, 3, P, P], got {tuple(gp.shape)}")
+    P = gp.shape[2]
+    N, S, rows = _chk_patch(g, alpha, table, k, P)
+    if gp.shape[0] != N:
+        raise ValueError(f"gp must be [{N}, 3, {P}, {P}], got {tuple(gp.shape)}")
+    _call("ud_patch_grad", _p(g), _p(alpha), _p(table), _p(k), rows, _p(gp), N, S, P, _stream())
+    return gp
+
+
+def patch_update(patch, gsum, step, lo, hi):
+    """In place: patch <- clamp(patch + step sign(gsum), lo, hi), bitwise the torch fp32 expression; sign(0) = 0, a NaN in gsum
+    becomes a NaN in patch."""
+    _chk_same(patch, gsum)
+    _chk_apart(patch=patch, gsum=gsum)
+    _call("ud_patch_update", _p(patch), _p(gsum), patch.numel(), float(step), float(lo), float(hi), _stream())
+    return patch
+
+
 # ---- frequency-band attack (csrc/band.hip): planes fp32 [..., S, S]; d / dt: band.dct_matrix(S) and its transpose, fp32 [S, S] ----
 def plane_dct2(x, d, dt, mask=None, inverse=False, out=None, base=None, clip=None):
     """out = mask (.) (D x D^T) for every [S, S] plane of x (inverse: D^T (mask (.) x) D); mask [S, S] or None.  The inverse with

@@ -283,6 +283,13 @@ class RunnerMethods:
         from ..universal import universal_runner
         return universal_runner(self, batch, size, **kwargs)
 
+    def patch_runner(self, batch, size, **kwargs):
+        """The graph-replayed adversarial patch — one small texture pasted into every image at a random place, roll and size,
+        held by the runner across calls — for [batch, 3, size, size] inputs (unidefense_amd/patch.py: PatchRunner; kwargs:
+        patch, shape, alpha, steps, step, max_angle, scales, region, beta, source, clip, precision, grad_scale, reduce)."""
+        from ..patch import patch_runner
+        return patch_runner(self, batch, size, **kwargs)
+
     def flow_runner(self, batch, size, **kwargs):
         """The graph-replayed flow-field (stAdv) attack — a per-pixel displacement field of at most max_flow pixels, ascended
         through a differentiable warp — for [batch, 3, size, size] inputs (unidefense_amd/flow.py: FlowRunner; kwargs: max_flow,
